@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: MPC-steps/sec of the batched closed-loop rollout (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One bench "step" = one pass of the hot path over one batch, as BASELINE.md section 4 defines the metric
@@ -18,9 +18,15 @@ The kernel-only rate (HIP events around the rollout launch on its stream) is rep
 `kernel_steps_per_s`; `roofline` is computed from that kernel time.  Weak scaling: every rank (one per GPU) runs
 its own batch of 256; the only exchange is the final gather.
 
-The CPU baseline (oracle port, `-O3 -march=native`, built on this host) is measured in a child process that
-is started BEFORE this process touches torch / HIP (no fork of a process with a live HIP runtime) and that
-waits for the GPU measurement to finish before it starts its own (the two never compete for the host cores).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the
+line.  `--full` adds the measurements that are not the headline: the CPU baseline (`cpu_baseline`) and the throughput
+geometry (`secondary`); without it both are null / absent.  The CPU baseline (oracle port, `-O3 -march=native`, built on
+this host) is measured in a child process that is started BEFORE this process touches torch / HIP (no fork of a process
+with a live HIP runtime) and that waits for the GPU measurement to finish before it starts its own (the two never compete
+for the host cores).
+
+`--dump-outputs DIR` writes, after the timed steps, the result arrays the last timed step returned as DIR/<name>.npy in
+float64 (see dump_outputs), so that two builds can be compared output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -75,6 +81,46 @@ def pmc_traffic(batch, N, Nsim, solver):
         except (OSError, ValueError, KeyError):
             pass
     return None, None
+
+
+# ------------------------------------------------------------------------------------------- outputs
+DUMP_BUDGET_BYTES = 64_000_000
+# measured device clocks, not computed results: they differ from run to run, so they are left out of the dump
+DUMP_TIMING_ARRAYS = ("solver_time", "plant_time")
+DUMP_SUMMARY_TIMING_COLS = ("total_solver_time", "avg_mpc_time", "avg_solver_time", "avg_integration_time",
+                            "total_computation_time")
+
+
+def dump_outputs(outputs, out_dir: str, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Writes the per-simulation result arrays `outputs` (name -> array [batch, ...]) as out_dir/<name>.npy in float64,
+    without the timing arrays and, of `summary`, only the named columns that are not timings (engine.SUMMARY_COLS order).
+    When they hold more than `budget` bytes, every array keeps the same fixed sample of simulations (rng(0), in index
+    order), as many as fit.  Returns what was written."""
+    from robotic_mpc_amd import engine
+
+    arrays = {}
+    for k, v in outputs.items():
+        if k in DUMP_TIMING_ARRAYS:
+            continue
+        a = np.asarray(v, dtype=np.float64)
+        if k == "summary":
+            keep = [i for i, c in enumerate(engine.SUMMARY_COLS) if c not in DUMP_SUMMARY_TIMING_COLS]
+            a = a[:, keep]
+        arrays[k] = a
+    batch = {a.shape[0] for a in arrays.values()}
+    assert len(batch) == 1, "every output array is per simulation"
+    batch = batch.pop()
+    per_sim = sum(a[0].nbytes for a in arrays.values())
+    n = min(batch, (budget - 128 * len(arrays)) // per_sim)     # (128: the .npy header of each file)
+    if n < 1:
+        raise SystemExit(f"--dump-outputs: one simulation's outputs ({per_sim} bytes) exceed the {budget}-byte budget")
+    idx = np.arange(batch) if n == batch else np.sort(np.random.default_rng(0).choice(batch, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a[idx]))
+    return {"dir": out_dir, "arrays": sorted(arrays), "dtype": "float64", "simulations": int(n), "of": int(batch),
+            "sample": "all" if n == batch else "rng(0) choice without replacement, in index order",
+            "left_out": list(DUMP_TIMING_ARRAYS) + [f"summary.{c}" for c in DUMP_SUMMARY_TIMING_COLS]}
 
 
 # ------------------------------------------------------------------------------------------- CPU baseline (child)
@@ -339,7 +385,15 @@ def main():
                          "sharded over the ranks (strong scaling)")
     ap.add_argument("--results", default="full", choices=["full", "summary"], help="config2: what run_all gathers to rank 0")
     ap.add_argument("--coeff-sets", type=int, default=256, help="config2: surface coefficient sets (x 16 grid points)")
+    ap.add_argument("--full", action="store_true", help="also measure what is not the headline: the CPU baseline "
+                    "(cpu_baseline) and the throughput geometry (secondary); a plain run leaves them out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="config1: write the result arrays of the last timed step as "
+                    "DIR/<name>.npy (float64, at most 64 MB: a fixed sample of the simulations when they hold more)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "config1":
+        ap.error("--dump-outputs is implemented for the config1 workload")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)      # plain `python bench.py --gpus N`: start the N ranks ourselves (no torch / HIP touched yet)
@@ -348,7 +402,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     cpu_proc = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu_proc = start_cpu_baseline(args)      # before the first torch / HIP call of this process
 
     import torch
@@ -485,7 +539,11 @@ def main():
                      "fp64_valu_frac": flops_step * steps_per_pass / avg_kernel_s / 1e12 / FP64_VALU_PEAK_TFLOPS,
                      "vgprs": info["vgprs"], "lds_bytes": info["lds_bytes"], "scratch_bytes": info["scratch_bytes"]},
     }
-    if rank == 0 and not multi and not args.no_secondary:
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step returned; with --kernel-only the results stayed in HBM (the rollout's buffers)
+        outputs = host if host is not None else {k: v.cpu().numpy() for k, v in bufs.items()}
+        line["config"]["outputs_dumped"] = dump_outputs(outputs, args.dump_outputs)
+    if rank == 0 and not multi and args.full and not args.no_secondary:
         # outside the timed region, for the record: the throughput geometry in the same process
         line["secondary"] = throughput_leg(eng, chain, args)
     if rank == 0:

@@ -13,7 +13,7 @@ import pytest
 
 import helpers as hp
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 # ----------------------------------------------------------------------------- kinematics
@@ -85,13 +85,13 @@ def test_fk_sympy_exact(orc, ur10, ur10_rb):
         np.testing.assert_allclose(pose[3:].reshape(3, 3), Tn[:3, :3], atol=2e-15)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 def test_builtin_constants_match_reference_urdf():
+    """tests/golden/ur*.urdf: the kinematic joints of the reference's ur_description URDFs, copied verbatim."""
     from robotic_mpc_amd import robots
 
     for name, frame in (("ur10", "ee_link"), ("ur5", "tool0")):
         a = robots.builtin_chain(name)
-        b = robots.chain_from_urdf(f"{REF}/ur_description/urdf/{name}.urdf", frame)
+        b = robots.chain_from_urdf(os.path.join(GOLDEN, f"{name}.urdf"), frame)
         assert np.array_equal(a.place, b.place) and np.array_equal(a.axis, b.axis)
 
 
