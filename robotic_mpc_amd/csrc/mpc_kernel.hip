@@ -615,11 +615,7 @@ int mpcb_setup(mpcb_handle *h, const mpcb_problem *p, const double *params_host,
         // streaming path 730 k steps/s; as one per CU with the LDS-resident factor, the grid running in two rounds, 640 k: two
         // factorisation chains side by side on a CU beat one faster one, so the residency target stays 2 beyond #CUs.)
         if (const char *e2 = getenv("MPCB_SIMS_PER_CU")) { const int v = atoi(e2); if (v >= 1 && v <= 8) wpc = v; }
-        const int lds_total = 160 * 1024, fixed = (int)sizeof(Smem) + 64;
-        int bytes = lds_total / (wpc < 1 ? 1 : wpc) - fixed;
-        if (bytes > POOL_DEFAULT_DOUBLES * 8) bytes = POOL_DEFAULT_DOUBLES * 8;
-        if (bytes < POOL_MIN_DOUBLES * 8) bytes = POOL_MIN_DOUBLES * 8;
-        h->pool_doubles = (bytes / 16) * 2;
+        h->pool_doubles = lay_pool_doubles(wpc);
         // wavefronts per simulation: the four SIMDs of a CU are otherwise idle at one simulation per CU
         const char *env = getenv("MPCB_WAVES_PER_SIM");
         // one simulation per CU: 4 wavefronts, 512 registers; beyond: two 4-wavefront simulations per CU at 256 registers

@@ -220,5 +220,16 @@ struct Smem {
 // Chunk pool sizes (doubles).  The widest pass needs ~500 doubles per stage (+1 halo stage).
 constexpr int POOL_MIN_DOUBLES = 2048;
 constexpr int POOL_DEFAULT_DOUBLES = 19456;  // 152 KiB cap: one simulation per CU (batch <= 256 per GPU) gets all the LDS left beside Smem
+constexpr int LDS_CU_BYTES = 160 * 1024;
+// The chunk pool of one simulation when `sims_per_cu` simulations share a CU's LDS (mpcb_setup; the boundary tests read the same
+// function through tests/emu): what is left beside Smem, capped at the default, at least the minimum, in whole 16-byte items.
+MPC_HD int lay_pool_doubles(int sims_per_cu)
+{
+    const int fixed = (int)sizeof(Smem) + 64;
+    int bytes = LDS_CU_BYTES / (sims_per_cu < 1 ? 1 : sims_per_cu) - fixed;
+    if (bytes > POOL_DEFAULT_DOUBLES * 8) bytes = POOL_DEFAULT_DOUBLES * 8;
+    if (bytes < POOL_MIN_DOUBLES * 8) bytes = POOL_MIN_DOUBLES * 8;
+    return (bytes / 16) * 2;
+}
 
 }  // namespace mpcb

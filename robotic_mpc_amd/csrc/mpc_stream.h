@@ -86,6 +86,8 @@ constexpr int OUT_MAX = 232;   // doubles of the largest output bundle (factor r
 #define MPCB_RING_DOUBLES 1476
 #endif
 constexpr int RING_DOUBLES = MPCB_RING_DOUBLES;
+// y of every stage fits the idle ring: the residual pass of the interior-point iterations runs item-parallel (residual_items below)
+MPC_HD bool residual_items_ok(int N) { return (N + 1) * 6 <= RING_DOUBLES; }
 constexpr int SLOGB = 2;       // log columns collected before they leave (LOGB of the latency engine is 8: here every KB of LDS is
                                // prefetch depth of the input ring, and the sweeps wait on the memory latency that depth hides)
 
@@ -762,7 +764,7 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
 // 64 ITEMS at a time, operands straight from the stage records in HBM / L2 into registers (mpc_core.h residual_direct, the same
 // three phases U | Y | S,D and the same arithmetic per element).  ~17 batches of loads per pass instead of 101 stages of chain;
 // while a batch is in flight the SIMD's other simulation runs.  y of every stage waits in the (idle) ring between Y and S.
-SE_DEV bool residual_items_ok(int N) { return (N + 1) * 6 <= RING_DOUBLES; }
+// (residual_items_ok: beside RING_DOUBLES above)
 SE_PASS IpmNorms residual_items(double a)
 {
     SSmem &sm = g_ssm;

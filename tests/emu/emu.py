@@ -53,3 +53,24 @@ def run(cfgs, chain, step_chunk=0, pool_doubles=0, waves=1):
     rc = lib.emu_run(*args)
     assert rc == 0
     return o
+
+
+SWEEPS = ("resident", "register", "segment", "streaming")
+
+
+def emu_paths(N, pool_doubles, waves):
+    """Which implementation the device takes at horizon N with a chunk pool of `pool_doubles` and `waves` wavefronts per
+    simulation, from the engine's own predicates (emu_harness.cpp emu_paths): the sweep of the interior-point solve, the merit
+    pass's lanes per trial point and trial points per pass, the lane groups and transitions per segment of the resident,
+    segment and register sweeps, and the throughput engine's ring size and residual pass (item-parallel or sequential)."""
+    lib = C.CDLL(build())
+    o = (C.c_int * 9)()
+    rc = lib.emu_paths(C.c_int(N), C.c_int(pool_doubles), C.c_int(waves), o)
+    assert rc == 0, (N, pool_doubles, waves)
+    return dict(sweep=SWEEPS[o[0]], merit_lanes=o[1], merit_groups=o[2], groups=o[3], seg_T=o[4], reg_T=o[5], lanes=o[6],
+                ring_doubles=o[7], residual_items=bool(o[8]))
+
+
+def pool_doubles(sims_per_cu):
+    """The chunk pool mpcb_setup gives one simulation at `sims_per_cu` simulations per CU (mpc_layout.h lay_pool_doubles)."""
+    return int(C.CDLL(build()).emu_pool_doubles(C.c_int(sims_per_cu)))

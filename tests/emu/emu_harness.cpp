@@ -14,6 +14,7 @@
 
 #include "../../robotic_mpc_amd/csrc/mpc_core.h"
 #include "../../robotic_mpc_amd/csrc/mpc_pack.h"
+#include "../../robotic_mpc_amd/csrc/mpc_stream.h"   // (host side only: its ring size and residual_items_ok, for emu_paths)
 
 using namespace mpcb;
 
@@ -146,6 +147,50 @@ extern "C" int emu_run(const Problem *pb, const double *robot105, const double *
     if (waves == 2) return emu_run_t<2>(pb, robot105, params, out, step_chunk, pool_doubles);
     return emu_run_t<1>(pb, robot105, params, out, step_chunk, pool_doubles);
 }
+
+// Which implementation the device takes at horizon N with a chunk pool of `pool_doubles` and `waves` wavefronts per simulation --
+// through the Engine's own predicates (the same three lines as Engine::ipm_solve), for tests/test_boundaries.py:
+//   o[0] sweep of ipm_solve: 0 resident, 1 register, 2 segment, 3 streaming     o[1] merit_lanes()   o[2] merit_groups()
+//   o[3] lane groups of the resident sweeps      o[4] transitions per segment (seg_map)   o[5] transitions per segment (reg_map)
+//   o[6] lanes per simulation
+//   o[7] throughput engine: doubles of the input ring (MPCB_RING_DOUBLES)   o[8] its residual_items_ok(N)
+template <int NWV>
+static void emu_paths_t(int N, int pool_doubles, int *o)
+{
+    Problem pb{1, N, 1, 1, 1, 1, 0, 0};
+    Smem sm;
+    std::memset(&sm, 0, sizeof sm);
+    std::vector<double> pool((size_t)pool_doubles + 64, 0.0);
+    HostExec<NWV> ex{&sm, pool.data()};
+    Ctx c{&pb, Ws{}, pool_doubles, N};
+    Engine<HostExec<NWV>> eng(ex, c);
+    const bool res = eng.resident_ok();
+    const bool reg = eng.reg_ok();
+    const bool seg = !reg && eng.segment_ok();
+    o[0] = res ? 0 : reg ? 1 : seg ? 2 : 3;
+    o[1] = eng.merit_lanes();
+    o[2] = eng.merit_groups();
+    o[3] = Engine<HostExec<NWV>>::RS_GROUPS;
+    o[4] = eng.seg_map().T;
+    o[5] = eng.reg_map().T;
+    o[6] = HostExec<NWV>::NT;
+}
+
+extern "C" int emu_paths(int N, int pool_doubles, int waves, int *o)
+{
+    if (N < 1 || pool_doubles < POOL_MIN_DOUBLES) return 1;
+    if (waves == 8) emu_paths_t<8>(N, pool_doubles, o);
+    else if (waves == 4) emu_paths_t<4>(N, pool_doubles, o);
+    else if (waves == 2) emu_paths_t<2>(N, pool_doubles, o);
+    else if (waves == 1) emu_paths_t<1>(N, pool_doubles, o);
+    else return 1;
+    o[7] = se::RING_DOUBLES;
+    o[8] = se::residual_items_ok(N) ? 1 : 0;
+    return 0;
+}
+
+// the chunk pool mpcb_setup gives one simulation at `sims_per_cu` simulations per CU
+extern "C" int emu_pool_doubles(int sims_per_cu) { return lay_pool_doubles(sims_per_cu); }
 
 // the product's joint-angle sincos (mpc_kin.h), for tests/test_emulation.py::test_joint_sincos_against_libm
 extern "C" void emu_sincos(int n, const double *th, double *sn, double *cs)

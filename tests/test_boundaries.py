@@ -1,0 +1,210 @@
+"""Both sides of every code-path switch of the latency engine, through the host emulation of the device code (tests/emu).
+
+The engine picks its implementation at run time from the horizon N, the LDS chunk pool and the wavefronts per simulation
+(csrc/mpc_core.h ipm_solve: resident / register / segment / streaming sweeps; merit_lanes / merit_groups of the full-SQP
+line search), and none of these choices shows in the outputs.  So:
+
+  * BOUNDARIES pins, for every geometry the device launches (1 / 2 / 4 / 8 wavefronts, 1 / 2 simulations per CU), the first N
+    on the far side of every switch and seam, as the engine's own predicates give them (emu.emu_paths).  A layout change that
+    moves a boundary has to update this table on purpose.
+  * EDGE_POOLS pins the smallest pool at which a horizon still takes a sweep: the scratch conditions of the predicates at
+    equality.
+  * Every switch and seam is run at N - 1, N and N + 1 against the oracle at the emulation's bar, and every case first asserts
+    that it takes the branch the table names for it.
+
+tests/test_gpu_boundaries.py runs the same boundaries on the device.
+"""
+import os
+import shutil
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+
+pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc needed to build the emulation harness")
+
+NMAX = 520          # past the last merit-lane step (N + 1 > 512 at eight wavefronts)
+WAVES = (1, 2, 4, 8)
+SIMS_PER_CU = (1, 2)
+
+# (wavefronts per simulation, simulations per CU) -> chunk pool (doubles) and the first N of every branch up to NMAX:
+#   sweep   [(N, sweep of the interior-point solve from N on)]
+#   merit   [(N, lanes per trial point, trial points per pass from N on)]
+#   lanes_below_stages   first N whose N + 1 stages outnumber the merit lanes of a trial point (a lane sums several stages)
+#   seams   first N of every further segment of the segment / register sweeps (N = j T + 1, T transitions per segment)
+BOUNDARIES = {
+    (1, 1): dict(pool=19392, sweep=[(1, "resident"), (141, "streaming")], merit=[(1, 64, 1)], lanes_below_stages=64, seams=[]),
+    (2, 1): dict(pool=19392, sweep=[(1, "resident"), (136, "segment")], merit=[(1, 128, 1)], lanes_below_stages=128,
+                 seams=[169, 225, 281, 337, 393, 449, 505]),
+    (4, 1): dict(pool=19392, sweep=[(1, "resident"), (126, "segment")], merit=[(1, 128, 2), (128, 256, 1)], lanes_below_stages=256,
+                 seams=[225, 337, 449]),
+    (8, 1): dict(pool=19392, sweep=[(1, "resident"), (126, "segment")], merit=[(1, 128, 2), (128, 256, 2), (256, 512, 1)],
+                 lanes_below_stages=512, seams=[225, 337, 449]),
+    (1, 2): dict(pool=9152, sweep=[(1, "resident"), (43, "streaming")], merit=[(1, 64, 1)], lanes_below_stages=64, seams=[]),
+    (2, 2): dict(pool=9152, sweep=[(1, "resident"), (38, "streaming")], merit=[(1, 128, 1)], lanes_below_stages=128, seams=[]),
+    (4, 2): dict(pool=9152, sweep=[(1, "resident"), (26, "register")], merit=[(1, 128, 2), (128, 256, 1)], lanes_below_stages=256,
+                 seams=[113, 225, 337, 449]),
+    (8, 2): dict(pool=9152, sweep=[(1, "resident"), (26, "register")], merit=[(1, 128, 2), (128, 256, 2), (256, 512, 1)],
+                 lanes_below_stages=512, seams=[113, 225, 337, 449]),
+}
+# (wavefronts, N, sweep) -> the smallest pool (doubles, even) at which horizon N takes that sweep
+EDGE_POOLS = {
+    (4, 25, "resident"): 9052,     # lay_resident_ok: scratch of exactly 4096 doubles (the chunked factorisation's floor)
+    (4, 125, "resident"): 19336,   # lay_resident_ok: scratch of exactly the corrector's (N + 1) 30 + 2 groups 12 + 16
+    (4, 126, "register"): 7690,    # Engine::reg_ok: scratch of exactly (T + 1) 30 + 3 16 12 + 64
+    (4, 126, "segment"): 17668,    # lay_segment_ok: scratch of exactly (T + 1) 30 + 2 groups 12 + 64
+}
+# the throughput engine: the longest horizon whose y fits the input ring (item-parallel residual pass from the second
+# interior-point iteration on; sequential residual pass beyond), and the ring
+STREAM = dict(ring_doubles=1476, residual_items_last=245)
+
+
+def _paths(N, pool, waves):
+    import emu
+
+    return emu.emu_paths(N, pool, waves)
+
+
+def _derive(waves, pool, nmax=NMAX):
+    """The table entry of one geometry, from the engine's predicates alone."""
+    rows = {N: _paths(N, pool, waves) for N in range(1, nmax + 1)}
+    sweep = [(N, r["sweep"]) for N, r in rows.items() if N == 1 or r["sweep"] != rows[N - 1]["sweep"]]
+    mkey = lambda r: (r["merit_lanes"], r["merit_groups"])  # noqa: E731
+    merit = [(N, *mkey(r)) for N, r in rows.items() if N == 1 or mkey(r) != mkey(rows[N - 1])]
+    below = min(N for N, r in rows.items() if r["merit_lanes"] < N + 1)
+    seams = []
+    for N, r in rows.items():
+        T = {"segment": r["seg_T"], "register": r["reg_T"]}.get(r["sweep"])
+        if T and N > 1 and rows[N - 1]["sweep"] == r["sweep"] and (N - 1) % T == 0:
+            seams.append(N)
+    return dict(pool=pool, sweep=sweep, merit=merit, lanes_below_stages=below, seams=seams)
+
+
+def _named(key, N):
+    """The branch the PINNED table names for horizon N of geometry `key`: (sweep, merit lanes, merit groups)."""
+    g = BOUNDARIES[key]
+    sweep = [s for n, s in g["sweep"] if n <= N][-1]
+    lanes, groups = [(l, m) for n, l, m in g["merit"] if n <= N][-1]
+    return sweep, lanes, groups
+
+
+def _switch_points(key):
+    """Every switch and seam of a geometry: (first N on the far side, what switches there)."""
+    g = BOUNDARIES[key]
+    pts = [(N, "sweep") for N, _ in g["sweep"][1:]] + [(N, "merit") for N, _, _ in g["merit"][1:]]
+    pts += [(g["lanes_below_stages"], "merit")] + [(N, "seam") for N in g["seams"]]
+    return pts
+
+
+def _cases():
+    """(geometry, pool, waves, N, solver) at N - 1, N, N + 1 of every switch and seam.  The sweeps run under SQP_RTI with the
+    bound-inactive fast path (one factorisation and forward sweep per QP) and without it (the interior-point loop: every sweep);
+    the merit pass runs under full SQP only, so its steps run there, as do the sweep switches."""
+    out = {}
+    for key in BOUNDARIES:
+        waves, pool = key[0], BOUNDARIES[key]["pool"]
+        for p, kind in _switch_points(key):
+            solvers = {"sweep": ("SQP_RTI", "SQP_RTI_IPM", "SQP"), "seam": ("SQP_RTI", "SQP_RTI_IPM"), "merit": ("SQP",)}[kind]
+            for N in (p - 1, p, p + 1):
+                if 1 <= N <= NMAX:
+                    for s in solvers:
+                        out[(key, N, s)] = (key, pool, waves, N, s)
+    # the pool edges: the horizon at the smallest pool that admits its sweep, and one item below it
+    for (waves, N, sweep), pool in EDGE_POOLS.items():
+        for pl in (pool, pool - 2):
+            for s in ("SQP_RTI", "SQP_RTI_IPM"):
+                out[(("edge", sweep, pl), N, s)] = (("edge", sweep, pl == pool), pl, waves, N, s)
+    return sorted(out.values(), key=lambda c: (str(c[0]), c[3], c[4]))
+
+
+CASES = _cases()
+
+
+def test_pool_of_every_launch_geometry():
+    """The pools the table is derived at are the ones mpcb_setup gives a launch (lay_pool_doubles, shared with it)."""
+    import emu
+
+    assert sorted(BOUNDARIES) == sorted((w, s) for w in WAVES for s in SIMS_PER_CU)
+    for (waves, spc), g in BOUNDARIES.items():
+        assert emu.pool_doubles(spc) == g["pool"], (waves, spc)
+
+
+@pytest.mark.parametrize("key", list(BOUNDARIES), ids=lambda k: "w%d_s%d" % k)
+def test_boundary_table_is_pinned(key):
+    """Every switch and seam of the engine's predicates, first N on the far side, at each launch geometry."""
+    assert _derive(key[0], BOUNDARIES[key]["pool"]) == BOUNDARIES[key]
+
+
+def test_edge_pools_are_pinned():
+    """The scratch conditions of lay_resident_ok, reg_ok and lay_segment_ok at equality: at the pinned pool the horizon takes
+    the sweep, one 16-byte item less it does not."""
+    for (waves, N, sweep), pool in EDGE_POOLS.items():
+        assert _paths(N, pool, waves)["sweep"] == sweep, (waves, N, sweep, pool)
+        assert _paths(N, pool - 2, waves)["sweep"] != sweep, (waves, N, sweep, pool - 2)
+
+
+def test_stream_engine_switch_is_pinned():
+    """Throughput engine (mpc_stream.h residual_items_ok, ring MPCB_RING_DOUBLES): item-parallel residual pass up to N = 245."""
+    last = STREAM["residual_items_last"]
+    for N, want in ((1, True), (last - 1, True), (last, True), (last + 1, False), (last + 2, False), (NMAX, False)):
+        r = _paths(N, 19392, 1)
+        assert r["ring_doubles"] == STREAM["ring_doubles"] and r["residual_items"] == want, (N, r)
+
+
+@pytest.mark.parametrize("key", list(BOUNDARIES), ids=lambda k: "w%d_s%d" % k)
+def test_every_switch_has_cases_on_both_sides(key):
+    """Coverage: every switch and seam the predicates give (derived, not pinned) is run at N - 1, N and N + 1, with the solvers
+    that reach it -- a boundary missing from the table leaves its switch without cases."""
+    d = _derive(key[0], BOUNDARIES[key]["pool"])
+    have = {(c[3], c[4]) for c in CASES if c[0] == key}
+    pts = [(N, ("SQP_RTI", "SQP_RTI_IPM")) for N, _ in d["sweep"][1:]] + [(N, ("SQP_RTI", "SQP_RTI_IPM")) for N in d["seams"]]
+    pts += [(N, ("SQP",)) for N, _, _ in d["merit"][1:]] + [(d["lanes_below_stages"], ("SQP",))]
+    for p, solvers in pts:
+        for N in (p - 1, p, p + 1):
+            for s in solvers:
+                assert N > NMAX or (N, s) in have, (key, p, N, s)
+
+
+_REF = {}
+
+
+def _oracle(orc, rb, cfg, tag):
+    if tag not in _REF:
+        _REF[tag] = orc.run(rb, orc.make_params(cfg))
+    return _REF[tag]
+
+
+def _case_id(c):
+    key, pool, waves, N, solver = c
+    geo = "edge_%s_%s_p%d" % (key[1], "in" if key[2] else "out", pool) if key[0] == "edge" else "w%d_s%d" % key
+    return "%s-w%d-N%d-%s" % (geo, waves, N, solver)
+
+
+@pytest.mark.parametrize("key,pool,waves,N,solver", CASES, ids=[_case_id(c) for c in CASES])
+def test_emulated_boundary_matches_oracle(orc, ur10, ur10_rb, key, pool, waves, N, solver):
+    """The latency engine at one side of a switch or seam, against the oracle at the emulation's bar (test_emulation.py): the case
+    first asserts that it takes the sweep and merit layout the table names for it."""
+    import emu
+
+    from robotic_mpc_amd import config
+
+    p = emu.emu_paths(N, pool, waves)
+    if key[0] == "edge":
+        assert (p["sweep"] == key[1]) == key[2], (N, pool, waves, p)
+    else:
+        assert (p["sweep"], p["merit_lanes"], p["merit_groups"]) == _named(key, N), (key, N, p)
+    ipm_only = solver.endswith("_IPM")
+    T = 0.05 if N < 200 else 0.03
+    cfg = config.resolve_config(config.base_params(prediction_horizon=N, simulation_time=T, qp_fast_path=not ipm_only,
+                                                   solver_options={"nlp_solver_type": solver.replace("_IPM", "")}))
+    ref = _oracle(orc, ur10_rb, cfg, (N, solver))
+    out = emu.run([cfg], ur10, pool_doubles=pool, waves=waves)
+    for k in ("z", "u", "ee_pose", "ee_rpy", "ee_vel"):
+        np.testing.assert_allclose(out[k][0], ref[k], atol=1e-11, rtol=0, err_msg=k)
+    np.testing.assert_allclose(out["cost"][0], ref["cost"], atol=1e-10, rtol=1e-10)
+    for k in ("status", "sqp_iter", "qp_iter"):
+        np.testing.assert_array_equal(out[k][0], ref[k], err_msg=k)
+    if solver == "SQP":
+        assert (ref["sqp_iter"] > 1).any()            # the merit line search ran
