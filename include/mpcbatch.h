@@ -195,6 +195,36 @@ int mpcb_summary(mpcb_handle *h, const mpcb_result *out_dev, double *summary_dev
 int mpcb_run(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host,
              const mpcb_result *out_host);
 
+/* ---- controller step: the MPC solve from caller-supplied states, for a plant the caller owns ----
+ * (acados solver.set(0,'lbx'|'ubx',x); solver.solve(); solver.get(0,'u') -- simulator.py:210-221 -- for a whole batch.)
+ * All pointers are DEVICE pointers, batch-major.  x_pred / u_pred may be NULL (not written); every other array is required. */
+typedef struct {
+    const double *xhat;  /* [batch][12]     feedback state q;qdot of each simulation (in)                      */
+    double *u0;          /* [batch][6]      solver.get(0,'u'): the input to apply                              */
+    int *status;         /* [batch]         acados status 0/1/2/3/4                                            */
+    int *sqp_iter;       /* [batch]                                                                            */
+    int *qp_iter;        /* [batch]         Riccati factorisations, as in mpcb_result                          */
+    double *residuals;   /* [batch][4]      stat, eq, ineq, comp                                               */
+    double *cost;        /* [batch]                                                                            */
+    double *solver_time; /* [batch]         device seconds of the solve                                        */
+    double *x_pred;      /* [batch][N+1][12] predicted states x_0..x_N of the iterate, or NULL                 */
+    double *u_pred;      /* [batch][N][6]   predicted inputs u_0..u_{N-1} of the iterate, or NULL              */
+} mpcb_step_io;
+
+/* Like mpcb_setup (same validation and packing; Nsim is checked but not used), for mpcb_step: always the latency engine,
+ * at any batch size, with mpcb_setup's geometry rules.  Refuses ragged horizons (parameter [65] != 0 and != N) and
+ * MPCB_PRECISION_FP32_RICCATI with MPCB_EINVAL (the throughput engine alone implements those).  On the handle this sets
+ * up, mpcb_rollout and mpcb_summary return MPCB_ESTATE; mpcb_setup or mpcb_run set it up for rollouts again. */
+int mpcb_setup_controller(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host);
+
+/* One MPC step of every simulation from the states io->xhat: the iterate, the linearisation and the QP memory carry
+ * over from the previous step (the warm start of a real-time controller); `reset` != 0 starts from the initial guess
+ * (x_k = [q_0; qdot_0], u_k = 0, multipliers 0), and so does the first step after mpcb_setup_controller.  No plant
+ * step, no logs.  Asynchronous on `stream` (a hipStream_t, NULL = default stream), no host synchronisation;
+ * mpcb_sync and mpcb_last_kernel_ms apply to it.  MPCB_ESTATE on a handle not set up by mpcb_setup_controller.
+ * mpcb_kernel_info and mpcb_launch_info report the step kernel on a controller handle. */
+int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,5 +12,6 @@ __version__ = "0.1.0"
 
 from .config import BASE_PARAMS, base_params, resolve_config  # noqa: E402,F401
 from .simulator import SimulationManager, Simulator  # noqa: E402,F401
+from .controller import BatchController  # noqa: E402,F401
 
-__all__ = ["SimulationManager", "Simulator", "BASE_PARAMS", "base_params", "resolve_config", "__version__"]
+__all__ = ["SimulationManager", "Simulator", "BatchController", "BASE_PARAMS", "base_params", "resolve_config", "__version__"]

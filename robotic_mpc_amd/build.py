@@ -11,6 +11,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmpcbatch.so")
 LIB_PROF = os.path.join(HERE, "libmpcbatch_prof.so")
 ARCH = "gfx950"
+# translation units of the library: the rollout kernels + C ABI, and the controller step kernels (a module of their own)
+SOURCES = ("mpc_kernel.hip", "mpc_step.hip")
 
 
 def _stale(target: str) -> bool:
@@ -28,7 +30,7 @@ def build(force: bool = False, profile: bool = False, verbose: bool = False) -> 
     if not force and not _stale(target):
         return target
     cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-shared", "-std=c++17", "-o", target,
-           os.path.join(CSRC, "mpc_kernel.hip")]
+           *[os.path.join(CSRC, f) for f in SOURCES]]
     if profile:
         cmd.insert(1, "-DMPCB_PROFILE")
     if verbose:
@@ -44,7 +46,7 @@ def build_variant(name: str, defines) -> str:
     target = os.path.join(HERE, f"libmpcbatch_{name}.so")
     if _stale(target):
         subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-shared", "-std=c++17", *[f"-D{d}" for d in defines],
-                               "-o", target, os.path.join(CSRC, "mpc_kernel.hip")])
+                               "-o", target, *[os.path.join(CSRC, f) for f in SOURCES]])
     return target
 
 

@@ -2952,6 +2952,9 @@ struct Engine {
     // state and G2 holds the linearisation at the current iterate when `lin_valid`; on exit it
     // is valid for the (new) iterate again, together with its cost and NLP residuals.
     // `plant_done` (out): the plant step and the log of the new state were done inside the last NLP pass (SQP_RTI)
+    // PLANT = false (control_step: the caller owns the plant): the last NLP pass of SQP_RTI runs no plant lane and forms no fast-path
+    // right-hand side -- there is no next state to form it for; the next step's QP forms it itself (ipm_solve, !rhs_valid).
+    template <bool PLANT = true>
     MPC_HD int nlp_step(bool &lin_valid, int *sqp_iter_out, int *qp_iter_out, double *res4, double *cost_out, bool *plant_done)
     {
         *plant_done = false;
@@ -2970,11 +2973,16 @@ struct Engine {
             // residuals / cost are evaluated at the new iterate (acados get_residuals() for RTI,
             // get_cost()); this linearisation is reused by the next solve() call -- and so is the fast path's right-hand side,
             // formed by the same pass when the next QP will try the fast path (ipm_solve: fast_off == 0 and no suspension left)
-            const bool next_fast = ex.uni(MPCB_FUSE != 0 && ex.smem().P.fast_off == 0.0 && fast_skip == 0);
-            cost = NLP_PASS(1.0, ok, false, res4, true, commit_pending, next_fast);
-            rhs_valid = next_fast;
+            if constexpr (PLANT) {
+                const bool next_fast = ex.uni(MPCB_FUSE != 0 && ex.smem().P.fast_off == 0.0 && fast_skip == 0);
+                cost = NLP_PASS(1.0, ok, false, res4, true, commit_pending, next_fast);
+                rhs_valid = next_fast;
+                *plant_done = true;
+            } else {
+                cost = NLP_PASS(1.0, ok, false, res4, false, commit_pending, false);
+                rhs_valid = false;
+            }
             commit_pending = false;
-            *plant_done = true;
             lin_valid = true;
         } else {
             const double tol = ex.smem().P.tol, tol_eq = ex.smem().P.tol_eq, tol_in = ex.smem().P.tol_ineq, tol_co = ex.smem().P.tol_comp;
@@ -3017,28 +3025,13 @@ struct Engine {
         bool lin_valid = false;
         int log_lo = step0 == 0 ? 0 : step0 + 1;   // first log column this launch produces
         if (step0 == 0) {
-            // acados initial guess: x_k = x0, u_k = 0, all multipliers / QP memory 0 (SURVEY A.7 iv)
-            const size_t tot = ws_doubles_per_instance(N);
-            ex.par([&](int lane) {
-                for (size_t e = lane; e < tot; e += NT) w.G1[e] = 0.0;  // G1 is the workspace base
-            });
-            ex.par([&](int lane) {
-                for (int e = lane; e < (N + 1) * NX; e += NT) {
-                    const int k = e / NX, i = e - k * NX;
-                    w.G1[(size_t)k * W1 + O_X + i] = i < 6 ? P.q0[i] : P.qdot0[i - 6];
-                }
-                if (lane < NX) sm.xhat[lane] = lane < 6 ? P.q0[lane] : P.qdot0[lane - 6];
-                if (lane < NU) sm.u0[lane] = P.qdot0[lane];  // u[:,0] = qdot_0 (simulator.py:81)
-            });
+            initial_guess();
             log_lo = ex.uni(log_state(out, inst, 0, log_lo, false));
         } else {
             ex.par([&](int lane) {
                 if (lane < NX) sm.xhat[lane] = w.state[lane];
             });
-            lin_cost = w.state[12];
-            lin_valid = ex.uni(w.state[25] != 0.0);
-            rhs_valid = false;     // (not carried across launches: the first fast attempt of a launch forms its right-hand side itself)
-            fast_skip = ex.uni((int)w.state[26]); fast_back = ex.uni((int)w.state[27]);
+            load_carry(lin_valid);
         }
         for (int i = step0; i < step1; i++) {
             int sqp_iter = 0, qp_iter = 0;
@@ -3082,6 +3075,43 @@ struct Engine {
             PROF_ADD(PF_PLANT, tp);
         }
         if (log_lo <= step1) log_flush(out, inst, log_lo, step1);   // the columns of a partly filled block
+        store_carry(lin_valid);
+    }
+
+    // acados initial guess: x_k = x0, u_k = 0, all multipliers / QP memory 0 (SURVEY A.7 iv); sm.xhat = x0, sm.u0 = qdot_0
+    MPC_HD void initial_guess()
+    {
+        Smem &sm = ex.smem();
+        const InstParams &P = sm.P;
+        Ws &w = c.w;
+        const size_t tot = ws_doubles_per_instance(N);
+        ex.par([&](int lane) {
+            for (size_t e = lane; e < tot; e += NT) w.G1[e] = 0.0;  // G1 is the workspace base
+        });
+        ex.par([&](int lane) {
+            for (int e = lane; e < (N + 1) * NX; e += NT) {
+                const int k = e / NX, i = e - k * NX;
+                w.G1[(size_t)k * W1 + O_X + i] = i < 6 ? P.q0[i] : P.qdot0[i - 6];
+            }
+            if (lane < NX) sm.xhat[lane] = lane < 6 ? P.q0[lane] : P.qdot0[lane - 6];
+            if (lane < NU) sm.u0[lane] = P.qdot0[lane];  // u[:,0] = qdot_0 (simulator.py:81)
+        });
+    }
+
+    // Solver memory carried from one launch to the next in w.state (besides the workspace records): [0..11] the last feedback state,
+    // [12] lin_cost, [25] lin_valid, [26] fast_skip, [27] fast_back (the x_0 merit weights [13..24] are read and written in place)
+    MPC_HD void load_carry(bool &lin_valid)
+    {
+        Ws &w = c.w;
+        lin_cost = w.state[12];
+        lin_valid = ex.uni(w.state[25] != 0.0);
+        rhs_valid = false;     // (not carried across launches: the first fast attempt of a launch forms its right-hand side itself)
+        fast_skip = ex.uni((int)w.state[26]); fast_back = ex.uni((int)w.state[27]);
+    }
+    MPC_HD void store_carry(bool lin_valid)
+    {
+        Smem &sm = ex.smem();
+        Ws &w = c.w;
         ex.par([&](int lane) {
             if (lane < NX) w.state[lane] = sm.xhat[lane];
             if (lane == 12) { w.state[12] = lin_cost; w.state[25] = lin_valid ? 1.0 : 0.0; w.state[26] = fast_skip; w.state[27] = fast_back; }
@@ -3094,6 +3124,55 @@ struct Engine {
             }
 #endif
         });
+    }
+
+    // ==================================================================== controller step
+    // One solver.solve() from the caller's feedback state (mpcb_step; acados set(0,'lbx'|'ubx',x), solve(), get(0,'u'),
+    // simulator.py:210-221) for instance `inst`: the iterate, the linearisation and the fast-path suspension carry over from the
+    // previous step in the workspace as between two rollout launches; `reset` starts from the initial guess instead.  No plant step,
+    // no log columns: io.u0 is the plant's input, the caller's plant produces the next io.xhat.
+    MPC_HD void control_step(const StepIO &io, int inst, bool reset)
+    {
+        Smem &sm = ex.smem();
+        Ws &w = c.w;
+        bool lin_valid = false;
+        if (reset) initial_guess();
+        else load_carry(lin_valid);
+        ex.par([&](int lane) {
+            if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
+        });
+        int sqp_iter = 0, qp_iter = 0;
+        double res4[4] = {0, 0, 0, 0}, cost = 0.0;
+        const double t0 = ex.clock();
+        bool plant_done = false;
+        const int status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done);
+        const double t1 = ex.clock();
+        ex.par([&](int lane) {
+            if (lane < NU) io.u0[(size_t)inst * NU + lane] = w.G1[O_U + lane];   // solver.get(0,'u')
+            if (lane == 8) {
+                io.status[inst] = status;
+                io.sqp_iter[inst] = sqp_iter;
+                io.qp_iter[inst] = qp_iter;
+                io.cost[inst] = cost;
+                io.solver_time[inst] = t1 - t0;
+            }
+            if (lane >= 12 && lane < 16) io.residuals[(size_t)inst * 4 + (lane - 12)] =
+                lane == 12 ? res4[0] : (lane == 13 ? res4[1] : (lane == 14 ? res4[2] : res4[3]));
+            // the predicted trajectory: the iterate's x_0..x_N and u_0..u_{N-1} (orc_solver_get_iterate)
+            if (io.x_pred) {
+                for (int e = lane; e < (N + 1) * NX; e += NT) {
+                    const int k = e / NX, i = e - k * NX;
+                    io.x_pred[(size_t)inst * (N + 1) * NX + e] = w.G1[(size_t)k * W1 + O_X + i];
+                }
+            }
+            if (io.u_pred) {
+                for (int e = lane; e < N * NU; e += NT) {
+                    const int k = e / NU, j = e - k * NU;
+                    io.u_pred[(size_t)inst * N * NU + e] = w.G1[(size_t)k * W1 + O_U + j];
+                }
+            }
+        });
+        store_carry(lin_valid);
     }
 
     // simulation_model.py:87-90: log state, input, FK pose, rpy, J*qdot at column `col`, plus the task errors of

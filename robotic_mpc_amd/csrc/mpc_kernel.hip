@@ -1,7 +1,7 @@
 // mpc_kernel.hip -- gfx950 kernel + C ABI (include/mpcbatch.h) of the batched MPC engine.
 //
 // Launch geometry: one workgroup of NWV wavefronts (1, 2, 4 or 8; mpcb_setup picks it from the
-// batch) per simulation instance, grid = batch.  DevExec<NWV> below is the device executor of the
+// batch) per simulation instance, grid = batch.  DevExec<NWV> (mpc_devexec.h) is the device executor of the
 // engine template (mpc_core.h): workgroup barriers between bulk-synchronous phases, wave-local
 // fences inside a recursion, role-split windows (overlap3), DPP/readlane cross-lane helpers.
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 
 #include "../../include/mpcbatch.h"
 #include "mpc_core.h"
+#include "mpc_devexec.h"
 #include "mpc_pack.h"
 #include "mpc_stream.h"
 
@@ -24,243 +25,16 @@ using namespace mpcb;
 
 static_assert(sizeof(mpcb_problem) == sizeof(Problem), "ABI struct mismatch");
 static_assert(sizeof(mpcb_result) == sizeof(Outputs), "ABI struct mismatch");
+static_assert(sizeof(mpcb_step_io) == sizeof(StepIO), "ABI struct mismatch");
 static_assert(sizeof(Robot) == MPCB_NROBOT * sizeof(double), "robot layout");
 
-// LDS of the workgroup (= one simulation): fixed working set + chunk pool.
-__shared__ __attribute__((aligned(16))) Smem g_sm;
-extern __shared__ __attribute__((aligned(16))) double g_pool[];
-
-// Stateless on purpose: inside a non-inlined pass the executor is reached through `this`, and a
-// data member (e.g. a cached lane id) would be re-loaded from the stack at every phase.
-// NWV wavefronts (one workgroup) cooperate on one simulation.
-#ifndef MPCB_POLL_SLEEP
-#define MPCB_POLL_SLEEP 2
-#endif
-
-// WPE (wavefronts per SIMD the kernel is compiled for) only makes the executor -- and with it every pass of the
-// engine template -- a distinct type per kernel variant, so each variant gets its own register allocation.
-template <int NWV, int WPE = 1>
-struct DevExec {
-    static constexpr int NT = WAVE * NWV;
-    static constexpr int VGPR_BUDGET = (WPE >= 2 || NWV > 4) ? 256 : 512;   // registers per lane this variant is compiled for (two wavefronts per SIMD: 256)
-    __device__ __forceinline__ static int lane_id() { return (int)threadIdx.x; }
-    __device__ __forceinline__ Smem &smem() const { return g_sm; }
-    __device__ __forceinline__ double *pool() const { return g_pool; }
-    // value known to be identical in every lane -> scalar register (and scalar control flow)
-    __device__ __forceinline__ static int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-    __device__ __forceinline__ static bool uni(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-    __device__ __forceinline__ static double uni(double v)
-    {
-        return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-    }
-    template <class T>
-    __device__ __forceinline__ static T *uni(T *p)
-    {
-        const unsigned long long v = (unsigned long long)p;
-        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-        return (T *)(((unsigned long long)hi << 32) | lo);
-    }
-    // per-lane registers that live across phases
-    template <class T>
-    struct PerLane {
-        T v;
-        __device__ __forceinline__ T &at(int) { return v; }
-    };
-    __device__ __forceinline__ static void wave_fence()
-    {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    // phase on all NT lanes, then a workgroup barrier (a wave-local fence when one wave owns the sim)
-    template <class F>
-    __device__ __forceinline__ void par(F &&f)
-    {
-        f(lane_id());
-        if (NWV == 1) wave_fence();
-        else __syncthreads();
-    }
-    // wave-local phase on EVERY wavefront, no workgroup barrier: consecutive wpar phases of one wavefront see each
-    // other's LDS writes (in-order LDS); data of another wavefront needs a barrier() first
-    template <class F>
-    __device__ __forceinline__ void wpar(F &&f)
-    {
-        f(lane_id());
-        wave_fence();
-    }
-    __device__ __forceinline__ static void barrier()
-    {
-        if (NWV == 1) wave_fence();
-        else __syncthreads();
-    }
-    // phase on wavefront 0 only; consecutive seq phases need no s_barrier (one wave, in-order LDS)
-    template <class F>
-    __device__ __forceinline__ void seq(F &&f)
-    {
-        if (NWV == 1 || threadIdx.x < WAVE) {
-            f(lane_id());
-            wave_fence();
-        }
-    }
-    // A stage-by-stage recursion (`fg`, made of seq phases, wavefront 0) with the other wavefronts
-    // doing barrier-free background work `bg(lane, lanes)` (chunk copies for the neighbouring
-    // chunks) in its shadow; ends with the workgroup barrier.  With one wavefront per simulation
-    // the two simply run one after the other.
-    template <class FG, class BG>
-    __device__ __forceinline__ void overlap(FG &&fg, BG &&bg)
-    {
-        if (NWV == 1) {
-            fg();
-            wave_fence();
-            bg(lane_id(), std::integral_constant<int, WAVE>{});
-            wave_fence();
-        } else {
-            if (threadIdx.x < WAVE) fg();
-            else bg(lane_id() - WAVE, std::integral_constant<int, WAVE *(NWV > 1 ? NWV - 1 : 1)>{});
-            __syncthreads();
-        }
-    }
-    // Three concurrent roles: wavefront 0 runs `fg` (seq phases), wavefront 1 runs `mid` (sub
-    // phases, wave-local), the remaining wavefronts run the barrier-free `bg(lane, lanes)`.
-    // With fewer wavefronts the roles run one after the other on the last wavefront.
-    template <class FG, class MID, class BG>
-    __device__ __forceinline__ void overlap3(FG &&fg, MID &&mid, BG &&bg)
-    {
-        if (NWV == 1) {
-            fg(); wave_fence();
-            mid(); wave_fence();
-            bg(lane_id(), std::integral_constant<int, WAVE>{});
-            wave_fence();
-        } else if (NWV == 2) {
-            if (threadIdx.x < WAVE) fg();
-            else { mid(); wave_fence(); bg(lane_id() - WAVE, std::integral_constant<int, WAVE>{}); }
-            __syncthreads();
-        } else {
-            if (threadIdx.x < WAVE) fg();
-            else if (threadIdx.x < 2 * WAVE) mid();
-            else bg(lane_id() - 2 * WAVE, std::integral_constant<int, WAVE *(NWV > 2 ? NWV - 2 : 1)>{});
-            __syncthreads();
-        }
-    }
-    // A loop of `nwin` windows of three roles WITHOUT workgroup barriers between the windows (four wavefronts and more):
-    // every role runs its own loop and the roles meet through LDS counters (post / post_add / await) only; one barrier at
-    // the end.  With fewer wavefronts (roles share a wavefront) each window is an overlap3 with its barrier.
-    static constexpr int BG_WAVES = NWV > 2 ? NWV - 2 : 1;
-    template <class FG, class MID, class BG>
-    __device__ __forceinline__ void pipeline3(int nwin, FG &&fg, MID &&mid, BG &&bg)
-    {
-        if (NWV >= 4) {
-            if (threadIdx.x < WAVE) { for (int ci = 0; ci < nwin; ci++) fg(ci); }
-            else if (threadIdx.x < 2 * WAVE) { for (int ci = 0; ci < nwin; ci++) mid(ci); }
-            else { for (int ci = 0; ci < nwin; ci++) { bg(ci, lane_id() - 2 * WAVE, std::integral_constant<int, WAVE * BG_WAVES>{}); wave_fence(); } }
-            __syncthreads();
-        } else {
-            for (int ci = 0; ci < nwin; ci++)
-                overlap3([&]() { fg(ci); }, [&]() { mid(ci); }, [&](int lane, auto nl) { bg(ci, lane, nl); });
-        }
-    }
-    __device__ __forceinline__ static void post_add(int *flag, int v)
-    {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __hip_atomic_fetch_add(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    // progress counter between the recursion wavefront and the one following it (LDS, same CU):
-    // a wavefront's LDS operations complete in issue order, so data written before post() is
-    // visible to whoever has seen the posted value.
-    __device__ __forceinline__ static void post(int *flag, int v)
-    {
-        // compiler-only ordering: the LDS unit executes one wavefront's DS instructions in issue order,
-        // so no s_waitcnt is needed between the data writes and the flag write
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __hip_atomic_store(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    __device__ __forceinline__ static void await(int *flag, int v)
-    {
-        if (NWV > 1) {   // with a single wavefront the recursion has finished before the follower starts
-            while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < v) __builtin_amdgcn_s_sleep(MPCB_POLL_SLEEP);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    // one step of a recursion that runs on a single wavefront inside overlap3's `mid`
-    template <class F>
-    __device__ __forceinline__ void sub(F &&f)
-    {
-        f(lane_id() & (WAVE - 1));
-        wave_fence();
-    }
-    // ---- values handed from lane to lane between consecutive seq phases (registers, no LDS) ----
-    // share(): publish this lane's value for the next phase (a register stays a register here);
-    // gather(j): the value lane j published; shl6 / shr6: the value of lane + 6 / lane - 6
-    // (DPP row shifts, rows of 16 lanes; used by lanes < 12 only).
-    __device__ __forceinline__ static void share(double *, int, double) {}
-    __device__ __forceinline__ static double gather(const double *, int j, double mine) { return row_lane(mine, j); }
-    // entry `idx` of a small LDS array whose 16-byte item l lane l of this wavefront has just read (`mine` = the half
-    // holding the entry, `src` = idx / 2): a scalar here; the host executor reads the array
-    __device__ __forceinline__ static double lane_value(const double *, int, double mine, int src) { return row_lane(mine, src); }
-    __device__ __forceinline__ static double shl6(const double *, int, double mine) { return dpp<0x106>(mine); }
-    __device__ __forceinline__ static double shr6(const double *, int, double mine) { return dpp<0x116>(mine); }
-    // ---- reductions over the NT lanes of a simulation ------------------------------------
-    // put_*: called by every lane at the end of a par phase; the wavefront reduces its 64 values
-    // with DPP row operations (no LDS round trips) and leaves one partial per wavefront in r[].
-    // get_*: after the phase barrier, combines the NWV partials (same order in every lane).
-    template <int CTRL>
-    __device__ __forceinline__ static double dpp(double v)
-    {
-        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-        return __hiloint2double(hi, lo);
-    }
-    __device__ __forceinline__ static double row_lane(double v, int l)
-    {
-        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-    }
-    template <class Op>
-    __device__ __forceinline__ static double wave_reduce(double v, Op op)
-    {
-        v = op(v, dpp<0xB1>(v));    // quad_perm [1,0,3,2]
-        v = op(v, dpp<0x4E>(v));    // quad_perm [2,3,0,1]
-        v = op(v, dpp<0x141>(v));   // row_half_mirror
-        v = op(v, dpp<0x140>(v));   // row_mirror: every lane of a row of 16 holds the row result
-        return op(op(row_lane(v, 0), row_lane(v, 16)), op(row_lane(v, 32), row_lane(v, 48)));
-    }
-    struct OpSum { __device__ __forceinline__ double operator()(double a, double b) const { return a + b; } };
-    struct OpMax { __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); } };
-    struct OpMin { __device__ __forceinline__ double operator()(double a, double b) const { return fmin(a, b); } };
-    template <class Op>
-    __device__ __forceinline__ static void put(double *r, int lane, double v, Op op)
-    {
-        const double t = wave_reduce(v, op);
-        if ((lane & (WAVE - 1)) == 0) r[lane >> 6] = t;
-    }
-    __device__ __forceinline__ static void put_sum(double *r, int lane, double v) { put(r, lane, v, OpSum()); }
-    __device__ __forceinline__ static void put_max(double *r, int lane, double v) { put(r, lane, v, OpMax()); }
-    __device__ __forceinline__ static void put_min(double *r, int lane, double v) { put(r, lane, v, OpMin()); }
-    template <class Op>
-    __device__ __forceinline__ static double get(const double *r, Op op)
-    {
-        double tot = r[0];
-#pragma unroll
-        for (int w = 1; w < NWV; w++) tot = op(tot, r[w]);
-        return uni(tot);
-    }
-    // single-wavefront variants (inside overlap3's `mid`): one result in r[0]
-    __device__ __forceinline__ static void put1_sum(double *r, int lane, double v) { const double t = wave_reduce(v, OpSum()); if (lane == 0) r[0] = t; }
-    __device__ __forceinline__ static void put1_min(double *r, int lane, double v) { const double t = wave_reduce(v, OpMin()); if (lane == 0) r[0] = t; }
-    __device__ __forceinline__ static double get1(const double *r) { return uni(r[0]); }
-    __device__ __forceinline__ static double get_sum(const double *r) { return get(r, OpSum()); }
-    // per-wavefront partial sums (put_sum leaves exactly those) and the sum over wavefronts [w0, w0 + n)
-    __device__ __forceinline__ static void put_wsum(double *r, int lane, double v) { put(r, lane, v, OpSum()); }
-    __device__ __forceinline__ static double get_sum_range(const double *r, int w0, int n)
-    {
-        double tot = r[w0];
-        for (int w = 1; w < n; w++) tot += r[w0 + w];
-        return uni(tot);
-    }
-    __device__ __forceinline__ static double get_max(const double *r) { return get(r, OpMax()); }
-    __device__ __forceinline__ static double get_min(const double *r) { return get(r, OpMin()); }
-    // constant 100 MHz counter (s_memrealtime)
-    __device__ __forceinline__ double clock() { return (double)wall_clock64() * 1e-8; }
-};
+// The controller step kernels live in their own translation unit, mpc_step.hip: instantiated here, next to the rollout kernels,
+// they change the rollout kernels' code (the LDS lowering numbers the kernels of a module and passes the id to every pass).
+namespace mpcb {
+const void *step_kernel(int waves_per_sim, int wpe);
+void launch_step(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                 const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
+}  // namespace mpcb
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
 // the 1 / 2 / 8-wavefront geometries).  WPE = 2: 256 registers, two 4-wavefront simulations resident per CU -- the
@@ -441,6 +215,8 @@ struct mpcb_handle {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t last_stream = nullptr;
     bool timed = false;
+    bool controller = false;   // set up by mpcb_setup_controller: mpcb_step only (no rollouts)
+    bool reset_next = false;   // the next mpcb_step starts from the initial guess whatever its flag says
 };
 
 static int fail(mpcb_handle *h, int code, const char *what, hipError_t e = hipSuccess)
@@ -560,11 +336,15 @@ size_t mpcb_result_bytes_per_sim(const mpcb_problem *p)
     return (12 + 6 + 12 + 3 + 6 + 7) * T1 * sizeof(double) + 3 * S * sizeof(int) + (4 + 1 + 1 + 1) * S * sizeof(double);
 }
 
-int mpcb_setup(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host)
+// mpcb_setup and mpcb_setup_controller: validate, pack and upload the records, size the workspace, pick the geometry.
+// `controller`: the latency engine at any batch size, uniform horizons and fp64 only.
+static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host, bool controller)
 {
     if (!h) return MPCB_EINVAL;
     int rc = check_problem(h, p);
     if (rc) return rc;
+    if (controller && p->precision != MPCB_PRECISION_FP64)
+        return fail(h, MPCB_EINVAL, "the controller step runs on the latency engine, which has no fp32 Riccati leg");
     if (!params_host || !robot_host) return fail(h, MPCB_EINVAL, "params/robot pointer is NULL");
     HIPCHK(h, hipSetDevice(h->device));
     std::vector<InstParams> packed((size_t)p->batch);
@@ -583,6 +363,8 @@ int mpcb_setup(mpcb_handle *h, const mpcb_problem *p, const double *params_host,
             if (std::isnan(pp[j])) return fail(h, MPCB_EINVAL, "NaN in parameter record");
         pack_inst_params(pp, &packed[(size_t)i]);
     }
+    if (controller && ragged)
+        return fail(h, MPCB_EINVAL, "the controller step needs one horizon for the whole batch (parameter [65] must be 0 or N)");
     std::memcpy(&h->rb, robot_host, sizeof(Robot));
     std::memcpy(&h->pb, p, sizeof(Problem));
     const size_t pbytes = packed.size() * sizeof(InstParams);
@@ -595,8 +377,8 @@ int mpcb_setup(mpcb_handle *h, const mpcb_problem *p, const double *params_host,
     HIPCHK(h, hipMemcpy(h->d_params, packed.data(), pbytes, hipMemcpyHostToDevice));
     h->d_rb = reinterpret_cast<Robot *>(reinterpret_cast<char *>(h->d_params) + pbytes);
     HIPCHK(h, hipMemcpy(h->d_rb, &h->rb, sizeof(Robot), hipMemcpyHostToDevice));
-    h->engine = pick_engine(p, ragged);
-    h->ws_stride = ws_doubles_for(p, ragged);
+    h->engine = controller ? 0 : pick_engine(p, ragged);
+    h->ws_stride = controller ? ws_doubles_per_instance(p->N) : ws_doubles_for(p, ragged);
     const size_t wbytes = (size_t)p->batch * h->ws_stride * sizeof(double);
     if (wbytes > h->ws_cap) {
         if (h->d_ws) (void)hipFree(h->d_ws);
@@ -649,6 +431,36 @@ int mpcb_setup(mpcb_handle *h, const mpcb_problem *p, const double *params_host,
     h->ready = true;
     h->next_step = 0;
     h->timed = false;
+    h->controller = controller;
+    h->reset_next = true;
+    return MPCB_OK;
+}
+
+int mpcb_setup(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host)
+{
+    return setup_impl(h, p, params_host, robot_host, false);
+}
+
+int mpcb_setup_controller(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host)
+{
+    return setup_impl(h, p, params_host, robot_host, true);
+}
+
+// the latency engine's kernel for the handle's geometry: the step kernel on a controller handle, the rollout kernel otherwise
+static const void *latency_kernel(const mpcb_handle *h)
+{
+    if (h->controller) return step_kernel(h->waves_per_sim, h->wpe);
+    return h->waves_per_sim == 8 ? (const void *)mpc_rollout_kernel<8>
+         : h->waves_per_sim == 4 ? (h->wpe == 2 ? (const void *)mpc_rollout_kernel<4, 2> : (const void *)mpc_rollout_kernel<4>)
+         : h->waves_per_sim == 2 ? (const void *)mpc_rollout_kernel<2> : (const void *)mpc_rollout_kernel<1>;
+}
+
+// the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
+// handle can ask for, right before the launch
+static int raise_lds_limit(mpcb_handle *h)
+{
+    static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
+    HIPCHK(h, hipFuncSetAttribute(latency_kernel(h), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     return MPCB_OK;
 }
 
@@ -668,6 +480,7 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
+    if (h->controller) return fail(h, MPCB_ESTATE, "mpcb_rollout on a controller handle (mpcb_setup_controller): use mpcb_step");
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -721,15 +534,7 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
         return MPCB_OK;
     }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    {
-        // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to
-        // the largest pool any handle can ask for, right before the launch
-        static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-        const void *fn = h->waves_per_sim == 8 ? (const void *)mpc_rollout_kernel<8>
-                       : h->waves_per_sim == 4 ? (h->wpe == 2 ? (const void *)mpc_rollout_kernel<4, 2> : (const void *)mpc_rollout_kernel<4>)
-                       : h->waves_per_sim == 2 ? (const void *)mpc_rollout_kernel<2> : (const void *)mpc_rollout_kernel<1>;
-        HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    }
+    if (int rc = raise_lds_limit(h)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
     const dim3 grid((unsigned)h->pb.batch);
     if (h->waves_per_sim == 8)
@@ -752,6 +557,33 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
     h->last_stream = s;
     h->timed = true;
     h->next_step = step1;
+    return MPCB_OK;
+}
+
+int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream)
+{
+    if (!h) return MPCB_EINVAL;
+    if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
+    if (!h->controller) return fail(h, MPCB_ESTATE, "mpcb_step needs a handle set up by mpcb_setup_controller");
+    if (!io) return fail(h, MPCB_EINVAL, "step io pointer is NULL");
+    if (!io->xhat || !io->u0 || !io->status || !io->sqp_iter || !io->qp_iter || !io->residuals || !io->cost || !io->solver_time)
+        return fail(h, MPCB_EINVAL, "every step array but x_pred / u_pred must be provided");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    StepIO sio;
+    std::memcpy(&sio, io, sizeof sio);
+    const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
+    const size_t lds = (size_t)h->pool_doubles * sizeof(double);
+    if (int rc = raise_lds_limit(h)) return rc;
+    HIPCHK(h, hipEventRecord(h->ev0, s));
+    launch_step(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio, rs,
+                h->pool_doubles);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev1, s));
+    h->last_stream = s;
+    h->timed = true;
+    h->queue_used = false;
+    h->reset_next = false;
     return MPCB_OK;
 }
 
@@ -785,10 +617,7 @@ int mpcb_kernel_info(mpcb_handle *h, int *vgprs, int *sgprs, int *lds_bytes, int
         HIPCHK(h, hipFuncGetAttributes(&a, h->pb.precision == MPCB_PRECISION_FP32_RICCATI ? (const void *)mpc_stream_kernel<float>
                                                                                           : (const void *)mpc_stream_kernel<double>));
     } else
-    HIPCHK(h, hipFuncGetAttributes(&a, h->waves_per_sim == 8 ? (const void *)mpc_rollout_kernel<8>
-                                       : h->waves_per_sim == 4 ? (h->wpe == 2 ? (const void *)mpc_rollout_kernel<4, 2> : (const void *)mpc_rollout_kernel<4>)
-                                       : h->waves_per_sim == 2 ? (const void *)mpc_rollout_kernel<2>
-                                                               : (const void *)mpc_rollout_kernel<1>));
+    HIPCHK(h, hipFuncGetAttributes(&a, latency_kernel(h)));
     if (vgprs) *vgprs = a.numRegs;
     if (sgprs) *sgprs = 0;
     if (lds_bytes) *lds_bytes = (int)a.sharedSizeBytes;
@@ -841,6 +670,7 @@ int mpcb_summary(mpcb_handle *h, const mpcb_result *o, double *summary_dev, void
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_summary before mpcb_setup");
+    if (h->controller) return fail(h, MPCB_ESTATE, "mpcb_summary on a controller handle: it keeps no rollout logs");
     if (!o || !summary_dev || !o->errors || !o->status || !o->sqp_iter || !o->qp_iter || !o->residuals || !o->solver_time ||
         !o->plant_time)
         return fail(h, MPCB_EINVAL, "mpcb_summary needs the errors, status, iteration, residual and time arrays");

@@ -136,6 +136,21 @@ struct Outputs {
     double *plant_time; // [batch][Nsim] seconds: plant step + FK / J qdot / error logging (simulator.py:224-226)
 };
 
+// Device pointers of one controller step (== mpcb_step_io): the caller's feedback states in, solver.get(0,'u') and the
+// step's statistics out, batch-major.  x_pred / u_pred may be null (not written).
+struct StepIO {
+    const double *xhat;  // [batch][12]
+    double *u0;          // [batch][6]
+    int *status;         // [batch]
+    int *sqp_iter;       // [batch]
+    int *qp_iter;        // [batch]
+    double *residuals;   // [batch][4]
+    double *cost;        // [batch]
+    double *solver_time; // [batch] seconds (device realtime counter)
+    double *x_pred;      // [batch][N+1][12] or null
+    double *u_pred;      // [batch][N][6] or null
+};
+
 // One instance's workspace: five stage-major group arrays + persistent scalars.
 struct Ws {
     double *G1, *G2, *G3, *G4, *G5, *PH, *state;

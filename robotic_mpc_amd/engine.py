@@ -52,6 +52,20 @@ class MpcbResult(C.Structure):
                 ("errors", _dp), ("plant_time", _dp)]
 
 
+class MpcbStepIO(C.Structure):
+    """mpcb_step_io: DEVICE pointers, batch-major; x_pred / u_pred may be NULL."""
+    _fields_ = [("xhat", _dp), ("u0", _dp), ("status", _ip), ("sqp_iter", _ip), ("qp_iter", _ip), ("residuals", _dp),
+                ("cost", _dp), ("solver_time", _dp), ("x_pred", _dp), ("u_pred", _dp)]
+
+
+# name, ctype, per-simulation shape as a function of N (mpcb_step_io; x_pred / u_pred are optional)
+STEP_FIELDS = (
+    ("xhat", "f8", lambda N: (12,)), ("u0", "f8", lambda N: (6,)), ("status", "i4", lambda N: ()), ("sqp_iter", "i4", lambda N: ()),
+    ("qp_iter", "i4", lambda N: ()), ("residuals", "f8", lambda N: (4,)), ("cost", "f8", lambda N: ()),
+    ("solver_time", "f8", lambda N: ()), ("x_pred", "f8", lambda N: (N + 1, 12)), ("u_pred", "f8", lambda N: (N, 6)),
+)
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -59,7 +73,7 @@ class EngineError(RuntimeError):
 _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", "mpcb_last_error",
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
-            "mpcb_run")
+            "mpcb_run", "mpcb_setup_controller", "mpcb_step")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -100,6 +114,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_summary.argtypes = [C.c_void_p, C.POINTER(MpcbResult), _dp, C.c_void_p]
     lib.mpcb_launch_info.argtypes = [C.c_void_p, _ip, _ip]
     lib.mpcb_engine.argtypes = [C.c_void_p]
+    lib.mpcb_setup_controller.argtypes = [C.c_void_p, C.POINTER(MpcbProblem), _dp, _dp]
+    lib.mpcb_step.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), C.c_int, C.c_void_p]
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     return lib
@@ -235,6 +251,34 @@ class MpcBatchEngine:
         self._check(self.lib.mpcb_summary(self._h, C.byref(r), C.cast(C.c_void_p(out.data_ptr()), _dp), C.c_void_p(stream)),
                     "mpcb_summary")
         return out
+
+    # ------------------------------------------------------------------ controller step
+    def setup_controller(self, cfgs: Sequence[Dict], chain) -> MpcbProblem:
+        """mpcb_setup_controller: like setup(), for step() -- the latency engine at any batch size, one horizon, fp64."""
+        pb, params, robot = self.prepare(cfgs, chain)
+        self._check(self.lib.mpcb_setup_controller(self._h, C.byref(pb), params.ctypes.data_as(_dp), robot.ctypes.data_as(_dp)),
+                    "mpcb_setup_controller")
+        self._pb = pb
+        return pb
+
+    @staticmethod
+    def _step_struct(io) -> MpcbStepIO:
+        r = MpcbStepIO()
+        for name, ty, _ in STEP_FIELDS:
+            t = io.get(name)
+            if t is not None:
+                setattr(r, name, C.cast(C.c_void_p(t.data_ptr()), _dp if ty == "f8" else _ip))
+        return r
+
+    def step(self, io, reset: bool = False, stream: Optional[int] = None):
+        """mpcb_step: one MPC step of every simulation from the states io['xhat'] (device tensors named as the fields of
+        mpcb_step_io; 'x_pred' / 'u_pred' optional).  Asynchronous on `stream` (default: the current torch stream)."""
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._step_struct(io)
+        self._check(self.lib.mpcb_step(self._h, C.byref(r), int(bool(reset)), C.c_void_p(stream)), "mpcb_step")
 
     def debug_task_lin(self, cfgs: Sequence[Dict], chain, x: np.ndarray) -> np.ndarray:
         """Diagnostic: the device linearisation at points x[i] = [q; qdot] with the parameters of cfgs[i];

@@ -1,4 +1,5 @@
-"""Scan the gfx950 assembly of the rollout kernel for a known hipcc 7.2 miscompile.
+"""Scan the gfx950 assembly of the latency engine's kernels (rollout module mpc_kernel.hip, controller step module mpc_step.hip)
+for a known hipcc 7.2 miscompile and for register spills beyond their recorded budgets.
 
 A lane-divergent loop (`s_andn2_b64 exec ... s_cbranch_execnz`) falls through with an EMPTY exec
 mask; hipcc 7.2 sometimes places VGPR<-AGPR spill reloads (`v_accvgpr_read`) in that fall-through
@@ -11,6 +12,8 @@ import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_kernel.hip")
+# the controller step kernels (their own module): scanned like the rollout module, under the same budgets
+STEP_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_step.hip")
 
 
 def scan(asm_text):
@@ -58,6 +61,10 @@ BUDGET = {
 }
 
 
+# A step kernel is the rollout kernel of its geometry without the plant and the logs: it is held to that kernel's budget.
+KERNEL_ALIASES = (("15mpc_step_kernel", "18mpc_rollout_kernel"),)
+
+
 def scratch_by_function(asm_text):
     out, func = {}, None
     for l in asm_text.split("\n"):
@@ -77,8 +84,11 @@ def scratch_ops(asm_text):
     bad = {}
     for func, n in scratch_by_function(asm_text).items():
         limit = None
+        name = func
+        for alias, budgeted in KERNEL_ALIASES:
+            name = name.replace(alias, budgeted)
         for frag, b in BUDGET.items():
-            if frag in func:
+            if frag in name:
                 limit = b
         if limit is None:
             hot = (any(h in func for h in HOT) and any(g in func for g in HOT_GEOM)) or any(h in func for h in HOT_STREAM)
@@ -88,14 +98,21 @@ def scratch_ops(asm_text):
     return bad
 
 
+def compile_asm(src, d, extra):
+    out = os.path.join(d, os.path.basename(src) + ".s")
+    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--offload-device-only",
+                           "-o", out, src] + extra, cwd=d, stderr=subprocess.DEVNULL)
+    return open(out).read()
+
+
 def main():
     with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "k.s")
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--offload-device-only",
-                               "-o", out, SRC] + sys.argv[1:], cwd=d, stderr=subprocess.DEVNULL)
-        text = open(out).read()
+        text = compile_asm(SRC, d, sys.argv[1:])
         hits = scan(text)
         spills = scratch_ops(text)
+        step_text = compile_asm(STEP_SRC, d, sys.argv[1:])
+        hits += scan(step_text)
+        spills.update(scratch_ops(step_text))
     for h in hits:
         print("vector op under empty exec after divergent loop: %s line %d -> %d: %s" % h)
     for f, (n, limit) in spills.items():

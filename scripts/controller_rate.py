@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Closed-loop rate of the controller step (BatchController / mpcb_step) against the rollout (mpcb_rollout) on BASELINE
+configs[1]'s shape: batch 256, N = 100, SQP_RTI, 600 closed-loop steps (bench.workload_configs).
+
+The step path closes the loop over an RK4 plant written in torch on the device (the model's own dynamics, q' = qdot,
+qdot' = wcv (u - qdot)), so no host round trip sits in the loop.  Both paths are timed with device events after a warm-up
+run; the step path also reports the device time of the step launches alone (events around each launch).  Prints one JSON line.
+
+    python scripts/controller_rate.py [--batch 256] [--N 100] [--steps 600] [--skip-rollout]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def raw_configs(batch, N, steps, seed=0):
+    """bench.workload_configs's draws as the (unresolved) dicts BatchController takes."""
+    import numpy as np
+
+    from robotic_mpc_amd import config
+
+    rng = np.random.default_rng(seed)
+    flat = dict(a=0.0, b=0.0, c=0.0, d=0.0, e=0.0, f=0.0)
+    return [config.base_params(prediction_horizon=N, simulation_time=0.01 * steps, q_0=config.BASE_PARAMS["q_0"] + rng.uniform(-0.1, 0.1, 6),
+                               surface_coeffs=flat, solver_options={"nlp_solver_type": "SQP_RTI"}) for _ in range(batch)]
+
+
+def rk4_plant(wcv, dt):
+    """RK4 step of the joint model q' = qdot, qdot' = wcv (u - qdot) on [B, 12] device tensors."""
+    import torch
+
+    def f(x, u):
+        return torch.cat([x[:, 6:], wcv * (u - x[:, 6:])], 1)
+
+    def step(x, u):
+        k1 = f(x, u)
+        k2 = f(x + 0.5 * dt * k1, u)
+        k3 = f(x + 0.5 * dt * k2, u)
+        k4 = f(x + dt * k3, u)
+        return x + (dt / 6) * (k1 + 2 * k2 + 2 * k3 + k4)
+    return step
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--N", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=600)
+    ap.add_argument("--skip-rollout", action="store_true")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+
+    import bench
+    from robotic_mpc_amd import BatchController, engine
+    from robotic_mpc_amd.simulator import chain_for
+
+    B, S = args.batch, args.steps
+    raw = raw_configs(B, args.N, S)
+    ctl = BatchController(raw)
+    cfgs = ctl.configs
+    dev = torch.device("cuda", 0)
+    wcv = torch.tensor(np.stack([c["wcv"] for c in cfgs]), dtype=torch.float64, device=dev)
+    plant = rk4_plant(wcv, cfgs[0]["dt"])
+    x0 = torch.tensor(np.stack([np.concatenate([c["q0"], c["qdot0"]]) for c in cfgs]), dtype=torch.float64, device=dev)
+
+    def closed_loop(events=None):
+        ctl.reset()
+        x = x0
+        for _ in range(S):
+            if events is not None:
+                events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                events[-1][0].record()
+            u = ctl.step(x)["u0"]
+            if events is not None:
+                events[-1][1].record()
+            x = plant(x, u)
+        return x
+
+    closed_loop()                                   # warm-up (code objects, allocator)
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    xf = closed_loop()
+    t1.record()
+    torch.cuda.synchronize()
+    loop_ms = t0.elapsed_time(t1)
+    ev = []
+    closed_loop(ev)
+    torch.cuda.synchronize()
+    step_ms = [a.elapsed_time(b) for a, b in ev]
+    out = dict(workload=f"batch {B}, N {args.N}, SQP_RTI, {S} steps", step_loop_ms=round(loop_ms, 3),
+               step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
+               step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
+               launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
+    if not args.skip_rollout:
+        bc = bench.workload_configs(B, args.N, 0.01 * S, seed=0, solver="SQP_RTI")
+        e = engine.MpcBatchEngine(0)
+        chain = chain_for(bc[0])
+        pb = e.setup(bc, chain)
+        bufs = e.alloc_results(pb)
+        e.rollout(bufs, 0, S)                       # warm-up
+        e.sync()
+        ms = []
+        for _ in range(3):
+            e.setup(bc, chain)
+            e.rollout(bufs, 0, S)
+            e.sync()
+            ms.append(e.kernel_ms())
+        out.update(rollout_ms=[round(m, 3) for m in ms], rollout_steps_per_s=round(B * S / (min(ms) * 1e-3)),
+                   rollout_launch_info=e.launch_info(), step_over_rollout_kernel_time=round(float(np.sum(step_ms)) / min(ms), 3))
+        e.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
