@@ -213,7 +213,8 @@ typedef struct {
 
 /* Like mpcb_setup (same validation and packing; Nsim is checked but not used), for mpcb_step: always the latency engine,
  * at any batch size, with mpcb_setup's geometry rules.  Refuses ragged horizons (parameter [65] != 0 and != N) and
- * MPCB_PRECISION_FP32_RICCATI with MPCB_EINVAL (the throughput engine alone implements those).  On the handle this sets
+ * MPCB_PRECISION_FP32_RICCATI with MPCB_EINVAL (mpcb_setup_controller_on below runs the step on the throughput engine,
+ * ragged horizons included).  On the handle this sets
  * up, mpcb_rollout and mpcb_summary return MPCB_ESTATE; mpcb_setup or mpcb_run set it up for rollouts again. */
 int mpcb_setup_controller(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host);
 
@@ -224,6 +225,33 @@ int mpcb_setup_controller(mpcb_handle *h, const mpcb_problem *p, const double *p
  * mpcb_sync and mpcb_last_kernel_ms apply to it.  MPCB_ESTATE on a handle not set up by mpcb_setup_controller.
  * mpcb_kernel_info and mpcb_launch_info report the step kernel on a controller handle. */
 int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream);
+
+/* ---- the controller step on either kernel family ---- */
+#define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
+#define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */
+#define MPCB_ENGINE_STREAM 1     /* one wavefront per simulation (mpc_stream_step_kernel)                */
+/* Crossover of the controller step (profiles/controller_step_rate_stream.txt): N = 100, SQP_RTI, a closed loop of 600 steps over a
+ * torch RK4 plant, device time of the 600 step launches, latency vs throughput engine: 1024 simulations 272 vs 313 ms, 1280: 346 vs
+ * 338 ms, 2048: 492 vs 399 ms, 4096: 925 vs 694 ms (1.33x; kernel trace at 4096: median step 1404 vs 990 us).  Full SQP never crossed
+ * over: at 4096 simulations 5.70 s vs 9.35 s -- a step launch ends with its slowest simulation, and in the settling phase that is a
+ * chain of many SQP iterations, which the latency engine's four wavefronts per simulation run faster than one (a rollout's work
+ * queue spreads such chains over its items; one step cannot).  So a uniform full-SQP batch stays on the latency engine. */
+#define MPCB_STREAM_MIN_BATCH_STEP 1280       /* SQP_RTI: the throughput engine from this many simulations on */
+
+/* Like mpcb_setup_controller, on the kernel family `engine` (MPCB_ENGINE_*).  MPCB_ENGINE_LATENCY is mpcb_setup_controller.
+ * MPCB_ENGINE_STREAM runs each simulation's step on one wavefront, and accepts ragged horizons (parameter [65], SQP_RTI only,
+ * as in a rollout); mpcb_problem.N is then the longest horizon, and the rows of x_pred / u_pred beyond a simulation's own
+ * horizon are written as NaN.  MPCB_ENGINE_AUTO takes mpcb_controller_engine_for's choice; there, and only there, the environment
+ * variable MPCB_ENGINE=latency|stream overrides it for a uniform batch.  MPCB_EINVAL: an unknown engine, ragged horizons on the
+ * latency engine or with full SQP, MPCB_PRECISION_FP32_RICCATI on any engine.  mpcb_step, mpcb_engine, mpcb_kernel_info and
+ * mpcb_launch_info (1 wavefront per simulation, no LDS pool) report the family chosen. */
+int mpcb_setup_controller_on(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host, int engine);
+
+/* The family MPCB_ENGINE_AUTO picks for the controller step of `p` (0 latency, 1 throughput engine; < 0: error).  Host logic only,
+ * no device touched.  `ragged` != 0: the simulations have different horizons (always the throughput engine).  A uniform SQP_RTI
+ * batch goes to the throughput engine from MPCB_STREAM_MIN_BATCH_STEP simulations on, a uniform full-SQP batch to the latency
+ * engine at every size.  Nsim is ignored: a controller has no run length. */
+int mpcb_controller_engine_for(const mpcb_problem *p, int ragged);
 
 #ifdef __cplusplus
 }

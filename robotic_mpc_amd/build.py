@@ -11,8 +11,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmpcbatch.so")
 LIB_PROF = os.path.join(HERE, "libmpcbatch_prof.so")
 ARCH = "gfx950"
-# translation units of the library: the rollout kernels + C ABI, and the controller step kernels (a module of their own)
-SOURCES = ("mpc_kernel.hip", "mpc_step.hip")
+# translation units of the library: the rollout kernels + C ABI, and the controller step kernels of each engine (modules of their own)
+SOURCES = ("mpc_kernel.hip", "mpc_step.hip", "mpc_stream_step.hip")
 
 
 def _stale(target: str) -> bool:

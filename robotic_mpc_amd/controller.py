@@ -1,9 +1,10 @@
 """BatchController: the MPC solve as a batched controller for a plant the caller owns.
 
 Where ``Simulator.run`` closes the loop over the engine's own plant, a controller takes B measured states and returns B
-controls -- acados' ``set(0, 'lbx', x); solve(); get(0, 'u')`` (simulator.py:210-221) for a whole batch in one launch of
-the latency engine (``mpcb_setup_controller`` / ``mpcb_step``, include/mpcbatch.h).  Between steps every simulation keeps
-its iterate, linearisation and QP memory on the device: step k warm-starts from step k-1, as acados does.
+controls -- acados' ``set(0, 'lbx', x); solve(); get(0, 'u')`` (simulator.py:210-221) for a whole batch in one launch
+(``mpcb_setup_controller_on`` / ``mpcb_step``, include/mpcbatch.h), on the latency engine or the throughput engine.  Between
+steps every simulation keeps its iterate, linearisation and QP memory on the device: step k warm-starts from step k-1, as
+acados does.
 
     ctl = BatchController([base_params(prediction_horizon=50) for _ in range(256)])
     x = torch.tensor(x0, dtype=torch.float64, device="cuda")     # [256, 12] q; qdot
@@ -18,42 +19,68 @@ from typing import Dict, Mapping, Optional, Sequence
 import numpy as np
 
 from . import config as cfgmod, packing
-from .engine import STEP_FIELDS, MpcBatchEngine
+from .engine import CONTROLLER_ENGINES, STEP_FIELDS, MpcBatchEngine
 
 
 class BatchController:
     """One MPC controller per configuration, all solved together on one GPU.
 
     ``configs`` are the per-simulation dicts ``Simulator`` / ``SimulationManager`` take (``config.base_params``); they must
-    share one launch bucket (same horizon, solver options, robot and ``simulation_time / dt``) and use fp64 Riccati.  Their
-    ``q_0`` / ``qdot_0`` seed the initial guess of the iterate (x_k = [q_0; qdot_0], u_k = 0), exactly as in a rollout.
-    Anything else raises ``ValueError`` before the device is touched; without a GPU, construction raises ``EngineError``.
+    share one launch bucket (same solver options, robot and ``simulation_time / dt``) and use fp64 Riccati.  Their ``q_0`` /
+    ``qdot_0`` seed the initial guess of the iterate (x_k = [q_0; qdot_0], u_k = 0), exactly as in a rollout.
+
+    ``engine`` picks the kernel family of the step:
+
+    * ``"latency"`` (the default): one workgroup of 4-8 wavefronts per simulation; one prediction horizon for the batch.
+    * ``"stream"``: the throughput engine, one wavefront per simulation -- the faster one for large batches.  It also takes
+      configurations of DIFFERENT prediction horizons with SQP_RTI (a ragged batch, e.g. a grid over ``prediction_horizon``).
+    * ``"auto"``: ragged batches go to the throughput engine, the only one that runs them; a uniform batch goes there from
+      ``MPCB_STREAM_MIN_BATCH_STEP`` (1280) SQP_RTI simulations on, the batch size from which it measured faster, and to the
+      latency engine below; a uniform full-SQP batch always goes to the latency engine, since one step launch lasts as long as its
+      slowest simulation's SQP iterations, which four wavefronts run faster than one (include/mpcbatch.h).
+      ``launch_info()["engine"]`` tells which.
+
+    ``horizons`` holds each configuration's horizon and ``N`` the longest: the prediction buffers have N + 1 / N rows, and the
+    rows beyond a configuration's own horizon are NaN.  Anything the chosen engine cannot run raises ``ValueError`` before
+    the device is touched; without a GPU, construction raises ``EngineError``.
     """
 
-    def __init__(self, configs: Sequence[Mapping], device: int = 0):
+    def __init__(self, configs: Sequence[Mapping], device: int = 0, engine: str = "latency"):
+        if engine not in CONTROLLER_ENGINES:
+            raise ValueError(f"engine must be one of {sorted(CONTROLLER_ENGINES)}, got {engine!r}")
         if len(configs) == 0:
             raise ValueError("BatchController needs at least one configuration")
         cfgs = [cfgmod.resolve_config(c) for c in configs]
-        key0 = packing.bucket_key(cfgs[0])
+        horizons = np.array([c["N"] for c in cfgs], dtype=np.int64)
+        ragged = bool((horizons != horizons[0]).any())
+        if ragged and engine == "latency":
+            raise ValueError("configurations of different prediction horizons need engine='stream' or 'auto': the latency "
+                             "engine's controller step needs one horizon for the whole batch")
+        key0 = packing.bucket_key(cfgs[0], ragged=engine != "latency")
         for i, c in enumerate(cfgs[1:], 1):
-            if packing.bucket_key(c) != key0:
+            if packing.bucket_key(c, ragged=engine != "latency") != key0:
                 raise ValueError(f"configuration {i} does not share the bucket of configuration 0: one controller batch needs "
-                                 "one prediction horizon, the same solver options, robot and simulation_time / dt")
+                                 "the same solver options, robot and simulation_time / dt (and, on the latency engine, one "
+                                 "prediction horizon)")
+        if ragged and cfgs[0]["solver_type"] != packing.SOLVER_RTI:
+            raise ValueError("configurations of different prediction horizons share a controller batch only with SQP_RTI")
         if cfgs[0]["precision"] != 0:
-            raise ValueError("riccati_precision='fp32' runs on the throughput engine only; the controller step is fp64")
+            raise ValueError("riccati_precision='fp32' is refused by the controller step on every engine: it is fp64 only")
         from .simulator import chain_for
 
         chain = chain_for(cfgs[0])
         self.configs = cfgs
-        self.batch, self.N = len(cfgs), cfgs[0]["N"]
+        self.horizons = horizons
+        self.batch, self.N = len(cfgs), int(horizons.max())
         self.engine = MpcBatchEngine(device)
         self.device = self.engine.device
-        self.engine.setup_controller(cfgs, chain)
+        self.engine.setup_controller(cfgs, chain, engine=engine)
         self._bufs: Optional[Dict] = None
         self._reset = True
 
     def _buffers(self, predict: bool):
-        """The output buffers of a step; x_pred / u_pred ([B, N+1, 12] + [B, N, 6]) only from the first step that asks for them."""
+        """The output buffers of a step; x_pred / u_pred ([B, N+1, 12] + [B, N, 6], N the longest horizon) only from the first step
+        that asks for them."""
         import torch
 
         if self._bufs is None:
@@ -86,7 +113,7 @@ class BatchController:
 
         Returns device tensors: ``u0`` [B, 6] (the input to apply), ``status``, ``sqp_iter``, ``qp_iter`` [B] (int32),
         ``residuals`` [B, 4], ``cost``, ``solver_time`` [B]; with ``predict`` also the iterate's predicted trajectory
-        ``x_pred`` [B, N+1, 12] and ``u_pred`` [B, N, 6].  The launch is asynchronous on the current torch stream and nothing
+        ``x_pred`` [B, N+1, 12] and ``u_pred`` [B, N, 6] (N the longest horizon; rows past ``horizons[i]`` are NaN).  The launch is asynchronous on the current torch stream and nothing
         is synchronised.  The returned tensors are the controller's own buffers: the next ``step`` overwrites them, so clone
         what must outlive it."""
         import torch
@@ -103,7 +130,7 @@ class BatchController:
         self._reset = True
 
     def launch_info(self) -> Dict[str, int]:
-        """Geometry of the step kernel: kernel family (always 0, the latency engine), wavefronts per simulation, LDS pool."""
+        """Geometry of the step kernel: kernel family (0 latency, 1 throughput engine), wavefronts per simulation, LDS pool."""
         return self.engine.launch_info()
 
     def close(self):

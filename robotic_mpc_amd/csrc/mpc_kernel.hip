@@ -34,6 +34,10 @@ namespace mpcb {
 const void *step_kernel(int waves_per_sim, int wpe);
 void launch_step(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
                  const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
+// ... and the throughput engine's step kernel in mpc_stream_step.hip, for the same reason
+const void *stream_step_kernel();
+void launch_stream_step(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                        size_t ws_stride, const StepIO &io, int reset);
 }  // namespace mpcb
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
@@ -316,6 +320,19 @@ static int pick_engine(const mpcb_problem *p, bool ragged = false)
     }
     return e;
 }
+// which kernel family runs the controller step of `p` under MPCB_ENGINE_AUTO (see include/mpcbatch.h): ragged batches need the
+// throughput engine; a uniform batch crosses over at the measured batch sizes (profiles/controller_step_rate_stream.txt)
+static int pick_controller_engine(const mpcb_problem *p, bool ragged)
+{
+    if (ragged) return MPCB_ENGINE_STREAM;
+    // (full SQP: the latency engine at every batch size measured -- a step ends with its slowest simulation's chain of SQP iterations)
+    int e = p->solver_type == MPCB_SOLVER_SQP_RTI && p->batch >= MPCB_STREAM_MIN_BATCH_STEP ? MPCB_ENGINE_STREAM : MPCB_ENGINE_LATENCY;
+    if (const char *env = getenv("MPCB_ENGINE")) {
+        if (!strcmp(env, "stream")) e = MPCB_ENGINE_STREAM;
+        else if (!strcmp(env, "latency")) e = MPCB_ENGINE_LATENCY;
+    }
+    return e;
+}
 static size_t ws_doubles_for(const mpcb_problem *p, bool ragged = false)
 {
     if (pick_engine(p, ragged) == 0) return ws_doubles_per_instance(p->N);
@@ -336,15 +353,19 @@ size_t mpcb_result_bytes_per_sim(const mpcb_problem *p)
     return (12 + 6 + 12 + 3 + 6 + 7) * T1 * sizeof(double) + 3 * S * sizeof(int) + (4 + 1 + 1 + 1) * S * sizeof(double);
 }
 
-// mpcb_setup and mpcb_setup_controller: validate, pack and upload the records, size the workspace, pick the geometry.
-// `controller`: the latency engine at any batch size, uniform horizons and fp64 only.
-static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host, bool controller)
+// mpcb_setup and mpcb_setup_controller(_on): validate, pack and upload the records, size the workspace, pick the geometry.
+// `controller`: the controller step on kernel family `ctl_engine` (MPCB_ENGINE_*), fp64 only; ragged horizons on the throughput
+// engine only, with SQP_RTI.
+static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host, bool controller,
+                      int ctl_engine = MPCB_ENGINE_LATENCY)
 {
     if (!h) return MPCB_EINVAL;
     int rc = check_problem(h, p);
     if (rc) return rc;
+    if (controller && ctl_engine != MPCB_ENGINE_LATENCY && ctl_engine != MPCB_ENGINE_STREAM && ctl_engine != MPCB_ENGINE_AUTO)
+        return fail(h, MPCB_EINVAL, "engine must be MPCB_ENGINE_LATENCY, MPCB_ENGINE_STREAM or MPCB_ENGINE_AUTO");
     if (controller && p->precision != MPCB_PRECISION_FP64)
-        return fail(h, MPCB_EINVAL, "the controller step runs on the latency engine, which has no fp32 Riccati leg");
+        return fail(h, MPCB_EINVAL, "the controller step is fp64 only (no fp32 Riccati leg on either engine)");
     if (!params_host || !robot_host) return fail(h, MPCB_EINVAL, "params/robot pointer is NULL");
     HIPCHK(h, hipSetDevice(h->device));
     std::vector<InstParams> packed((size_t)p->batch);
@@ -363,8 +384,11 @@ static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *param
             if (std::isnan(pp[j])) return fail(h, MPCB_EINVAL, "NaN in parameter record");
         pack_inst_params(pp, &packed[(size_t)i]);
     }
-    if (controller && ragged)
-        return fail(h, MPCB_EINVAL, "the controller step needs one horizon for the whole batch (parameter [65] must be 0 or N)");
+    if (controller && ctl_engine == MPCB_ENGINE_AUTO) ctl_engine = pick_controller_engine(p, ragged);
+    if (controller && ragged && ctl_engine == MPCB_ENGINE_LATENCY)
+        return fail(h, MPCB_EINVAL, "the latency engine's controller step needs one horizon for the whole batch (parameter [65] must be 0 or N)");
+    if (controller && ragged && p->solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "simulations of different horizons share a controller batch only with SQP_RTI");
     std::memcpy(&h->rb, robot_host, sizeof(Robot));
     std::memcpy(&h->pb, p, sizeof(Problem));
     const size_t pbytes = packed.size() * sizeof(InstParams);
@@ -377,8 +401,10 @@ static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *param
     HIPCHK(h, hipMemcpy(h->d_params, packed.data(), pbytes, hipMemcpyHostToDevice));
     h->d_rb = reinterpret_cast<Robot *>(reinterpret_cast<char *>(h->d_params) + pbytes);
     HIPCHK(h, hipMemcpy(h->d_rb, &h->rb, sizeof(Robot), hipMemcpyHostToDevice));
-    h->engine = controller ? 0 : pick_engine(p, ragged);
-    h->ws_stride = controller ? ws_doubles_per_instance(p->N) : ws_doubles_for(p, ragged);
+    h->engine = controller ? ctl_engine : pick_engine(p, ragged);
+    h->ws_stride = !controller ? ws_doubles_for(p, ragged)
+                 : h->engine == MPCB_ENGINE_STREAM ? se::sws_doubles_per_instance<double>(p->N, p->solver_type == MPCB_SOLVER_SQP)
+                                                   : ws_doubles_per_instance(p->N);
     const size_t wbytes = (size_t)p->batch * h->ws_stride * sizeof(double);
     if (wbytes > h->ws_cap) {
         if (h->d_ws) (void)hipFree(h->d_ws);
@@ -444,6 +470,17 @@ int mpcb_setup(mpcb_handle *h, const mpcb_problem *p, const double *params_host,
 int mpcb_setup_controller(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host)
 {
     return setup_impl(h, p, params_host, robot_host, true);
+}
+
+int mpcb_setup_controller_on(mpcb_handle *h, const mpcb_problem *p, const double *params_host, const double *robot_host, int engine)
+{
+    return setup_impl(h, p, params_host, robot_host, true, engine);
+}
+
+int mpcb_controller_engine_for(const mpcb_problem *p, int ragged)
+{
+    if (!p || p->N < 1 || p->batch < 1) return MPCB_EINVAL;
+    return pick_controller_engine(p, ragged != 0);
 }
 
 // the latency engine's kernel for the handle's geometry: the step kernel on a controller handle, the rollout kernel otherwise
@@ -573,6 +610,18 @@ int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream)
     StepIO sio;
     std::memcpy(&sio, io, sizeof sio);
     const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
+    if (h->engine == MPCB_ENGINE_STREAM) {
+        // throughput engine: one wavefront per simulation, static LDS only, no work queue
+        HIPCHK(h, hipEventRecord(h->ev0, s));
+        launch_stream_step(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipEventRecord(h->ev1, s));
+        h->last_stream = s;
+        h->timed = true;
+        h->queue_used = false;
+        h->reset_next = false;
+        return MPCB_OK;
+    }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
     if (int rc = raise_lds_limit(h)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
@@ -613,7 +662,9 @@ int mpcb_kernel_info(mpcb_handle *h, int *vgprs, int *sgprs, int *lds_bytes, int
 {
     if (!h) return MPCB_EINVAL;
     hipFuncAttributes a;
-    if (h->engine == 1) {
+    if (h->engine == 1 && h->controller) {
+        HIPCHK(h, hipFuncGetAttributes(&a, stream_step_kernel()));
+    } else if (h->engine == 1) {
         HIPCHK(h, hipFuncGetAttributes(&a, h->pb.precision == MPCB_PRECISION_FP32_RICCATI ? (const void *)mpc_stream_kernel<float>
                                                                                           : (const void *)mpc_stream_kernel<double>));
     } else

@@ -2497,6 +2497,179 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
     if (lane < NX) w.state[lane] = sm.xhat[lane];
     if (lane == 12) { w.state[12] = lin_cost; w.state[25] = lin_valid ? 1.0 : 0.0; w.state[26] = fast[0]; w.state[27] = fast[1]; w.state[28] = cur; }
 }
+
+// Controller step (mpcb_step, mpc_stream_step.hip): ONE step of rollout<FT>'s loop for simulation `inst`, from the caller's state
+// io.xhat, with no plant and no logs.  The solver memory carries over in the workspace as between two rollout launches (w.state:
+// [12] lin_cost, [25] lin_valid, [26..27] fast, [28] cur; the x_0 merit weights [13..24] in place); `reset` starts from the acados
+// initial guess instead (the rollout's step 0).  Every step is the last of its launch: its cost and residual norms are formed by a
+// trailing pass here, not deferred to the next step's first pass (res_pending), since the caller reads them when the launch returns.
+template <class FT>
+SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
+                         const StepIO &io, int inst, bool reset)
+{
+    SSmem &sm = g_ssm;
+    const int lane = threadIdx.x;
+    // ragged batch: this simulation's own horizon (the workspace stride is sized for the longest)
+    const double nh = params[inst].n_hor;
+    const int N = uni(nh > 0.0 ? (int)nh : pb.N), NMAX = pb.N;
+    {
+        const double *ps = reinterpret_cast<const double *>(params + inst);
+        double *pd = reinterpret_cast<double *>(&sm.P);
+        for (int e = lane; e < (int)(sizeof(InstParams) / sizeof(double)); e += WAVE) pd[e] = ps[e];
+        if (lane == 0) {
+            sm.rbp = rbp;
+            SWs ws = sws_carve<FT>(ws_base + (size_t)inst * ws_stride, N, pb.solver_type == 0);
+            ws.state = ws_base + (size_t)inst * ws_stride + (ws_stride - STATE_DOUBLES);
+            sm.w = ws;
+            sm.n_hor = N;
+        }
+    }
+    fence();
+    const InstParams &P = sm.P;
+    const SWs w = sm.w;
+    bool lin_valid = false;
+    double lin_cost = 0.0;
+    int fast[2] = {0, 0};
+    int cur = 0;
+    if (uni(reset ? 1 : 0)) {
+        // acados initial guess: x_k = x0, u_k = 0, all multipliers / QP memory 0
+        const size_t tot = sws_doubles_per_instance<FT>(N, pb.solver_type == 0) - STATE_DOUBLES;
+        for (size_t e = lane; e < tot; e += WAVE) w.G1[e] = 0.0;      // G1 is the workspace base
+        if (lane < STATE_DOUBLES) w.state[lane] = 0.0;
+        fence();
+        for (int e = lane; e < (N + 1) * NX; e += WAVE) {
+            const int k = e / NX, i = e - k * NX;
+            w.G1[(size_t)k * (w.ld / 8) + O_X + i] = i < 6 ? P.q0[i] : P.qdot0[i - 6];
+        }
+        __builtin_amdgcn_s_waitcnt(0);                                // the initial iterate is in memory before the first pass reads it
+        fence();
+    } else {
+        lin_cost = unid(w.state[12]);
+        lin_valid = uni(w.state[25] != 0.0 ? 1 : 0) != 0;
+        fast[0] = uni((int)w.state[26]); fast[1] = uni((int)w.state[27]); cur = uni((int)w.state[28]);
+    }
+    if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
+    fence();
+    int qp_iter = 0, status = 0, sqp_iter = 1;
+    double res4[4] = {0, 0, 0, 0};
+    double cost = lin_cost;
+    const double t0 = wclock();
+    if (pb.solver_type == 1) {
+        // SQP_RTI: one linearisation, one QP, full step -- rollout<FT>'s step with res_pending false on entry and on exit
+#ifdef MPCB_STREAM_SEQ_RES
+        if (!lin_valid) { lin_pass(0.0, false); __builtin_amdgcn_s_waitcnt(0); fence(); lin_cost = unid(nlp_res_pass<false>(nullptr)); }
+#else
+        if (!lin_valid) {
+            lin_pass(0.0, false); __builtin_amdgcn_s_waitcnt(0); fence();
+            double o5[5];
+            rti_items<true, false>(0, o5, cur);
+            lin_cost = unid(o5[0]);
+        }
+#endif
+        const int qs = ipm_solve<FT>(pb.qp_iter_max, &qp_iter, fast, nullptr, &cur);
+        const bool ok = qs == 0 || qs == 1;
+        if (!ok) status = 4;                                           // ACADOS_QP_FAILURE, iterate untouched
+        __builtin_amdgcn_s_waitcnt(0);
+#ifdef MPCB_STREAM_SEQ_RES
+        lin_pass(1.0, ok);
+#else
+        lin_pass(1.0, ok, false, cur);
+#endif
+        __builtin_amdgcn_s_waitcnt(0);                                 // the records written lane by lane are complete before they are streamed
+        fence();
+#ifdef MPCB_STREAM_SEQ_RES
+        cost = unid(nlp_res_pass<false>(res4));
+#else
+        double o5[5];
+        rti_items<true, false>(0, o5, cur);                            // the caller reads the norms when this launch returns
+        cost = unid(o5[0]); res4[0] = o5[1]; res4[1] = o5[2]; res4[2] = o5[3]; res4[3] = o5[4];
+#endif
+        lin_valid = true;
+    } else {
+        // full SQP: rollout<FT>'s step as it stands (its norms are never deferred)
+        const double tol = P.tol, tol_eq = P.tol_eq, tol_in = P.tol_ineq, tol_co = P.tol_comp;
+        status = 2;
+        double alpha = 0.0;
+        bool pending = false;
+        for (sqp_iter = 0; sqp_iter < pb.max_iter; sqp_iter++) {
+            if (pending || !lin_valid || sqp_iter == 0) {
+                __builtin_amdgcn_s_waitcnt(0);
+                lin_pass(alpha, pending, true);
+                __builtin_amdgcn_s_waitcnt(0);
+                fence();
+#ifdef MPCB_STREAM_SEQ_RES
+                cost = unid(nlp_res_pass<true>(res4));
+                res4[0] = unid(res4[0]); res4[1] = unid(res4[1]); res4[2] = unid(res4[2]); res4[3] = unid(res4[3]);
+#else
+                double o5[5];
+                rti_items<true, false, true>(0, o5);
+                cost = unid(o5[0]); res4[0] = unid(o5[1]); res4[1] = unid(o5[2]); res4[2] = unid(o5[3]); res4[3] = unid(o5[4]);
+#endif
+                pending = false;
+                lin_valid = true;
+            }
+            if (res4[0] < tol && res4[1] < tol_eq && res4[2] < tol_in && res4[3] < tol_co) { status = 0; break; }
+            if (res4[0] != res4[0] || cost != cost) { status = 1; break; }
+            int it = 0;
+            const int qs = ipm_solve<FT>(pb.qp_iter_max, &it, fast);
+            qp_iter += it;
+            if (qs != 0 && qs != 1) { status = 4; break; }
+            __builtin_amdgcn_s_waitcnt(0);
+            fence();
+            alpha = pb.fixed_step ? 1.0 : line_search(sqp_iter);
+            pending = true;
+        }
+        if (pending) {   // max-iter exit: apply the last step; the residuals of the last check stay
+            __builtin_amdgcn_s_waitcnt(0);
+            lin_pass(alpha, true, true);
+            __builtin_amdgcn_s_waitcnt(0);
+            fence();
+#ifdef MPCB_STREAM_SEQ_RES
+            cost = unid(nlp_res_pass<true>(nullptr));
+#else
+            double o5[5];
+            rti_items<true, false, true>(0, o5);
+            cost = unid(o5[0]);
+#endif
+            lin_valid = true;
+        }
+    }
+    lin_cost = cost;
+    __builtin_amdgcn_s_waitcnt(0);
+    fence();
+    const double t1 = wclock();
+    // solver.get(0,'u') and the step's statistics.  The NLP iterate lives in G1 [X | U] whichever slot `cur` names (that is the QP
+    // iterate's: the step lin_pass has just applied).
+    if (lane < NU) io.u0[(size_t)inst * NU + lane] = w.G1[O_U + lane];
+    if (lane == 8) {
+        io.status[inst] = status;
+        io.sqp_iter[inst] = sqp_iter;
+        io.qp_iter[inst] = qp_iter;
+        io.cost[inst] = cost;
+        io.solver_time[inst] = t1 - t0;
+    }
+    if (lane >= 12 && lane < 16) io.residuals[(size_t)inst * 4 + (lane - 12)] =
+        lane == 12 ? res4[0] : (lane == 13 ? res4[1] : (lane == 14 ? res4[2] : res4[3]));
+    // the predicted trajectory x_0..x_N, u_0..u_{N-1} (orc_solver_get_iterate), in rows sized for the longest horizon of the batch: the
+    // rows beyond this simulation's own horizon are NaN, so that nothing stale passes for a prediction
+    const int LD = w.ld / 8;
+    if (io.x_pred) {
+        double *xp = io.x_pred + (size_t)inst * (NMAX + 1) * NX;
+        for (int e = lane; e < (NMAX + 1) * NX; e += WAVE) {
+            const int k = e / NX, i = e - k * NX;
+            xp[e] = k <= N ? w.G1[(size_t)k * LD + O_X + i] : __builtin_nan("");
+        }
+    }
+    if (io.u_pred) {
+        double *up = io.u_pred + (size_t)inst * NMAX * NU;
+        for (int e = lane; e < NMAX * NU; e += WAVE) {
+            const int k = e / NU, j = e - k * NU;
+            up[e] = k < N ? w.G1[(size_t)k * LD + O_U + j] : __builtin_nan("");
+        }
+    }
+    if (lane < NX) w.state[lane] = sm.xhat[lane];
+    if (lane == 12) { w.state[12] = lin_cost; w.state[25] = lin_valid ? 1.0 : 0.0; w.state[26] = fast[0]; w.state[27] = fast[1]; w.state[28] = cur; }
+}
 #endif  // __HIP_DEVICE_COMPILE__
 
 }  // namespace se

@@ -66,6 +66,10 @@ STEP_FIELDS = (
 )
 
 
+# BatchController / setup_controller engine names -> the MPCB_ENGINE_* values of include/mpcbatch.h
+CONTROLLER_ENGINES = {"auto": -1, "latency": 0, "stream": 1}
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -73,7 +77,7 @@ class EngineError(RuntimeError):
 _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", "mpcb_last_error",
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
-            "mpcb_run", "mpcb_setup_controller", "mpcb_step")
+            "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -116,6 +120,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_engine.argtypes = [C.c_void_p]
     lib.mpcb_setup_controller.argtypes = [C.c_void_p, C.POINTER(MpcbProblem), _dp, _dp]
     lib.mpcb_step.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), C.c_int, C.c_void_p]
+    lib.mpcb_setup_controller_on.argtypes = [C.c_void_p, C.POINTER(MpcbProblem), _dp, _dp, C.c_int]
+    lib.mpcb_controller_engine_for.argtypes = [C.POINTER(MpcbProblem), C.c_int]
+    lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     return lib
@@ -140,6 +147,14 @@ def engine_for(batch: int, N: int, Nsim: int, solver: str = "SQP_RTI", precision
     lib = lib or load_library()
     pb = MpcbProblem(batch, N, Nsim, 0 if solver == "SQP" else 1, 100, 50, 0, precision)
     return int(lib.mpcb_engine_for(C.byref(pb)))
+
+
+def controller_engine_for(batch: int, N: int, solver: str = "SQP_RTI", ragged: bool = False, lib: Optional[C.CDLL] = None) -> int:
+    """Kernel family ``BatchController(..., engine="auto")`` runs a batch of this shape on (mpcb_controller_engine_for; host logic,
+    no GPU needed): 0 latency engine, 1 throughput engine."""
+    lib = lib or load_library()
+    pb = MpcbProblem(batch, N, 1, 0 if solver == "SQP" else 1, 100, 50, 0, 0)
+    return int(lib.mpcb_controller_engine_for(C.byref(pb), int(bool(ragged))))
 
 
 class MpcBatchEngine:
@@ -253,11 +268,14 @@ class MpcBatchEngine:
         return out
 
     # ------------------------------------------------------------------ controller step
-    def setup_controller(self, cfgs: Sequence[Dict], chain) -> MpcbProblem:
-        """mpcb_setup_controller: like setup(), for step() -- the latency engine at any batch size, one horizon, fp64."""
+    def setup_controller(self, cfgs: Sequence[Dict], chain, engine: str = "latency") -> MpcbProblem:
+        """mpcb_setup_controller_on: like setup(), for step(), fp64, on the kernel family `engine` ("latency": any batch size, one
+        horizon; "stream": one wavefront per simulation, ragged SQP_RTI horizons too; "auto": mpcb_controller_engine_for decides)."""
+        if engine not in CONTROLLER_ENGINES:
+            raise ValueError(f"engine must be one of {sorted(CONTROLLER_ENGINES)}, got {engine!r}")
         pb, params, robot = self.prepare(cfgs, chain)
-        self._check(self.lib.mpcb_setup_controller(self._h, C.byref(pb), params.ctypes.data_as(_dp), robot.ctypes.data_as(_dp)),
-                    "mpcb_setup_controller")
+        self._check(self.lib.mpcb_setup_controller_on(self._h, C.byref(pb), params.ctypes.data_as(_dp), robot.ctypes.data_as(_dp),
+                                                      CONTROLLER_ENGINES[engine]), "mpcb_setup_controller_on")
         self._pb = pb
         return pb
 

@@ -1,5 +1,5 @@
-"""Scan the gfx950 assembly of the latency engine's kernels (rollout module mpc_kernel.hip, controller step module mpc_step.hip)
-for a known hipcc 7.2 miscompile and for register spills beyond their recorded budgets.
+"""Scan the gfx950 assembly of the engine's kernels (rollout module mpc_kernel.hip, controller step modules mpc_step.hip and
+mpc_stream_step.hip) for a known hipcc 7.2 miscompile and for register spills beyond their recorded budgets.
 
 A lane-divergent loop (`s_andn2_b64 exec ... s_cbranch_execnz`) falls through with an EMPTY exec
 mask; hipcc 7.2 sometimes places VGPR<-AGPR spill reloads (`v_accvgpr_read`) in that fall-through
@@ -14,6 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_kernel.hip")
 # the controller step kernels (their own module): scanned like the rollout module, under the same budgets
 STEP_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_step.hip")
+# the throughput engine's controller step kernel (a module of its own as well): its passes are the rollout's, under HOT_STREAM
+STREAM_STEP_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_step.hip")
+SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC)
 
 
 def scan(asm_text):
@@ -62,7 +65,7 @@ BUDGET = {
 
 
 # A step kernel is the rollout kernel of its geometry without the plant and the logs: it is held to that kernel's budget.
-KERNEL_ALIASES = (("15mpc_step_kernel", "18mpc_rollout_kernel"),)
+KERNEL_ALIASES = (("15mpc_step_kernel", "18mpc_rollout_kernel"), ("22mpc_stream_step_kernel", "17mpc_stream_kernelId"))
 
 
 def scratch_by_function(asm_text):
@@ -106,13 +109,14 @@ def compile_asm(src, d, extra):
 
 
 def main():
+    hits, spills = [], {}
     with tempfile.TemporaryDirectory() as d:
-        text = compile_asm(SRC, d, sys.argv[1:])
-        hits = scan(text)
-        spills = scratch_ops(text)
-        step_text = compile_asm(STEP_SRC, d, sys.argv[1:])
-        hits += scan(step_text)
-        spills.update(scratch_ops(step_text))
+        for src in SOURCES:
+            text = compile_asm(src, d, sys.argv[1:])
+            hits += scan(text)
+            for f, (n, limit) in scratch_ops(text).items():     # (a pass compiled in several modules: its worst count)
+                if f not in spills or n > spills[f][0]:
+                    spills[f] = (n, limit)
     for h in hits:
         print("vector op under empty exec after divergent loop: %s line %d -> %d: %s" % h)
     for f, (n, limit) in spills.items():

@@ -4,9 +4,15 @@ configs[1]'s shape: batch 256, N = 100, SQP_RTI, 600 closed-loop steps (bench.wo
 
 The step path closes the loop over an RK4 plant written in torch on the device (the model's own dynamics, q' = qdot,
 qdot' = wcv (u - qdot)), so no host round trip sits in the loop.  Both paths are timed with device events after a warm-up
-run; the step path also reports the device time of the step launches alone (events around each launch).  Prints one JSON line.
+run; the step path also reports the device time of the step launches alone (events around each launch).  Prints one JSON line
+per (batch, engine) pair.
 
-    python scripts/controller_rate.py [--batch 256] [--N 100] [--steps 600] [--skip-rollout]
+`--engine` takes one or more kernel families (BatchController's engine=, "latency" by default) and `--batch` one or more batch
+sizes: every batch runs on each engine in turn, alternating, in one process.  The rollout is timed on the same family
+(MPCB_ENGINE) unless --skip-rollout.
+
+    python scripts/controller_rate.py [--batch 256 ...] [--engine latency|stream ...] [--N 100] [--steps 600] [--solver SQP_RTI]
+                                      [--skip-rollout]
 """
 import argparse
 import json
@@ -17,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def raw_configs(batch, N, steps, seed=0):
+def raw_configs(batch, N, steps, seed=0, solver="SQP_RTI"):
     """bench.workload_configs's draws as the (unresolved) dicts BatchController takes."""
     import numpy as np
 
@@ -26,7 +32,7 @@ def raw_configs(batch, N, steps, seed=0):
     rng = np.random.default_rng(seed)
     flat = dict(a=0.0, b=0.0, c=0.0, d=0.0, e=0.0, f=0.0)
     return [config.base_params(prediction_horizon=N, simulation_time=0.01 * steps, q_0=config.BASE_PARAMS["q_0"] + rng.uniform(-0.1, 0.1, 6),
-                               surface_coeffs=flat, solver_options={"nlp_solver_type": "SQP_RTI"}) for _ in range(batch)]
+                               surface_coeffs=flat, solver_options={"nlp_solver_type": solver}) for _ in range(batch)]
 
 
 def rk4_plant(wcv, dt):
@@ -47,11 +53,19 @@ def rk4_plant(wcv, dt):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--batch", type=int, nargs="+", default=[256])
+    ap.add_argument("--engine", nargs="+", choices=("latency", "stream"), default=["latency"])
     ap.add_argument("--N", type=int, default=100)
     ap.add_argument("--steps", type=int, default=600)
+    ap.add_argument("--solver", choices=("SQP_RTI", "SQP"), default="SQP_RTI")
     ap.add_argument("--skip-rollout", action="store_true")
     args = ap.parse_args()
+    for B in args.batch:
+        for eng in args.engine:
+            measure(args, B, eng)
+
+
+def measure(args, B, eng):
     import numpy as np
     import torch
 
@@ -59,9 +73,9 @@ def main():
     from robotic_mpc_amd import BatchController, engine
     from robotic_mpc_amd.simulator import chain_for
 
-    B, S = args.batch, args.steps
-    raw = raw_configs(B, args.N, S)
-    ctl = BatchController(raw)
+    S = args.steps
+    raw = raw_configs(B, args.N, S, solver=args.solver)
+    ctl = BatchController(raw, engine=eng)
     cfgs = ctl.configs
     dev = torch.device("cuda", 0)
     wcv = torch.tensor(np.stack([c["wcv"] for c in cfgs]), dtype=torch.float64, device=dev)
@@ -93,12 +107,13 @@ def main():
     closed_loop(ev)
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
-    out = dict(workload=f"batch {B}, N {args.N}, SQP_RTI, {S} steps", step_loop_ms=round(loop_ms, 3),
+    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, step_loop_ms=round(loop_ms, 3),
                step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
                step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
                launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
     if not args.skip_rollout:
-        bc = bench.workload_configs(B, args.N, 0.01 * S, seed=0, solver="SQP_RTI")
+        bc = bench.workload_configs(B, args.N, 0.01 * S, seed=0, solver=args.solver)
+        os.environ["MPCB_ENGINE"] = eng                 # the rollout on the same kernel family
         e = engine.MpcBatchEngine(0)
         chain = chain_for(bc[0])
         pb = e.setup(bc, chain)
@@ -114,7 +129,9 @@ def main():
         out.update(rollout_ms=[round(m, 3) for m in ms], rollout_steps_per_s=round(B * S / (min(ms) * 1e-3)),
                    rollout_launch_info=e.launch_info(), step_over_rollout_kernel_time=round(float(np.sum(step_ms)) / min(ms), 3))
         e.close()
-    print(json.dumps(out))
+        del os.environ["MPCB_ENGINE"]
+    ctl.close()
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
