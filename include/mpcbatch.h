@@ -226,6 +226,20 @@ int mpcb_setup_controller(mpcb_handle *h, const mpcb_problem *p, const double *p
  * mpcb_kernel_info and mpcb_launch_info report the step kernel on a controller handle. */
 int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream);
 
+/* ---- the controller step against a time-varying task reference (acados solver.set(k, 'yref', ...) between solves) ---- */
+#define MPCB_NREF 5              /* task outputs g1..g5: S(x,y) - z, n . z_task, y_task.x, p_x, v_task.y    */
+/* mpcb_step with the targets of the five task outputs given per simulation AND per stage: the stage-k residual is
+ * g(x_k) - yref[i][k] instead of g(x_k) - g_ref, g_ref = [0, 1, 0, px_ref, vy_ref] the references packed by mpcb_setup_controller
+ * (parameters [5] and [6]).  `yref` is a DEVICE pointer [batch][N][MPCB_NREF], N the longest horizon of the batch (stage N
+ * has no task cost, so there is no row N); on a ragged batch rows k >= the simulation's own horizon are never read.  NULL means
+ * the packed references.  The targets of the u and qddot cost rows stay 0.  The array is read during the launch only (the
+ * reference in force is the caller's to keep: pass it again with every step).
+ * `ref_changed` != 0 says that the reference differs from the previous step's (NULL counting as the packed one): the step then
+ * linearises again at its start instead of reusing the linearisation carried from the previous step, which was formed against the
+ * old reference.  Everything else carries as in mpcb_step.  With yref == NULL and ref_changed == 0 this is mpcb_step exactly:
+ * mpcb_step(h, io, reset, s) == mpcb_step_ref(h, io, NULL, 0, reset, s).  MPCB_ESTATE on a handle not set up as a controller. */
+int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, int reset, void *stream);
+
 /* ---- the controller step on either kernel family ---- */
 #define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
 #define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */

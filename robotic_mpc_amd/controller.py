@@ -11,6 +11,10 @@ acados does.
     for k in range(steps):
         u = ctl.step(x)["u0"]                                       # [256, 6] on the device
         x = my_plant(x, u)
+
+A controller regulates to the task reference packed from each configuration (``px_ref``, ``vy_ref``) unless it is given one
+with ``set_reference`` / ``step(..., yref=...)``: per simulation and per stage of the horizon, like acados'
+``set(k, 'yref', ...)`` between solves, and in force until it is changed (``default_reference()`` is the packed one).
 """
 from __future__ import annotations
 
@@ -20,6 +24,8 @@ import numpy as np
 
 from . import config as cfgmod, packing
 from .engine import CONTROLLER_ENGINES, STEP_FIELDS, MpcBatchEngine
+
+NREF = 5    # task outputs with a reference (MPCB_NREF, include/mpcbatch.h)
 
 
 class BatchController:
@@ -77,6 +83,13 @@ class BatchController:
         self.engine.setup_controller(cfgs, chain, engine=engine)
         self._bufs: Optional[Dict] = None
         self._reset = True
+        # task reference: the controller's own [B, N, 5] device buffer, whether it is in force, whether the next step must tell
+        # the device that it changed, and the streams that last wrote / read it
+        self._yref = None
+        self._ref_on = False
+        self._ref_changed = False
+        self._ref_stream = None
+        self._step_stream = None
 
     def _buffers(self, predict: bool):
         """The output buffers of a step; x_pred / u_pred ([B, N+1, 12] + [B, N, 6], N the longest horizon) only from the first step
@@ -107,7 +120,69 @@ class BatchController:
             raise ValueError(f"xhat must live on cuda:{self.device}, got {xhat.device}")
         return xhat.contiguous()
 
-    def step(self, xhat, predict: bool = False) -> Dict:
+    def default_reference(self):
+        """Each configuration's packed task reference g_ref = [0, 1, 0, px_ref, vy_ref] on every stage: a [B, N, 5] float64
+        tensor on the controller's device (a new one per call), the natural start for a reference schedule."""
+        import torch
+
+        g = np.zeros((self.batch, NREF))
+        g[:, 1] = 1.0
+        g[:, 3] = [c["px_ref"] for c in self.configs]
+        g[:, 4] = [c["vy_ref"] for c in self.configs]
+        return torch.from_numpy(np.repeat(g[:, None, :], self.N, axis=1)).to(torch.device("cuda", self.device))
+
+    def _check_reference(self, yref):
+        """Validates a reference ([B, N, 5] or [B, 5], float64, a numpy array or a tensor on the controller's device) without
+        touching the device; returns it as a [B, N, 5] or [B, 1, 5] array / tensor."""
+        import torch
+
+        B, N = self.batch, self.N
+        if isinstance(yref, np.ndarray):
+            arr, shape, dtype_ok = yref, tuple(yref.shape), yref.dtype == np.float64
+        elif isinstance(yref, torch.Tensor):
+            arr, shape, dtype_ok = yref, tuple(yref.shape), yref.dtype == torch.float64
+            if yref.device.type != "cuda" or yref.device.index != self.device:
+                raise ValueError(f"yref must live on cuda:{self.device}, got {yref.device}")
+        else:
+            raise ValueError(f"yref must be a torch tensor, a numpy array or None, got {type(yref).__name__}")
+        if shape not in ((B, N, NREF), (B, NREF)):
+            raise ValueError(f"yref must have shape ({B}, {N}, {NREF}) or ({B}, {NREF}), got {shape}")
+        if not dtype_ok:
+            raise ValueError(f"yref must be float64, got {yref.dtype}")
+        if isinstance(arr, np.ndarray):
+            # the rows a simulation's horizon reads must be finite (a ragged batch never reads rows k >= horizons[i])
+            rows = arr if len(shape) == 2 else arr[np.arange(N)[None, :] < self.horizons[:, None]]
+            if not np.isfinite(rows).all():
+                raise ValueError("yref has non-finite entries in rows a simulation's horizon reads")
+        return arr[:, None, :] if len(shape) == 2 else arr
+
+    def set_reference(self, yref):
+        """Sets the task reference the following steps track: ``yref[i, k]`` is the target of the task outputs g1..g5 of
+        simulation i at stage k = 0..N-1 (N the longest horizon; on a ragged batch rows k >= ``horizons[i]`` are not read), in
+        place of the packed ``[0, 1, 0, px_ref, vy_ref]``; a [B, 5] reference holds for the whole horizon.  The targets of the
+        input and joint-acceleration cost rows stay 0.  The reference is copied into the controller's own device buffer (later
+        edits of ``yref`` have no effect) and stays in force until it is set again -- ``reset()`` keeps it; ``None`` returns to
+        the packed references.  The next step linearises again first, since its carried linearisation was formed against the
+        old reference."""
+        import torch
+
+        if yref is None:
+            if self._ref_on:
+                self._ref_on, self._ref_changed = False, True
+            return
+        arr = self._check_reference(yref)
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(self.device)
+        if self._yref is None:
+            self._yref = torch.empty((self.batch, self.N, NREF), dtype=torch.float64, device=dev)
+        if self._step_stream is not None and self._step_stream != cur:
+            cur.wait_stream(self._step_stream)        # a step still reading the buffer on another stream finishes first
+        src = torch.from_numpy(np.ascontiguousarray(arr)).to(dev) if isinstance(arr, np.ndarray) else arr
+        self._yref.copy_(src.expand(self.batch, self.N, NREF))
+        self._ref_stream = cur
+        self._ref_on, self._ref_changed = True, True
+
+    def step(self, xhat, predict: bool = False, yref=None) -> Dict:
         """One MPC step of every controller from the feedback states ``xhat`` ([B, 12] q; qdot, float64: a tensor on the
         controller's device, or a numpy array that is copied there).
 
@@ -115,18 +190,33 @@ class BatchController:
         ``residuals`` [B, 4], ``cost``, ``solver_time`` [B]; with ``predict`` also the iterate's predicted trajectory
         ``x_pred`` [B, N+1, 12] and ``u_pred`` [B, N, 6] (N the longest horizon; rows past ``horizons[i]`` are NaN).  The launch is asynchronous on the current torch stream and nothing
         is synchronised.  The returned tensors are the controller's own buffers: the next ``step`` overwrites them, so clone
-        what must outlive it."""
+        what must outlive it.
+
+        ``yref`` (optional) is ``set_reference(yref)`` before the step: the reference then stays in force for later steps."""
         import torch
 
+        if yref is not None:
+            self._check_reference(yref)
         x = self._xhat(xhat)
         io = dict(self._buffers(predict), xhat=x)
+        if yref is not None:
+            self.set_reference(yref)
         stream = torch.cuda.current_stream(self.device)
-        self.engine.step(io, reset=self._reset, stream=stream.cuda_stream)
+        if self._ref_on or self._ref_changed:
+            if self._ref_on and self._ref_stream is not None and self._ref_stream != stream:
+                stream.wait_stream(self._ref_stream)      # the copy of the reference lands before the step reads it
+            self.engine.step_ref(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, reset=self._reset,
+                                 stream=stream.cuda_stream)
+        else:
+            self.engine.step(io, reset=self._reset, stream=stream.cuda_stream)
+        self._step_stream = stream
         self._reset = False
+        self._ref_changed = False
         return {k: v for k, v in io.items() if k != "xhat"}
 
     def reset(self):
-        """The next step starts from the initial guess (x_k = [q_0; qdot_0], u_k = 0, multipliers 0) again."""
+        """The next step starts from the initial guess (x_k = [q_0; qdot_0], u_k = 0, multipliers 0) again.  The task
+        reference in force stays."""
         self._reset = True
 
     def launch_info(self) -> Dict[str, int]:

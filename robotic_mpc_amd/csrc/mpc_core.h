@@ -462,9 +462,13 @@ struct Engine {
     // path's right-hand side for the NEW plant state (gt = g, Gamma = 0, rb = b + A dx_0: the same products the stationarity rows are
     // made of), so fast_rhs needs no pass of its own; with room for whole G2 records in LDS (stride L2W) it leaves with the
     // linearisation in one coalesced store, otherwise by 8-byte stores from the items.
+    // REF (the controller step's instantiation only): the task residuals are formed against the task reference `ref` (non-null,
+    // task_targets).
+    template <bool REF = false>
     MPC_PASS double nlp_direct(double alpha, bool do_update, bool sqp_mult, double *res4, bool do_plant = false, bool fuse_commit = false,
-                               bool want_rhs = false)
+                               bool want_rhs = false, TaskRef ref = TaskRef{nullptr})
     {
+        if constexpr (REF) ref = uni_ref(ref);
         PROF_T0(t0);
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
@@ -625,13 +629,25 @@ struct Engine {
                             rec[O_BD + j] = (xx[j] + P.a12[j] * vj + P.b1[j] * uj) - xn[j];
                             rec[O_BD + 6 + j] = (P.a22[j] * vj + P.b2[j] * uj) - xn[6 + j];
                         }
-                        task_lin<true>(rb, P, xx, xx + 6, rec);
+                        task_lin<true, double *, REF>(rb, P, xx, xx + 6, rec, rec);
                         double s_ = 0.0;
+                        if constexpr (REF) {
+                            double t[NTASK];    // (loaded here, past the kinematics: the linearisation is register-bound)
+                            task_targets(ref, k, t);
+#pragma unroll
+                            for (int i = 0; i < NTASK; i++) {
+                                const double r = rec[O_R + i] - t[i];
+                                rec[O_R + i] = r;
+                                s_ += P.w_task[i] * r * r;
+                                rec[O_Y + i] = P.w_task[i] * r;
+                            }
+                        } else {
 #pragma unroll
                         for (int i = 0; i < NTASK; i++) {
                             const double r = rec[O_R + i];
                             s_ += P.w_task[i] * r * r;
                             rec[O_Y + i] = P.w_task[i] * r;
+                        }
                         }
 #pragma unroll
                         for (int j = 0; j < 6; j++) s_ += cu[j];
@@ -2798,8 +2814,10 @@ struct Engine {
         return lpg;
     }
     MPC_HD int merit_groups() const { return imin(MERIT_MAX, imax(1, NT / merit_lanes())); }
-    MPC_PASS void merit_pass(const double *alphas, int na, bool update_weights, int sqp_iter, double *out)
+    template <bool REF = false>
+    MPC_PASS void merit_pass(const double *alphas, int na, bool update_weights, int sqp_iter, double *out, TaskRef ref = TaskRef{nullptr})
     {
+        if constexpr (REF) ref = uni_ref(ref);
         PROF_T0(t0);
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
@@ -2857,10 +2875,20 @@ struct Engine {
                     if (k < Nl) {
 #pragma unroll
                         for (int i = 0; i < 6; i++) uu[i] = r1[O_U + i] + alpha * r1[O_QW + i];
-                        task_lin<false>(rb, P, xx, xx + 6, rec);
+                        task_lin<false, double *, REF>(rb, P, xx, xx + 6, rec, rec);
                         double s = 0.0;
+                        if constexpr (REF) {
+                            double t[NTASK];
+                            task_targets(ref, k, t);
+#pragma unroll
+                            for (int i = 0; i < NTASK; i++) {
+                                const double r = rec[O_R + i] - t[i];
+                                s += P.w_task[i] * r * r;
+                            }
+                        } else {
 #pragma unroll
                         for (int i = 0; i < NTASK; i++) s += P.w_task[i] * rec[O_R + i] * rec[O_R + i];
+                        }
 #pragma unroll
                         for (int j = 0; j < 6; j++) {
                             const double qdd = P.cq[j] * (uu[j] - xx[6 + j]);
@@ -2947,6 +2975,29 @@ struct Engine {
         }
         return alpha;
     }
+    // ... and the controller step's, against the task reference `ref`
+    MPC_HD double line_search(int sqp_iter, TaskRef ref)
+    {
+        update_x0_weights(sqp_iter);
+        const int G = merit_groups();
+        // the backtracking sequence is fixed (1, 0.7, 0.49, ...): G trial points per pass, the reference point 0 in the first
+        double al[MERIT_MAX], m[MERIT_MAX], m0 = 0.0, alpha = 1.0;
+        bool first = true;
+        while (alpha >= 0.05) {
+            int na = 0;
+            if (first) al[na++] = 0.0;
+            double a = alpha;
+            while (na < G && a >= 0.05) { al[na++] = a; a *= 0.7; }
+            merit_pass<true>(al, na, first, sqp_iter, m, ref);
+            int j = 0;
+            if (first) { m0 = m[0]; j = 1; first = false; }
+            for (; j < na; j++) {
+                if (ex.uni(m[j] < m0)) return al[j];
+                alpha = al[j] * 0.7;
+            }
+        }
+        return alpha;
+    }
 
     // One solver.solve() call (simulator.py:210-221).  On entry sm.xhat holds the feedback
     // state and G2 holds the linearisation at the current iterate when `lin_valid`; on exit it
@@ -2954,16 +3005,29 @@ struct Engine {
     // `plant_done` (out): the plant step and the log of the new state were done inside the last NLP pass (SQP_RTI)
     // PLANT = false (control_step: the caller owns the plant): the last NLP pass of SQP_RTI runs no plant lane and forms no fast-path
     // right-hand side -- there is no next state to form it for; the next step's QP forms it itself (ipm_solve, !rhs_valid).
+    // The controller step's passes (PLANT = false) also form the task residuals against the caller's task reference `ref` (REF
+    // instantiations of nlp_direct / merit_pass); the rollout's keep the packed g_ref.
     template <bool PLANT = true>
-    MPC_HD int nlp_step(bool &lin_valid, int *sqp_iter_out, int *qp_iter_out, double *res4, double *cost_out, bool *plant_done)
+    MPC_HD int nlp_step(bool &lin_valid, int *sqp_iter_out, int *qp_iter_out, double *res4, double *cost_out, bool *plant_done,
+                        TaskRef ref = TaskRef{nullptr})
     {
+        constexpr bool REF = !PLANT;
+        // (without a reference the controller step runs the passes of the packed g_ref: the step of mpcb_step as it was)
+        const auto ctl_pass = [&](double alpha, bool do_update, bool sqp_mult, double *r4, bool fuse_commit) {
+            if (ex.uni(ref.y != nullptr)) return nlp_direct<true>(alpha, do_update, sqp_mult, r4, false, fuse_commit, false, ref);
+            return NLP_PASS(alpha, do_update, sqp_mult, r4, false, fuse_commit, false);
+        };
         *plant_done = false;
         PROF_T0(t0);
         int status = 0, sqp_iter = 0, qp_iter = 0, it = 0;
         double cost = lin_cost;
         if (c.pb->solver_type == 1) {
             // SQP_RTI: one linearisation, one QP, full step
-            if (!lin_valid) { cost = NLP_PASS(0.0, false, false, nullptr); rhs_valid = false; }
+            if (!lin_valid) {
+                if constexpr (REF) cost = ctl_pass(0.0, false, false, nullptr, false);
+                else cost = NLP_PASS(0.0, false, false, nullptr);
+                rhs_valid = false;
+            }
             commit_pending = false;
             const int qs = ipm_solve(&it, MPCB_FUSE != 0);
             qp_iter += it;
@@ -2979,7 +3043,7 @@ struct Engine {
                 rhs_valid = next_fast;
                 *plant_done = true;
             } else {
-                cost = NLP_PASS(1.0, ok, false, res4, false, commit_pending, false);
+                cost = ctl_pass(1.0, ok, false, res4, commit_pending);
                 rhs_valid = false;
             }
             commit_pending = false;
@@ -2991,7 +3055,8 @@ struct Engine {
             bool pending = false;  // a step (alpha) waits to be applied by the next nlp_pass
             for (sqp_iter = 0; sqp_iter < c.pb->max_iter; sqp_iter++) {
                 if (pending || !lin_valid || sqp_iter == 0) {
-                    cost = NLP_PASS(alpha, pending, true, res4);
+                    if constexpr (REF) cost = ctl_pass(alpha, pending, true, res4, false);
+                    else cost = NLP_PASS(alpha, pending, true, res4);
                     pending = false;
                     lin_valid = true;
                 }
@@ -3000,10 +3065,15 @@ struct Engine {
                 const int qs = ipm_solve(&it);
                 qp_iter += it;
                 if (qs != 0 && qs != 1) { status = 4; break; }
-                alpha = c.pb->fixed_step ? 1.0 : line_search(sqp_iter);
+                if constexpr (REF) alpha = c.pb->fixed_step ? 1.0 : ex.uni(ref.y != nullptr) ? line_search(sqp_iter, ref) : line_search(sqp_iter);
+                else alpha = c.pb->fixed_step ? 1.0 : line_search(sqp_iter);
                 pending = true;
             }
-            if (pending) { cost = NLP_PASS(alpha, true, true, nullptr); lin_valid = true; }  // max-iter exit: residuals of the last check stay
+            if (pending) {   // max-iter exit: residuals of the last check stay
+                if constexpr (REF) cost = ctl_pass(alpha, true, true, nullptr, false);
+                else cost = NLP_PASS(alpha, true, true, nullptr);
+                lin_valid = true;
+            }
         }
         lin_cost = cost;
         *sqp_iter_out = sqp_iter;
@@ -3138,6 +3208,9 @@ struct Engine {
         bool lin_valid = false;
         if (reset) initial_guess();
         else load_carry(lin_valid);
+        // a new task reference: the carried linearisation was formed against the old one -- linearise again (everything else carries)
+        if (io.ref_changed) lin_valid = false;
+        const TaskRef ref{io.yref ? io.yref + (size_t)inst * N * NTASK : nullptr};
         ex.par([&](int lane) {
             if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
         });
@@ -3145,7 +3218,7 @@ struct Engine {
         double res4[4] = {0, 0, 0, 0}, cost = 0.0;
         const double t0 = ex.clock();
         bool plant_done = false;
-        const int status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done);
+        const int status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, ref);
         const double t1 = ex.clock();
         ex.par([&](int lane) {
             if (lane < NU) io.u0[(size_t)inst * NU + lane] = w.G1[O_U + lane];   // solver.get(0,'u')

@@ -25,7 +25,8 @@ using namespace mpcb;
 
 static_assert(sizeof(mpcb_problem) == sizeof(Problem), "ABI struct mismatch");
 static_assert(sizeof(mpcb_result) == sizeof(Outputs), "ABI struct mismatch");
-static_assert(sizeof(mpcb_step_io) == sizeof(StepIO), "ABI struct mismatch");
+static_assert(offsetof(StepIO, yref) == sizeof(mpcb_step_io), "ABI struct mismatch: StepIO is mpcb_step_io + the task reference");
+static_assert(MPCB_NREF == NTASK, "task reference width");
 static_assert(sizeof(Robot) == MPCB_NROBOT * sizeof(double), "robot layout");
 
 // The controller step kernels live in their own translation unit, mpc_step.hip: instantiated here, next to the rollout kernels,
@@ -599,6 +600,11 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
 
 int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream)
 {
+    return mpcb_step_ref(h, io, nullptr, 0, reset, stream);
+}
+
+int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, int reset, void *stream)
+{
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
     if (!h->controller) return fail(h, MPCB_ESTATE, "mpcb_step needs a handle set up by mpcb_setup_controller");
@@ -608,7 +614,9 @@ int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream)
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     StepIO sio;
-    std::memcpy(&sio, io, sizeof sio);
+    std::memcpy(&sio, io, sizeof(mpcb_step_io));
+    sio.yref = yref;
+    sio.ref_changed = ref_changed != 0 ? 1 : 0;
     const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
     if (h->engine == MPCB_ENGINE_STREAM) {
         // throughput engine: one wavefront per simulation, static LDS only, no work queue

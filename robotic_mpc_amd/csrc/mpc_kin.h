@@ -119,7 +119,9 @@ MPC_HD void kin_eval(const Robot &rb, const double *q, Kin &k)
 // Jacobian goes straight to memory).
 // (PG: the Jacobian's destination keeps its address space -- a `double *` parameter would turn the throughput engine's stores to its HBM
 // record into flat_store, which occupy the LDS queue as well)
-template <bool JAC, class PG>
+// RAW (the controller step's passes): rec_r[O_R..] receives g itself (minus 0.0: the same value); the caller subtracts the targets of
+// task_targets where it uses the residuals, after the kinematics have released their registers.
+template <bool JAC, class PG, bool RAW = false>
 MPC_HD void task_lin(const Robot &rb, const InstParams &P, const double *q, const double *qd, double *rec_r, PG rec_g)
 {
     Kin k;
@@ -144,10 +146,10 @@ MPC_HD void task_lin(const Robot &rb, const InstParams &P, const double *q, cons
     }
     const V3 s = vl + cross(om, tw);
     rec_r[O_R + 0] = (S - pt.z) - 0.0;
-    rec_r[O_R + 1] = dot(n, zh) - 1.0;
+    rec_r[O_R + 1] = dot(n, zh) - (RAW ? 0.0 : 1.0);
     rec_r[O_R + 2] = yh.x - 0.0;
-    rec_r[O_R + 3] = pt.x - P.px_ref;
-    rec_r[O_R + 4] = dot(yh, s) - P.vy_ref;  // v_task,y = (R^T (v + w x t_w))_y, prediction_model.py:313
+    rec_r[O_R + 3] = pt.x - (RAW ? 0.0 : P.px_ref);
+    rec_r[O_R + 4] = dot(yh, s) - (RAW ? 0.0 : P.vy_ref);  // v_task,y = (R^T (v + w x t_w))_y, prediction_model.py:313
     if (!JAC) return;
     const V3 mX = v3(2 * a, c, 0), mY = v3(c, 2 * b, 0);
     const double pX = dot(n, mX), pY = dot(n, mY);
@@ -186,6 +188,27 @@ template <bool JAC>
 MPC_HD void task_lin(const Robot &rb, const InstParams &P, const double *q, const double *qd, double *rec)
 {
     task_lin<JAC>(rb, P, q, qd, rec, rec);
+}
+
+// Stage k's targets of the task outputs g1..g5: row k of the task reference `ref` (non-null: without a reference the controller step
+// runs the passes of the packed g_ref).  r = g - target is then one subtraction, as task_lin forms g - g_ref.
+MPC_HD void task_targets(TaskRef ref, int k, double *t)
+{
+    const double *y = ref.y + (size_t)k * NTASK;
+#pragma unroll
+    for (int i = 0; i < NTASK; i++) t[i] = y[i];
+}
+
+// The reference pointer is the same in every lane: kept in scalar registers, not in a vector register pair for the whole pass
+MPC_HD TaskRef uni_ref(TaskRef ref)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long v = (unsigned long long)ref.y;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return TaskRef{(const double *)(((unsigned long long)hi << 32) | lo)};
+#else
+    return ref;
+#endif
 }
 
 // Plant log (simulation_model.py:60-77): pose = [p; R row-major], rpy, J_world * qdot.

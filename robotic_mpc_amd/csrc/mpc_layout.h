@@ -136,8 +136,9 @@ struct Outputs {
     double *plant_time; // [batch][Nsim] seconds: plant step + FK / J qdot / error logging (simulator.py:224-226)
 };
 
-// Device pointers of one controller step (== mpcb_step_io): the caller's feedback states in, solver.get(0,'u') and the
-// step's statistics out, batch-major.  x_pred / u_pred may be null (not written).
+// Device pointers of one controller step (mpcb_step_io, then the task reference of mpcb_step_ref): the caller's feedback states in,
+// solver.get(0,'u') and the step's statistics out, batch-major.  x_pred / u_pred may be null (not written).  The members past
+// u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged".
 struct StepIO {
     const double *xhat;  // [batch][12]
     double *u0;          // [batch][6]
@@ -149,6 +150,15 @@ struct StepIO {
     double *solver_time; // [batch] seconds (device realtime counter)
     double *x_pred;      // [batch][N+1][12] or null
     double *u_pred;      // [batch][N][6] or null
+    const double *yref = nullptr;   // [batch][N][NTASK] targets of g1..g5 at stages 0..N-1, or null: each instance's packed g_ref
+    int ref_changed = 0;            // != 0: the reference differs from the previous step's (the carried linearisation is stale)
+};
+
+// The task reference of one instance in a controller step: its [N][NTASK] rows of StepIO::yref, or null for the packed
+// g_ref = [0, 1, 0, px_ref, vy_ref].  Also the tag that selects the reference-tracking variant of a pass (an overload taking
+// it first), which only the controller step kernels instantiate: the rollout kernels keep their passes as they are.
+struct TaskRef {
+    const double *y;
 };
 
 // One instance's workspace: five stage-major group arrays + persistent scalars.

@@ -1896,8 +1896,11 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
 // ocp_nlp_update_variables_sqp): N* += alpha (Q* - N*) on [pi | lam | t] (60 entries of G5).
 // `slot` (SQP_RTI: 0 / 1, full SQP: -1): where the QP iterate -- the step to apply -- sits (rti_items); in SQP_RTI stage 0's x part of it,
 // x_hat - x_0 (lbx_0 = ubx_0: the sweeps' dx_0 is 0), is formed AND written here, the only pass that has the x_0 it refers to.
-SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int slot = -1)
+// REF (the controller step's instantiation only): the task residuals are formed against the task reference `ref` (non-null, task_targets).
+template <bool REF = false>
+SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int slot = -1, TaskRef ref = TaskRef{nullptr})
 {
+    if constexpr (REF) ref = uni_ref(ref);
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
     const Robot &rb = robot_in_lds();
@@ -1971,7 +1974,13 @@ SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int s
 #endif
         if (k < N) {
             double rl[10];                                             // r | Y; the Jacobian goes straight to the record
-            task_lin<true>(rb, P, xx, xx + 6, rl, r2);
+            task_lin<true, decltype(r2), REF>(rb, P, xx, xx + 6, rl, r2);
+            if constexpr (REF) {
+                double t[NTASK];    // (loaded here, past the kinematics)
+                task_targets(ref, k, t);
+#pragma unroll
+                for (int i = 0; i < NTASK; i++) rl[O_R + i] -= t[i];
+            }
 #pragma unroll
             for (int i = 0; i < NTASK; i++) rl[O_Y + i] = P.w_task[i] * rl[O_R + i];
 #pragma unroll
@@ -2111,8 +2120,10 @@ SE_PASS double nlp_res_pass(double *res4)
 // L1 merit function at the trial point (X,U) + alpha (dX,dU) (acados ocp_nlp_evaluate_merit_fun restated;
 // mpc_core.h merit_pass).  lane <-> stage, straight from HBM.  With `update_weights` the merit weights (G5 MW) are
 // first refreshed from the QP multipliers by Leineweber's rule.
-SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter)
+template <bool REF = false>
+SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskRef ref = TaskRef{nullptr})
 {
+    if constexpr (REF) ref = uni_ref(ref);
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
     const Robot &rb = robot_in_lds();
@@ -2157,7 +2168,13 @@ SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter)
         if (k < N) {
 #pragma unroll
             for (int i = 0; i < 6; i++) uu[i] = r1[O_U + i] + alpha * r1[O_QW + i];
-            task_lin<false>(rb, P, xx, xx + 6, rec);
+            task_lin<false, double *, REF>(rb, P, xx, xx + 6, rec, rec);
+            if constexpr (REF) {
+                double t[NTASK];
+                task_targets(ref, k, t);
+#pragma unroll
+                for (int i = 0; i < NTASK; i++) rec[O_R + i] -= t[i];
+            }
             double s = 0.0;
 #pragma unroll
             for (int i = 0; i < NTASK; i++) s += P.w_task[i] * rec[O_R + i] * rec[O_R + i];
@@ -2214,16 +2231,21 @@ SE_PASS void update_x0_weights(int sqp_iter)
     fence();
 }
 
-// MERIT_BACKTRACKING (trajectory_optimizer.py:68; acados alpha_reduction 0.7, alpha_min 0.05)
-SE_DEV double line_search(int sqp_iter)
+// MERIT_BACKTRACKING (trajectory_optimizer.py:68; acados alpha_reduction 0.7, alpha_min 0.05).  REF: against the task reference `ref`.
+template <bool REF = false>
+SE_DEV double line_search(int sqp_iter, TaskRef ref = TaskRef{nullptr})
 {
     update_x0_weights(sqp_iter);
-    const double m0 = unid(merit_pass(0.0, true, sqp_iter));
+    const auto merit = [&](double a, bool upd) {
+        if constexpr (REF) return merit_pass<true>(a, upd, sqp_iter, ref);
+        else return merit_pass(a, upd, sqp_iter);
+    };
+    const double m0 = unid(merit(0.0, true));
     __builtin_amdgcn_s_waitcnt(0);
     fence();
     double alpha = 1.0;
     while (alpha >= 0.05) {
-        if (uni(unid(merit_pass(alpha, false, sqp_iter)) < m0 ? 1 : 0)) break;
+        if (uni(unid(merit(alpha, false)) < m0 ? 1 : 0)) break;
         alpha *= 0.7;
     }
     return alpha;
@@ -2548,6 +2570,15 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
         lin_valid = uni(w.state[25] != 0.0 ? 1 : 0) != 0;
         fast[0] = uni((int)w.state[26]); fast[1] = uni((int)w.state[27]); cur = uni((int)w.state[28]);
     }
+    // a new task reference: the carried linearisation was formed against the old one -- linearise again (everything else carries).
+    // The reference rows are strided by the batch's longest horizon; rows past this simulation's own are never read.
+    if (io.ref_changed) lin_valid = false;
+    const TaskRef ref{io.yref ? io.yref + (size_t)inst * NMAX * NTASK : nullptr};
+    // (without a reference the passes of the packed g_ref: the step of mpcb_step as it was)
+    const auto lin = [&](double alpha, bool do_update, bool sqp_mult, int slot) {
+        if (ref.y) lin_pass<true>(alpha, do_update, sqp_mult, slot, ref);
+        else lin_pass(alpha, do_update, sqp_mult, slot);
+    };
     if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
     fence();
     int qp_iter = 0, status = 0, sqp_iter = 1;
@@ -2557,10 +2588,10 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
     if (pb.solver_type == 1) {
         // SQP_RTI: one linearisation, one QP, full step -- rollout<FT>'s step with res_pending false on entry and on exit
 #ifdef MPCB_STREAM_SEQ_RES
-        if (!lin_valid) { lin_pass(0.0, false); __builtin_amdgcn_s_waitcnt(0); fence(); lin_cost = unid(nlp_res_pass<false>(nullptr)); }
+        if (!lin_valid) { lin(0.0, false, false, -1); __builtin_amdgcn_s_waitcnt(0); fence(); lin_cost = unid(nlp_res_pass<false>(nullptr)); }
 #else
         if (!lin_valid) {
-            lin_pass(0.0, false); __builtin_amdgcn_s_waitcnt(0); fence();
+            lin(0.0, false, false, -1); __builtin_amdgcn_s_waitcnt(0); fence();
             double o5[5];
             rti_items<true, false>(0, o5, cur);
             lin_cost = unid(o5[0]);
@@ -2571,9 +2602,9 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
         if (!ok) status = 4;                                           // ACADOS_QP_FAILURE, iterate untouched
         __builtin_amdgcn_s_waitcnt(0);
 #ifdef MPCB_STREAM_SEQ_RES
-        lin_pass(1.0, ok);
+        lin(1.0, ok, false, -1);
 #else
-        lin_pass(1.0, ok, false, cur);
+        lin(1.0, ok, false, cur);
 #endif
         __builtin_amdgcn_s_waitcnt(0);                                 // the records written lane by lane are complete before they are streamed
         fence();
@@ -2594,7 +2625,7 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
         for (sqp_iter = 0; sqp_iter < pb.max_iter; sqp_iter++) {
             if (pending || !lin_valid || sqp_iter == 0) {
                 __builtin_amdgcn_s_waitcnt(0);
-                lin_pass(alpha, pending, true);
+                lin(alpha, pending, true, -1);
                 __builtin_amdgcn_s_waitcnt(0);
                 fence();
 #ifdef MPCB_STREAM_SEQ_RES
@@ -2616,12 +2647,12 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
             if (qs != 0 && qs != 1) { status = 4; break; }
             __builtin_amdgcn_s_waitcnt(0);
             fence();
-            alpha = pb.fixed_step ? 1.0 : line_search(sqp_iter);
+            alpha = pb.fixed_step ? 1.0 : (ref.y ? line_search<true>(sqp_iter, ref) : line_search(sqp_iter));
             pending = true;
         }
         if (pending) {   // max-iter exit: apply the last step; the residuals of the last check stay
             __builtin_amdgcn_s_waitcnt(0);
-            lin_pass(alpha, true, true);
+            lin(alpha, true, true, -1);
             __builtin_amdgcn_s_waitcnt(0);
             fence();
 #ifdef MPCB_STREAM_SEQ_RES

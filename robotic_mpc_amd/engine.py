@@ -77,7 +77,8 @@ class EngineError(RuntimeError):
 _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", "mpcb_last_error",
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
-            "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for")
+            "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
+            "mpcb_step_ref")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -122,6 +123,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_step.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), C.c_int, C.c_void_p]
     lib.mpcb_setup_controller_on.argtypes = [C.c_void_p, C.POINTER(MpcbProblem), _dp, _dp, C.c_int]
     lib.mpcb_controller_engine_for.argtypes = [C.POINTER(MpcbProblem), C.c_int]
+    lib.mpcb_step_ref.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, C.c_int, C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -297,6 +299,19 @@ class MpcBatchEngine:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         r = self._step_struct(io)
         self._check(self.lib.mpcb_step(self._h, C.byref(r), int(bool(reset)), C.c_void_p(stream)), "mpcb_step")
+
+    def step_ref(self, io, yref=None, ref_changed: bool = False, reset: bool = False, stream: Optional[int] = None):
+        """mpcb_step_ref: step() against the task reference `yref`, a contiguous float64 device tensor [batch, N, 5] (N the longest
+        horizon) of the targets of g1..g5 per stage, or None for the packed references.  `ref_changed`: the reference differs from
+        the previous step's (the step linearises again first)."""
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._step_struct(io)
+        yp = C.cast(C.c_void_p(yref.data_ptr()), _dp) if yref is not None else None
+        self._check(self.lib.mpcb_step_ref(self._h, C.byref(r), yp, int(bool(ref_changed)), int(bool(reset)), C.c_void_p(stream)),
+                    "mpcb_step_ref")
 
     def debug_task_lin(self, cfgs: Sequence[Dict], chain, x: np.ndarray) -> np.ndarray:
         """Diagnostic: the device linearisation at points x[i] = [q; qdot] with the parameters of cfgs[i];

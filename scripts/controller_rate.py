@@ -9,10 +9,11 @@ per (batch, engine) pair.
 
 `--engine` takes one or more kernel families (BatchController's engine=, "latency" by default) and `--batch` one or more batch
 sizes: every batch runs on each engine in turn, alternating, in one process.  The rollout is timed on the same family
-(MPCB_ENGINE) unless --skip-rollout.
+(MPCB_ENGINE) unless --skip-rollout.  `--ref` takes one or more task-reference modes: none (the packed reference), once (a
+per-stage tracking reference set before the loop) and every (a new one every step: the copy and one more linearisation per step).
 
     python scripts/controller_rate.py [--batch 256 ...] [--engine latency|stream ...] [--N 100] [--steps 600] [--solver SQP_RTI]
-                                      [--skip-rollout]
+                                      [--skip-rollout] [--ref none|once|every ...]
 """
 import argparse
 import json
@@ -59,13 +60,16 @@ def main():
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--solver", choices=("SQP_RTI", "SQP"), default="SQP_RTI")
     ap.add_argument("--skip-rollout", action="store_true")
+    # task reference: none (the packed one), set once before the loop, or a new one every step (one more linearisation per step)
+    ap.add_argument("--ref", nargs="+", choices=("none", "once", "every"), default=["none"])
     args = ap.parse_args()
     for B in args.batch:
         for eng in args.engine:
-            measure(args, B, eng)
+            for ref in args.ref:
+                measure(args, B, eng, ref)
 
 
-def measure(args, B, eng):
+def measure(args, B, eng, ref="none"):
     import numpy as np
     import torch
 
@@ -82,14 +86,24 @@ def measure(args, B, eng):
     plant = rk4_plant(wcv, cfgs[0]["dt"])
     x0 = torch.tensor(np.stack([np.concatenate([c["q0"], c["qdot0"]]) for c in cfgs]), dtype=torch.float64, device=dev)
 
+    # a tracking schedule: a px_ref ramp along the horizon that moves 0.2 mm per step, and a vy_ref profile
+    base = ctl.default_reference()
+    ramp = torch.arange(ctl.N, dtype=torch.float64, device=dev)
+    sched = [base.clone() for _ in range(2)]
+    for j, y in enumerate(sched):
+        y[:, :, 3] += 0.002 * ramp - 0.01 + 0.0002 * j
+        y[:, :, 4] += 0.01 * torch.sin(0.3 * ramp + j)
+    if ref == "once":
+        ctl.set_reference(sched[0])
+
     def closed_loop(events=None):
         ctl.reset()
         x = x0
-        for _ in range(S):
+        for k in range(S):
             if events is not None:
                 events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
                 events[-1][0].record()
-            u = ctl.step(x)["u0"]
+            u = ctl.step(x, yref=sched[k % 2] if ref == "every" else None)["u0"]
             if events is not None:
                 events[-1][1].record()
             x = plant(x, u)
@@ -107,7 +121,7 @@ def measure(args, B, eng):
     closed_loop(ev)
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
-    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, step_loop_ms=round(loop_ms, 3),
+    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, step_loop_ms=round(loop_ms, 3),
                step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
                step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
                launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
