@@ -607,7 +607,7 @@ struct Engine {
             ex.par([&](int lane) {
                 double csum = 0.0;
                 for (int k = k0 + lane; k <= k1; k += NT) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MPCB_NO_LICM_BLOCK)
+#if defined(__HIP_DEVICE_COMPILE__)
                     asm volatile("" ::: "memory");     // (parameters are read where they are used, not hoisted out of the loop and spilled: see merit_pass)
 #endif
                     double *rec = v2 + (size_t)(k - k0) * LS;
@@ -2861,7 +2861,7 @@ struct Engine {
                 double acc = 0.0;
                 if (g < na) {
                 for (int k = k0 + lane; k <= k1; k += LPG) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MPCB_NO_LICM_BLOCK)
+#if defined(__HIP_DEVICE_COMPILE__)
                     // (the parameter block is read from LDS where it is used: hoisted out of this loop -- ~60 values -- it is spilled to
                     // scratch memory as a whole by the 256-register builds)
                     asm volatile("" ::: "memory");

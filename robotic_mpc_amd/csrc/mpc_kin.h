@@ -73,11 +73,7 @@ MPC_HD void sincos_joint(double th, double *sn, double *cs)
 MPC_HD M3 axis_rot(V3 a, double th)
 {
     double s, c;
-#ifdef MPCB_LIBM_SINCOS      // (A/B builds)
-    sincos(th, &s, &c);
-#else
     sincos_joint(th, &s, &c);
-#endif
     const double v = 1.0 - c;
     M3 R;
     R.r0 = v3(c + v * a.x * a.x, v * a.x * a.y - s * a.z, v * a.x * a.z + s * a.y);

@@ -76,12 +76,16 @@ constexpr int W5 = 116;
 constexpr int O_NPI = 0, O_NLAM = 12, O_NT = 36, O_TX = 60, O_TU = 72, O_MW = 78;  // MW: dyn 12 + ineq 24
 
 constexpr int STAGE_DOUBLES = W1 + W2 + W3 + W4 + W5;
-// [0..11] plant state z, [12] cost of the held linearisation, [13..24] merit weights of the x0
-// constraint, [25] linearisation-valid flag, [26] fast path: QPs left before the next attempt, [27] length of the
-// current suspension, [28] throughput engine, SQP_RTI: the slot of the stage records that holds the QP iterate (0: G1, 1: G3),
-// [32..47] profile counters (diagnostic build)
-constexpr int STATE_DOUBLES = 64;
+// The scalars at the end of a simulation's workspace, carried from one launch to the next (`state`): slots
+constexpr int ST_Z = 0;            // [12] plant state z
+constexpr int ST_LIN_COST = 12;    // cost of the held linearisation
+constexpr int ST_X0_MW = 13;       // [12] merit weights of the x0 constraint
+constexpr int ST_LIN_VALID = 25;   // linearisation-valid flag
+constexpr int ST_FAST = 26;        // [2] fast path: QPs left before the next attempt, length of the current suspension
+constexpr int ST_CUR = 28;         // throughput engine, SQP_RTI: the slot of the stage records that holds the QP iterate (0: G1, 1: G3)
+constexpr int ST_PROF = 32;        // [NPROF] profile counters (diagnostic build)
 constexpr int NPROF = 16;
+constexpr int STATE_DOUBLES = 64;
 
 // Kinematic constants (robots.py KinematicChain.packed): 105 doubles
 struct Robot {

@@ -381,40 +381,28 @@ struct IpmNorms {
 // multiplier step stored with stage k+1; pi_{k-1} travels in LDS from the previous iteration.
 //   in  : G1 row | G3 [DW..DT] | G2 [R..GV]            (234 doubles)
 //   out : G1 [QW..QT] | G2 [R,Y] | G2 [GAM|GT|RB] | G3 [RG|RD|RM]   (196 doubles)
-// MODE 2 = MODE 0 fused with nlp_res_pass<false> of the step BEFORE (SQP_RTI): the first pass of a step streams every
-// record the NLP residual pass needs, so the dynamics defect BD (an input of this very pass), the cost and acados'
-// residual norms of the previous step's iterate are formed here -- from the rows as they arrive, i.e. before the
-// warm-start clamp touches lam, t -- and the separate sweep disappears.  nlp_out = [cost, stat, eq, ineq, comp];
-// sm.vec[3] holds the x_hat the previous QP was solved for.  The output bundle then carries G2 [R..BD] (210 doubles).
-// MODE 3 / 4 = right-hand side of the bound-inactive FAST PATH (mpc_ipm.h; mpc_core.h fast_rhs), plain / fused like MODE 2: the same
-// sweep evaluated at (dw, pi, lam) = 0 with x_0 embedded and no bound terms -- Gamma = 0, gt = g, rb = b (+ A dx0 at stage 0) -- and
-// WITHOUT the warm-start clamp: the previous QP's (w, pi, lam, t) in G1 stay as they are (only the x_0 embedding, which MODE 0 would
-// write identically, and y go out), so a rejected attempt is followed by residual_pass<0> as if nothing had happened.
 template <int MODE>
-SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
+SE_PASS IpmNorms residual_pass(double a)
 {
-    constexpr bool FUSE = MODE == 2 || MODE == 4;
-    constexpr bool FASTM = MODE >= 3;
+    static_assert(MODE == 0 || MODE == 1, "warm start or Newton step");
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
     const int lane = threadIdx.x;
     const int N = uni(sm.n_hor);
     const SWs w = sm.w;
-    // FAST modes stream less (round 4): no Newton step comes in (dw = 0: G1 row | lin, 156 doubles) and neither the QP iterate
-    // (untouched) nor the residual records rg | rd | rm (nobody reads them on the fast path) go out: [R, Y(, BD)] | [GAM | GT | RB].
-    constexpr int I_D = 96, I_L = FASTM ? 96 : 174;          // input image: G1 row | D | lin   (FAST: G1 row | lin)
-    constexpr int IN_ITEMS = FASTM ? 78 : 117;
-    constexpr int RYW = FUSE ? O_BD + 12 : 10;               // G2 columns written from 0: [R, Y] or [R, Y, pad, BD]
-    constexpr int O_W = 0, O_RY = FASTM ? 0 : 78, O_G = O_RY + RYW, O_3 = O_G + 42;   // output image
-    constexpr int OUT_ITEMS = FASTM ? (RYW + 42) / 2 : (78 + RYW + 42 + 66) / 2;
+    constexpr int I_D = 96, I_L = 174;                       // input image: G1 row | D | lin
+    constexpr int IN_ITEMS = 117;
+    constexpr int RYW = 10;                                  // G2 columns written from 0: [R, Y]
+    constexpr int O_W = 0, O_RY = 78, O_G = O_RY + RYW, O_3 = O_G + 42;   // output image
+    constexpr int OUT_ITEMS = (78 + RYW + 42 + 66) / 2;
     constexpr int OUT_NI = (OUT_ITEMS + WAVE - 1) / WAVE;
     Bundle<2, IN_ITEMS> bin;
     Bundle<OUT_NI, OUT_ITEMS> bout;
     {
-        if (FASTM) { const Seg si[2] = {segd(w.G1, w.ld, 0, W1), segd(w.G2, w.ld, 0, W2_LIN)}; bin.setup(si, lane); }
-        else { const Seg si[3] = {segd(w.G1, w.ld, 0, W1), segd(w.G3, w.ld, O_DW, 78), segd(w.G2, w.ld, 0, W2_LIN)}; bin.setup(si, lane); }
-        if (FASTM) { const Seg so[2] = {segd(w.G2, w.ld, 0, RYW), segd(w.G2, w.ld, O_GAM, 42)}; bout.setup(so, lane); }
-        else { const Seg so[4] = {segd(w.G1, w.ld, O_QW, 78), segd(w.G2, w.ld, 0, RYW), segd(w.G2, w.ld, O_GAM, 42), segd(w.G3, w.ld, 0, 66)}; bout.setup(so, lane); }
+        const Seg si[3] = {segd(w.G1, w.ld, 0, W1), segd(w.G3, w.ld, O_DW, 78), segd(w.G2, w.ld, 0, W2_LIN)};
+        bin.setup(si, lane);
+        const Seg so[4] = {segd(w.G1, w.ld, O_QW, 78), segd(w.G2, w.ld, 0, RYW), segd(w.G2, w.ld, O_GAM, 42), segd(w.G3, w.ld, 0, 66)};
+        bout.setup(so, lane);
         bout.seek(0, 1);
     }
     double a_g = 0, a_b = 0, a_d = 0, a_m = 0, a_mu = 0, ncl = 0;
@@ -422,8 +410,8 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
     // block inside the stage loop also make the compiler drain the fetches in flight: same LDS object as the ring).
     const int lj = lane >= 18 && lane < 30 ? lane - 18 : 0;                 // lanes 18..29: bounded component (update) / row of rb
     const bool lj_lo = bnd_lo(P, lj) > -BOUND_INF, lj_hi = bnd_hi(P, lj) < BOUND_INF;
-    // lanes 0..17: stationarity row of the QP; MODE 2: lanes 30..47 hold the same rows for the NLP residual of the row ahead
-    const int ci = lane < NW ? lane : (FUSE && lane >= 30 && lane < 30 + NW ? lane - 30 : 0), cls = ci / 6, cj = ci - cls * 6;
+    // lanes 0..17: stationarity row of the QP
+    const int ci = lane < NW ? lane : 0, cls = ci / 6, cj = ci - cls * 6;
     const bool c_lo = cls < 2 && bnd_lo(P, ci < NB ? ci : 0) > -BOUND_INF, c_hi = cls < 2 && bnd_hi(P, ci < NB ? ci : 0) < BOUND_INF;
     const double cb_lo = bnd_lo(P, ci < NB ? ci : 0), cb_hi = bnd_hi(P, ci < NB ? ci : 0);
     const double k_dt = P.dt, k_2wu = 2.0 * P.w_u, k_c2 = P.w_qddot * P.cq[cj] * P.cq[cj], k_lm = P.lm;
@@ -431,67 +419,8 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
     const double k_wy = P.w_task[lane >= 48 && lane < 48 + NTASK ? lane - 48 : 0];
     const double k_ra = lj < 6 ? P.a12[lj] : P.a22[lj - 6], k_rb = lj < 6 ? P.b1[lj] : P.b2[lj - 6];
     const double xh = lane < NX ? sm.xhat[lane] : 0.0;
-    // MODE 2, lanes 0..11: dynamics row / cost share of the NLP residual (nlp_res_pass), x_hat of the previous QP
-    const int jd = lane < 12 ? lane % 6 : 0;
-    const double d_a = lane < 6 ? P.a12[jd] : P.a22[jd], d_b = lane < 6 ? P.b1[jd] : P.b2[jd], d_cq = P.cq[jd];
-    const double d_wt = P.w_task[lane >= 6 && lane < 6 + NTASK ? lane - 6 : 0], k_wq = P.w_qddot;
-    const double xprev = FUSE && lane < NX ? sm.vec[3][lane] : 0.0;
-    double csum = 0.0, n_s = 0, n_e = 0, n_i = 0, n_c = 0;
-    // NLP stationarity / bound violation / complementarity of stage kk from its landed row (multipliers as the QP left
-    // them) -- nlp_res_pass lanes 16..33, here lanes 30..47; ppi = pi_{kk-1}
     const int ix_v = ci < 6 ? O_U + ci : O_X + ci - 6;      // the bounded variable of stationarity row ci
     const int ix_h = ci >= 6 ? ci - 6 : 0;                    // its entry of pi_{k-1}
-    auto nlp_stat = [&](const double *row, const double *ppi, int kk) {
-        // operands first, by every lane (idle lanes: row offsets of ci = 0), then the rows on registers
-        const double *r1 = row, *r2 = row + I_L, *pk = row + O_QPI;
-        const int j = cj;
-        double uj = r1[O_U + j], vj = r1[O_X + 6 + j], pkq = pk[j], pkv = pk[6 + j], pp = ppi[ix_h];
-        double h0 = r2[O_GQ + j], h1 = r2[O_GQ + 6 + j], h2 = r2[O_GQ + 12 + j], h3 = r2[O_GQ + 18 + j], h4 = r2[O_GQ + 24 + j], hv = r2[O_GV + j];
-        double z0 = r2[O_Y], z1 = r2[O_Y + 1], z2 = r2[O_Y + 2], z3 = r2[O_Y + 3], z4 = r2[O_Y + 4];
-        double curv = r1[ix_v], la = row[O_QLAM + ci], ta = row[O_QT + ci], lb = row[O_QLAM + 12 + ci], tb = row[O_QT + 12 + ci];
-        pin(uj); pin(vj); pin(pkq); pin(pkv); pin(pp); pin(h0); pin(h1); pin(h2); pin(h3); pin(h4); pin(hv);
-        pin(z0); pin(z1); pin(z2); pin(z3); pin(z4); pin(curv); pin(la); pin(ta); pin(lb); pin(tb);
-        if (lane < 30 || lane >= 30 + NW) return;
-        double v = 0.0;
-        if (cls == 0) {
-            if (kk < N) {
-                v = k_dt * (k_2wu * uj + k_c2 * (uj - vj));
-                v += k_p1 * pkq + k_p2 * pkv;
-            }
-        } else if (cls == 1) {
-            if (kk > 0) {
-                if (kk < N) {
-                    double s_ = 0.0;
-                    s_ += h0 * z0; s_ += h1 * z1; s_ += h2 * z2; s_ += h3 * z3; s_ += h4 * z4;
-                    v = k_dt * s_ + pkq;
-                }
-                v -= pp;
-            }
-        } else {
-            if (kk > 0) {
-                if (kk < N) {
-                    v = k_dt * (hv * z4 + k_c2 * (vj - uj));
-                    v += k_p1 * pkq + k_p2 * pkv;
-                }
-                v -= pp;
-            }
-        }
-        const bool hc = cls == 0 ? kk < N : (cls == 1 && kk >= 1 && kk < N);
-        if (hc) {
-            if (c_lo) {
-                v -= la;
-                n_i = fmax(n_i, fabs((cb_lo - curv) + ta));
-                n_c = fmax(n_c, fabs(la * ta));
-            }
-            if (c_hi) {
-                v += lb;
-                n_i = fmax(n_i, fabs((curv - cb_hi) + tb));
-                n_c = fmax(n_c, fabs(lb * tb));
-            }
-        }
-        if (ci >= 6 && kk == 0) v = 0.0;
-        n_s = fmax(n_s, fabs(v));
-    };
     // update of one landed row: dw += a ddw ; (lam, t) += a (dlam, dt) -- or the warm-start clamp in mode 0
     // phase R operand slots: every lane fetches its role's operands up front (idle lanes: offset 0)
     //   lanes 0..17 stationarity row | 18..29 dynamics residual row | 32.. record copies, pi hand-over
@@ -508,9 +437,9 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
             if (lane < NW) row[O_QW + lane] += a * row[I_D + lane];
         } else {
             if (kr == 0 && lane < NX) row[O_QW + 6 + lane] = xh - row[O_X + lane];
-            if (!FASTM && kr == N && lane >= 12 && lane < 18) row[O_QW + lane - 12] = 0.0;
+            if (kr == N && lane >= 12 && lane < 18) row[O_QW + lane - 12] = 0.0;
         }
-        if (!FASTM && lane >= 18 && lane < 30) {
+        if (lane >= 18 && lane < 30) {
             const int j = lj;
             const bool hc = j < 6 ? kr < N : (kr >= 1 && kr < N);
             const bool blo = hc && lj_lo, bhi = hc && lj_hi;
@@ -535,37 +464,6 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
 #ifdef MPCB_NOCOMPUTE
         (void)cur; (void)nxt; store_out(bout, o, lane); return;
 #endif
-        if (FUSE) {
-            // NLP residual of the previous step's iterate, from the rows as they landed (program order: these LDS reads
-            // are issued before the warm-start writes below)
-            if (k == 0) nlp_stat(cur, cur, 0);
-            // (the defect lanes' operands go out with the stationarity lanes': one round trip for both)
-            const int l12 = lane < 12 ? lane : 0;
-            double b_xq = cur[O_X + jd], b_xv = cur[O_X + 6 + jd], b_u = cur[O_U + jd], b_xn = nxt[O_X + l12], b_x0 = cur[O_X + l12];
-            double b_r = cur[I_L + O_R + (lane >= 6 && lane < 6 + NTASK ? lane - 6 : 0)];
-            if (k + 1 <= N) nlp_stat(nxt, cur + O_QPI, k + 1);
-            pin(b_xq); pin(b_xv); pin(b_u); pin(b_xn); pin(b_x0); pin(b_r);
-            if (lane < 12) {
-                // dynamics defect (prediction_model.py:317-320) and this stage's share of the cost
-                double v = 0.0;
-                if (k < N) {
-                    v = lane < 6 ? (b_xq + d_a * b_xv + d_b * b_u) - b_xn : (d_a * b_xv + d_b * b_u) - b_xn;
-                    n_e = fmax(n_e, fabs(v));
-                    if (lane < 6) {
-                        const double qdd = d_cq * (b_u - b_xv);
-                        csum += 0.5 * k_dt * (k_2wu * b_u * b_u + k_wq * qdd * qdd);
-                    } else if (lane < 6 + NTASK) {
-                        csum += 0.5 * k_dt * d_wt * b_r * b_r;
-                    }
-                }
-                if (k == 0) n_i = fmax(n_i, fabs(xprev - b_x0));   // lbx_0 = ubx_0 = x_hat of that QP
-                cur[I_L + O_BD + lane] = v;          // the QP's dynamics residual rb of this stage reads it below
-                o[O_RY + O_BD + lane] = v;
-            } else if (lane < 14) {
-                o[O_RY + 10 + (lane - 12)] = 0.0;    // padding scalars of the record
-            }
-            fence();
-        }
         if (k == 0) { upd_row(cur, 0); fence(); }
         // ---- U: update the lookahead row; pi_k += a dpi (stored with stage k+1)
         //      Y (lanes 48..52): y_i = w_i (r_i + G_i . delta_k) -- dw_k was updated when row k was the lookahead row
@@ -608,10 +506,7 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
             pin(gv0); pin(gv1); pin(gv2); pin(gv3); pin(gv4); pin(gv5);
             double l0 = nxt[O_QLAM + lj], t0 = nxt[O_QT + lj], l1 = nxt[O_QLAM + 12 + lj], t1 = nxt[O_QT + 12 + lj];
             pin(l0); pin(t0); pin(l1); pin(t1);
-            if (FASTM && k > 0) {   // dw = 0 beyond the embedded x_0
-                wq0 = wq1 = wq2 = wq3 = wq4 = wq5 = 0.0; wv0 = wv1 = wv2 = wv3 = wv4 = wv5 = 0.0;
-            }
-            if (!FASTM && k + 1 <= N) {
+            if (k + 1 <= N) {
                 // (upd_row of the lookahead row on registers: warm-start clamp; the row is never row 0)
                 const int kr = k + 1;
                 if (kr == N && lane >= 12 && lane < 18) nxt[O_QW + lane - 12] = 0.0;
@@ -650,18 +545,6 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
             pin(l_lo); pin(t_lo); pin(l_hi); pin(t_hi);
             pin(g0); pin(g1); pin(g2); pin(g3); pin(g4); pin(gv); pin(y0); pin(y1); pin(y2); pin(y3); pin(y4);
             pin(q_h); pin(q_n); pin(c1); pin(c2);
-            if (FASTM) {
-                // (dw, pi, lam) = 0: only the embedded x_0 part of stage 0 survives
-                if (lane < NW) {
-                    q_b = 0.0; q_e = 0.0; q_f = 0.0; q_h = 0.0;
-                    q_d = k == 0 ? q_d : 0.0; q_g = 0.0;
-                } else if (lane < 30) {
-                    // dynamics rows: q_a = dx_k[lj], q_b = dv_lj (lj < 6) | du_(lj-6), q_c = du_lj, q_n = dx_{k+1}[lj]
-                    q_a = k == 0 ? q_a : 0.0;
-                    q_b = k == 0 && lj < 6 ? q_b : 0.0;
-                    q_c = 0.0; q_n = 0.0;
-                }
-            }
             if (lane < NW) {
                 // stationarity of the QP at w + dw (mpc_core.h stat_cls with `with_delta`), same operation order
                 double rg = 0.0;
@@ -696,7 +579,7 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
                 double gt = rg;
                 if (cls < 2) {
                     const bool hc = cls == 0 ? k < N : (k >= 1 && k < N);
-                    const bool blo = !FASTM && hc && c_lo, bhi = !FASTM && hc && c_hi;
+                    const bool blo = hc && c_lo, bhi = hc && c_hi;
                     const double v = hc ? q_v : 0.0, dv = q_g;
                     // both sides are evaluated in every lane and masked by selects (an absent bound holds lam = 0, t = 1:
                     // its terms are exact zeros or are deselected), in the operation order of the branchy form
@@ -716,13 +599,11 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
                     gt = bhi ? gt - (rmu + l_hi * rdu) * it_hi : gt;
                     a_mu = bhi ? a_mu + rmu : a_mu;
                     a_d = fmax(a_d, fabs(rdu)); a_m = fmax(a_m, fabs(rmu));
-                    if (!FASTM) {
-                        o[O_3 + O_RD + ci] = rdl; o[O_3 + O_RD + 12 + ci] = rdu;
-                        o[O_3 + O_RM + ci] = rml; o[O_3 + O_RM + 12 + ci] = rmu;
-                    }
+                    o[O_3 + O_RD + ci] = rdl; o[O_3 + O_RD + 12 + ci] = rdu;
+                    o[O_3 + O_RM + ci] = rml; o[O_3 + O_RM + 12 + ci] = rmu;
                     o[O_G + ci] = gam;
                 }
-                if (!FASTM) o[O_3 + O_RG + ci] = rg;
+                o[O_3 + O_RG + ci] = rg;
                 o[O_G + 12 + ci] = gt;
                 a_g = fmax(a_g, fabs(rg));
             } else if (lane < 30) {
@@ -737,11 +618,9 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
                 o[O_G + 30 + i] = v;
             } else if (lane >= 32) {
                 // the updated QW..QT of this stage and r, y go out with the residual records (39 + 5 items, two per lane
-                // where needed; MODE 2: BD was put there by its lanes); lanes 48..59: pi_k for the next stage
-                if (!FASTM) {
-                    ((MPC_LOCAL D2 *)(o + O_W))[lc] = c1;
-                    if (lc < 7) ((MPC_LOCAL D2 *)(o + O_W))[32 + lc] = c2;
-                }
+                // where needed); lanes 48..59: pi_k for the next stage
+                ((MPC_LOCAL D2 *)(o + O_W))[lc] = c1;
+                if (lc < 7) ((MPC_LOCAL D2 *)(o + O_W))[32 + lc] = c2;
                 if (lc >= 7 && lc < 12) ((MPC_LOCAL D2 *)(o + O_RY))[lc - 7] = c2;
                 if (lane >= 48 && lane < 60) sm.vec[(k + 1) & 1][lane - 48] = q_a;
             }
@@ -751,10 +630,6 @@ SE_PASS IpmNorms residual_pass(double a, double *nlp_out = nullptr)
     });
     IpmNorms r;
     r.ng = wmax(a_g); r.nb = wmax(a_b); r.nd = wmax(a_d); r.nm = wmax(a_m); r.smu = wsum(a_mu); r.nc = wsum(ncl);
-    if (FUSE) {
-        nlp_out[0] = wsum(csum);
-        nlp_out[1] = wmax(n_s); nlp_out[2] = wmax(n_e); nlp_out[3] = wmax(n_i); nlp_out[4] = wmax(n_c);
-    }
     return r;
 }
 
@@ -1012,15 +887,18 @@ SE_PASS IpmNorms residual_items(double a)
     return r;
 }
 
-// SQP_RTI, the first pass of a step, ITEM-parallel (round 4): what residual_pass<3 | 4> and nlp_res_pass<false> did stage by stage with
-// 10-20 lanes busy per role (~400 instructions per stage: 154 us of a 586 us fast-path step at batch 4096) has no recursion in it -- every
-// element is a function of its own stage's records and one row of each neighbour -- so the 64 lanes take 64 JOINT ITEMS (k, j < 6) at a
-// time, operands straight from the stage records into registers (residual_items above; mpc_core.h nlp_direct's joint items):
-//   NORMS  acados get_residuals / get_cost of the iterate lin_pass has just linearised (nlp_res_pass<false>): dynamics defect BD -> G2,
+// SQP_RTI, the first pass of a step, ITEM-parallel: the NLP residual norms and the fast path's right-hand side have no recursion in them --
+// every element is a function of its own stage's records and one row of each neighbour -- so the 64 lanes take 64 JOINT ITEMS (k, j < 6) at a
+// time, operands straight from the stage records into registers (residual_items above; mpc_core.h nlp_direct's joint items), instead of
+// walking the stages with 10-20 lanes busy per role (~400 instructions per stage; 37 us instead of 154 us of a fast-path step at batch 4096,
+// profiles/r04_stream_items_ab.txt):
+//   NORMS  acados get_residuals / get_cost of the iterate lin_pass has just linearised: dynamics defect BD -> G2,
 //          cost = sum_k dt/2 r'Wr, inf-norms [stat, eq, ineq, comp] with the QP's multipliers as the last solve left them;
 //          out5 = [cost, stat, eq, ineq, comp]; `xsel`: x_hat that solve was made for (0: sm.xhat, 1: sm.vec[3])
-//   RHS    right-hand side of the bound-inactive fast path for the NEW x_hat (residual_pass<3>; mpc_core.h fast_rhs): Gamma = 0,
-//          gt = g at (dw, pi, lam) = 0 with dx_0 = x_hat - x_0 embedded, rb = b + A dx_0; stage 0's y = W (r + G dx_0)
+//   RHS    right-hand side of the bound-inactive fast path for the NEW x_hat (mpc_ipm.h; mpc_core.h fast_rhs): Gamma = 0,
+//          gt = g at (dw, pi, lam) = 0 with dx_0 = x_hat - x_0 embedded, rb = b + A dx_0; stage 0's y = W (r + G dx_0).  No warm-start
+//          clamp: the previous QP's (w, pi, lam, t) stay as they are, so a rejected attempt is followed by residual_pass<0> as if
+//          nothing had happened.
 // ONE function for every place the norms are formed (fused with the right-hand side, alone at the end of a launch / work item, before
 // an interior-point solve), so a run cut into work items reproduces the plain launch bit for bit.
 // SQPM (full SQP): the norms use the blended NLP multipliers of G5 (NPI | NLAM | NT: the same relative layout as QPI | QLAM | QT of G1).
@@ -1725,7 +1603,7 @@ SE_PASS void corrector_pass(double sigma_mu)
 // =============================================================================================== fast path: commit
 // The accepted candidate becomes the QP iterate.  SQP_RTI does not copy anything for that: the forward sweep left the candidate in
 // whichever of the two 78-double slots of a stage (G1 [QW | QPI | QLAM | QT], G3 [DW | DPI | DLAM | DT]: same layout) does not hold the
-// iterate, unshifted, and ipm_solve flips the slot index (`cur`, kept in the workspace, state[28]); lin_pass and rti_items read the iterate
+// iterate, unshifted, and ipm_solve flips the slot index (`cur`, kept in the workspace, state[ST_CUR]); lin_pass and rti_items read the iterate
 // through it.  This pass is what remains: the COPY of the G3 slot into the G1 slot -- 39 16-byte items per stage -- that puts the iterate
 // where the interior-point passes and the SQP line search expect it: before an interior-point solve when the iterate sits in G3
 // (rare), and at every acceptance in full SQP (`embed_x0`: stage 0's x part is x_hat - x_0 there, lbx_0 = ubx_0; SQP_RTI's lin_pass
@@ -1775,7 +1653,7 @@ SE_PASS void fast_commit(bool embed_x0)
 // HPIPM d_ocp_qp_ipm_solve main loop (mpc_core.h ipm_solve).  Returns HPIPM status 0 ok / 1 max-iter / 2 min-step / 3 NaN.
 #ifdef MPCB_SPROF
 #define SPROF_T0(v) const double v = wclock()
-#define SPROF_ADD(i, v) if (threadIdx.x == 0) g_ssm.w.state[32 + (i)] += wclock() - v
+#define SPROF_ADD(i, v) if (threadIdx.x == 0) g_ssm.w.state[ST_PROF + (i)] += wclock() - v
 #else
 #define SPROF_T0(v)
 #define SPROF_ADD(i, v)
@@ -1790,20 +1668,13 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
     SSmem &sm = g_ssm;
     const double tol = sm.P.qp_tol;
     int tried = 0;
-#ifdef MPCB_STREAM_SEQ_RES      // (A/B builds: the sequential passes read the iterate in G1 only)
-    cur = nullptr;
-#endif
     const int slot = cur ? *cur : 0;
     if (sizeof(FT) == 8 && uni(sm.P.fast_off == 0.0 ? 1 : 0)) {
         if (fast[0] > 0) fast[0]--;
         else {
             tried = 1;
             SPROF_T0(t_r);
-#ifdef MPCB_STREAM_SEQ_RES
-            if (nlp_prev) residual_pass<4>(0.0, nlp_prev); else residual_pass<3>(0.0);
-#else
             if (nlp_prev) rti_items<true, true>(1, nlp_prev, slot); else rti_items<false, true>(0, nullptr);
-#endif
             SPROF_ADD(10, t_r);
             nlp_prev = nullptr;                                    // the previous step's residuals are done, whatever happens next
             SPROF_T0(t_f);
@@ -1818,7 +1689,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
                 else fast_commit(true);          // full SQP: copied to G1, x_0 embedded
                 SPROF_ADD(13, t_c);
 #ifdef MPCB_SPROF
-                if (threadIdx.x == 0) g_ssm.w.state[32 + 15] += 1.0;
+                if (threadIdx.x == 0) g_ssm.w.state[ST_PROF + 15] += 1.0;
 #endif
                 fast[1] = 0;
                 *iters_out = 1;
@@ -1829,13 +1700,9 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         }
     }
     // nlp_prev: the NLP residual / cost of the previous step's iterate is still to be evaluated -- by this QP's first pass
-#ifdef MPCB_STREAM_SEQ_RES
-    IpmNorms r = nlp_prev ? residual_pass<2>(0.0, nlp_prev) : residual_pass<0>(0.0);
-#else
     if (nlp_prev) rti_items<true, false>(1, nlp_prev, slot);     // (the same items as everywhere else: see rti_items)
     if (cur && slot == 1) { fast_commit(false); *cur = 0; }      // the interior-point passes expect the iterate in G1 (this also overwrites a rejected candidate there)
     IpmNorms r = residual_pass<0>(0.0);
-#endif
     const double nc = unid(r.nc);
     double mu = nc > 0 ? unid(r.smu) / nc : 0.0;
     int it = 0, status = 1;
@@ -1874,16 +1741,12 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         }
         const double a = ipm::step_scale(alpha);
         SPROF_T0(tr);
-#ifdef MPCB_STREAM_SEQ_RES
-        r = residual_pass<1>(a);
-#else
         r = residual_items_ok(uni(sm.n_hor)) ? residual_items(a) : residual_pass<1>(a);
-#endif
         SPROF_ADD(4, tr);
         mu = nc > 0 ? unid(r.smu) / nc : 0.0;
     }
 #ifdef MPCB_SPROF
-    if (threadIdx.x == 0) g_ssm.w.state[32 + 7] += it;
+    if (threadIdx.x == 0) g_ssm.w.state[ST_PROF + 7] += it;
 #endif
     *iters_out = it + tried;
     return status;
@@ -1970,7 +1833,7 @@ SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int s
 #ifdef MPCB_SPROF_LIN
         __builtin_amdgcn_s_waitcnt(0);
         const double tl1 = wclock();
-        if (lane == 0) { g_ssm.w.state[32 + 0] += tl1 - tl0; }
+        if (lane == 0) { g_ssm.w.state[ST_PROF + 0] += tl1 - tl0; }
 #endif
         if (k < N) {
             double rl[10];                                             // r | Y; the Jacobian goes straight to the record
@@ -1995,125 +1858,9 @@ SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int s
         const double tl2 = wclock();
         __builtin_amdgcn_s_waitcnt(0);
         const double tl3 = wclock();
-        if (lane == 0) { g_ssm.w.state[32 + 1] += tl2 - tl1; g_ssm.w.state[32 + 2] += tl3 - tl2; }
+        if (lane == 0) { g_ssm.w.state[ST_PROF + 1] += tl2 - tl1; g_ssm.w.state[ST_PROF + 2] += tl3 - tl2; }
 #endif
     }
-}
-
-// Dynamics defect of the NLP iterate, cost = sum_k dt/2 r'Wr (acados get_cost()) and acados' ocp_nlp_res_compute
-// inf-norms [stat, eq, ineq, comp] with the QP multipliers (SQP_RTI).  Forward sweep, one row of lookahead (x_{k+1}).
-//   in : G1 row | G2 [R..GV]      out : G2 BD
-// SQPM: the residuals use the NLP multipliers of G5 (full SQP) instead of the QP's.
-template <bool SQPM>
-SE_PASS double nlp_res_pass(double *res4)
-{
-    SSmem &sm = g_ssm;
-    const InstParams &P = sm.P;
-    const int lane = threadIdx.x;
-    const int N = uni(sm.n_hor);
-    const SWs w = sm.w;
-    constexpr int I_L = 96, I_5 = 156;
-    constexpr int ITEMS = SQPM ? 108 : 78;
-    constexpr int MO_PI = SQPM ? I_5 + O_NPI : O_QPI, MO_LAM = SQPM ? I_5 + O_NLAM : O_QLAM, MO_T = SQPM ? I_5 + O_NT : O_QT;
-    Bundle<2, ITEMS> bin;
-    Bundle<1, 6> bout;
-    {
-        if (SQPM) { const Seg si[3] = {segd(w.G1, w.ld, 0, W1), segd(w.G2, w.ld, 0, W2_LIN), segd(w.G5, w.ld, 0, 60)}; bin.setup(si, lane); }
-        else { const Seg si[2] = {segd(w.G1, w.ld, 0, W1), segd(w.G2, w.ld, 0, W2_LIN)}; bin.setup(si, lane); }
-        const Seg so[1] = {segd(w.G2, w.ld, O_BD, 12)};
-        bout.setup(so, lane);
-        bout.seek(0, 1);
-    }
-    double csum = 0.0, a_s = 0, a_e = 0, a_i = 0, a_c = 0;
-    // per-lane parameters in registers for the whole sweep (see residual_pass)
-    const int jd = lane < 12 ? lane % 6 : 0;                                  // lanes 0..11: dynamics row / cost share
-    const double d_a = lane < 6 ? P.a12[jd] : P.a22[jd], d_b = lane < 6 ? P.b1[jd] : P.b2[jd], d_cq = P.cq[jd];
-    const double d_wt = P.w_task[lane >= 6 && lane < 6 + NTASK ? lane - 6 : 0];
-    const int ci = lane >= 16 && lane < 34 ? lane - 16 : 0, cls = ci / 6, cj = ci - cls * 6;   // lanes 16..33: stationarity row
-    const bool c_lo = cls < 2 && bnd_lo(P, ci < NB ? ci : 0) > -BOUND_INF, c_hi = cls < 2 && bnd_hi(P, ci < NB ? ci : 0) < BOUND_INF;
-    const double cb_lo = bnd_lo(P, ci < NB ? ci : 0), cb_hi = bnd_hi(P, ci < NB ? ci : 0);
-    const double k_dt = P.dt, k_2wu = 2.0 * P.w_u, k_wq = P.w_qddot, k_c2 = P.w_qddot * P.cq[cj] * P.cq[cj];
-    const double k_p1 = cls == 0 ? P.b1[cj] : P.a12[cj], k_p2 = cls == 0 ? P.b2[cj] : P.a22[cj];
-    const double xh = lane >= 48 && lane < 60 ? sm.xhat[lane - 48] : 0.0;
-    if (lane < NX) sm.vec[0][lane] = 0.0;
-    sweep<ITEMS, 1, false>(bin, N, lane, [&](int k, double *cur, double *nxt, double *) {
-        double *o = sm.out[k & 1];
-        const double *r1 = cur, *r2 = cur + I_L;
-        if (lane < 12) {
-            // dynamics defect (prediction_model.py:317-320) and this stage's share of the cost
-            double v = 0.0;
-            if (k < N) {
-                const int j = jd;
-                const double xq = r1[O_X + j], xv = r1[O_X + 6 + j], uj = r1[O_U + j];
-                v = lane < 6 ? (xq + d_a * xv + d_b * uj) - nxt[O_X + j] : (d_a * xv + d_b * uj) - nxt[O_X + 6 + j];
-                a_e = fmax(a_e, fabs(v));
-                if (lane < 6) {
-                    const double qdd = d_cq * (uj - xv);
-                    csum += 0.5 * k_dt * (k_2wu * uj * uj + k_wq * qdd * qdd);
-                } else if (lane < 6 + NTASK) {
-                    const double r = r2[O_R + (lane - 6)];
-                    csum += 0.5 * k_dt * d_wt * r * r;
-                }
-            }
-            o[lane] = v;
-        } else if (lane >= 16 && lane < 34 && res4) {
-            const int j = cj;
-            const double *pk = cur + MO_PI, *pm = sm.vec[k & 1];
-            // stationarity of the NLP at the iterate (mpc_core.h stat_cls without delta), same operation order
-            double v = 0.0;
-            if (cls == 0) {
-                if (k < N) {
-                    const double uj = r1[O_U + j], vj = r1[O_X + 6 + j];
-                    v = k_dt * (k_2wu * uj + k_c2 * (uj - vj));
-                    v += k_p1 * pk[j] + k_p2 * pk[6 + j];
-                }
-            } else if (cls == 1) {
-                if (k > 0) {
-                    if (k < N) {
-                        double s_ = 0.0;
-#pragma unroll
-                        for (int i = 0; i < NTASK; i++) s_ += r2[O_GQ + i * 6 + j] * r2[O_Y + i];
-                        v = k_dt * s_ + pk[j];
-                    }
-                    v -= pm[j];
-                }
-            } else {
-                if (k > 0) {
-                    if (k < N) {
-                        const double uj = r1[O_U + j], vj = r1[O_X + 6 + j];
-                        v = k_dt * (r2[O_GV + j] * r2[O_Y + 4] + k_c2 * (vj - uj));
-                        v += k_p1 * pk[j] + k_p2 * pk[6 + j];
-                    }
-                    v -= pm[6 + j];
-                }
-            }
-            const bool hc = cls == 0 ? k < N : (cls == 1 && k >= 1 && k < N);
-            if (hc) {
-                const double curv = r1[ci < 6 ? O_U + ci : O_X + ci - 6];
-                const double *lam = cur + MO_LAM, *tt = cur + MO_T;
-                if (c_lo) {
-                    v -= lam[ci];
-                    a_i = fmax(a_i, fabs((cb_lo - curv) + tt[ci]));
-                    a_c = fmax(a_c, fabs(lam[ci] * tt[ci]));
-                }
-                if (c_hi) {
-                    v += lam[12 + ci];
-                    a_i = fmax(a_i, fabs((curv - cb_hi) + tt[12 + ci]));
-                    a_c = fmax(a_c, fabs(lam[12 + ci] * tt[12 + ci]));
-                }
-            }
-            if (ci >= 6 && k == 0) v = 0.0;
-            a_s = fmax(a_s, fabs(v));
-        } else if (lane >= 48 && lane < 60) {
-            if (k == 0 && res4) a_i = fmax(a_i, fabs(xh - r1[O_X + lane - 48]));   // lbx_0 = ubx_0 = x_hat
-            sm.vec[(k + 1) & 1][lane - 48] = cur[MO_PI + lane - 48];
-        }
-        fence();
-        store_out(bout, o, lane);
-    });
-    const double cost = wsum(csum);
-    if (res4) { res4[0] = wmax(a_s); res4[1] = wmax(a_e); res4[2] = wmax(a_i); res4[3] = wmax(a_c); }
-    return cost;
 }
 
 // =============================================================================================== SQP line search
@@ -2132,9 +1879,7 @@ SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskR
     const SWs w = sm.w;
     double acc = 0.0;
     for (int k0 = 0; k0 <= N; k0 += WAVE) {
-#ifndef MPCB_NO_LICM_BLOCK
         asm volatile("" ::: "memory");     // (parameters are read where they are used, not hoisted out of the loop and spilled: mpc_core.h merit_pass)
-#endif
         const int k = k0 + lane;
         if (k > N) continue;
         MPC_GLOBAL double *r1 = (MPC_GLOBAL double *)((char *)w.G1 + (size_t)k * w.ld);
@@ -2195,7 +1940,7 @@ SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskR
         }
         if (k == 0) {
 #pragma unroll
-            for (int i = 0; i < 12; i++) acc += w.state[13 + i] * fabs(sm.xhat[i] - xx[i]);
+            for (int i = 0; i < 12; i++) acc += w.state[ST_X0_MW + i] * fabs(sm.xhat[i] - xx[i]);
         }
     }
     return wsum(acc);
@@ -2224,7 +1969,7 @@ SE_PASS void update_x0_weights(int sqp_iter)
                 P.a22[jj] * r1[O_QPI + 6 + jj] + P.dt * P.lm * r1[O_QW + 12 + jj];
         }
         const double a = fabs(v);
-        double *mwp = &w.state[13 + lane];
+        double *mwp = &w.state[ST_X0_MW + lane];
         *mwp = sqp_iter == 0 ? a : fmax(a, 0.5 * (*mwp + a));
     }
     __builtin_amdgcn_s_waitcnt(0);
@@ -2298,173 +2043,208 @@ SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo)
     return log_lo;
 }
 
-// Simulator.run (simulator.py:199-241) for steps [step0, step1) of one simulation, SQP_RTI.
+// =============================================================================================== one simulation: set-up, carry, MPC step
+// Simulation `inst` into this wavefront's LDS: its parameter block, its workspace, its horizon (returned).
+template <class FT>
+SE_DEV int load_instance(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride, int inst)
+{
+    SSmem &sm = g_ssm;
+    const int lane = threadIdx.x;
+    // ragged batch: this simulation's own horizon (the workspace stride is sized for the longest)
+    const double nh = params[inst].n_hor;
+    const int N = uni(nh > 0.0 ? (int)nh : pb.N);
+    const double *ps = reinterpret_cast<const double *>(params + inst);
+    double *pd = reinterpret_cast<double *>(&sm.P);
+    for (int e = lane; e < (int)(sizeof(InstParams) / sizeof(double)); e += WAVE) pd[e] = ps[e];
+    if (lane == 0) {
+        sm.rbp = rbp;
+        SWs ws = sws_carve<FT>(ws_base + (size_t)inst * ws_stride, N, pb.solver_type == 0);
+        ws.state = ws_base + (size_t)inst * ws_stride + (ws_stride - STATE_DOUBLES);   // at the end of the stride whatever this simulation's horizon
+        sm.w = ws;
+        sm.n_hor = N;
+    }
+    fence();
+    return N;
+}
+
+// acados initial guess: x_k = x0, u_k = 0, all multipliers / QP memory 0
+template <class FT>
+SE_DEV void initial_guess(const Problem &pb, int N)
+{
+    SSmem &sm = g_ssm;
+    const InstParams &P = sm.P;
+    const SWs w = sm.w;
+    const int lane = threadIdx.x;
+    const size_t tot = sws_doubles_per_instance<FT>(N, pb.solver_type == 0) - STATE_DOUBLES;
+    for (size_t e = lane; e < tot; e += WAVE) w.G1[e] = 0.0;      // G1 is the workspace base
+    if (lane < STATE_DOUBLES) w.state[lane] = 0.0;
+    fence();
+    for (int e = lane; e < (N + 1) * NX; e += WAVE) {
+        const int k = e / NX, i = e - k * NX;
+        w.G1[(size_t)k * (w.ld / 8) + O_X + i] = i < 6 ? P.q0[i] : P.qdot0[i - 6];
+    }
+    __builtin_amdgcn_s_waitcnt(0);                                // the initial iterate is in memory before the first pass reads it
+    fence();
+}
+
+// The solver memory that goes from one MPC step to the next in registers, and from one launch to the next in w.state (the x_0 merit
+// weights ST_X0_MW stay there, in place; everything else of the solver is the stage records).
+struct Carry {
+    double lin_cost = 0.0;             // cost of the held linearisation
+    bool lin_valid = false;
+    int fast[2] = {0, 0};              // fast path: QPs left before the next attempt, length of the current suspension
+    int cur = 0;                       // SQP_RTI: slot of the stage records that holds the QP iterate (fast_commit comment)
+    SE_DEV void load(const double *st)
+    {
+        lin_cost = unid(st[ST_LIN_COST]);
+        lin_valid = uni(st[ST_LIN_VALID] != 0.0 ? 1 : 0) != 0;
+        fast[0] = uni((int)st[ST_FAST]); fast[1] = uni((int)st[ST_FAST + 1]); cur = uni((int)st[ST_CUR]);
+    }
+    // (with the state the next step starts from: x_hat)
+    SE_DEV void store(double *st) const
+    {
+        const int lane = threadIdx.x;
+        if (lane < NX) st[ST_Z + lane] = g_ssm.xhat[lane];
+        if (lane == 12) { st[ST_LIN_COST] = lin_cost; st[ST_LIN_VALID] = lin_valid ? 1.0 : 0.0; st[ST_FAST] = fast[0]; st[ST_FAST + 1] = fast[1]; st[ST_CUR] = cur; }
+    }
+};
+
+struct StepStats {
+    int status, sqp_iter, qp_iter;
+    double cost, res4[4];              // cost and acados' residual norms [stat, eq, ineq, comp] of the iterate the step leaves
+};
+
+// One MPC step from sm.xhat (mpc_core.h nlp_step): SQP_RTI or full SQP.  The callers differ in the linearisation and the line search --
+// `lin(alpha, do_update, sqp_mult, slot)`: lin_pass or lin_pass<true> against a task reference, `search(sqp_iter)`: line_search likewise --
+// and, SQP_RTI, in who forms a step's cost and residual norms: a trailing rti_items here, or, with `defer`, the next step's first pass,
+// which streams the same records (the stats then hold the cost carried in and zeros; that next call gets `nlp_prev` and fills it with
+// [cost, stat, eq, ineq, comp] of this step).
+template <class FT, class Lin, class Search>
+SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer)
+{
+    SSmem &sm = g_ssm;
+    const InstParams &P = sm.P;
+    const int lane = threadIdx.x;
+    StepStats s = {0, 1, 0, c.lin_cost, {0, 0, 0, 0}};
+    if (pb.solver_type == 1) {
+        // SQP_RTI: one linearisation, one QP, full step
+        SPROF_T0(tq);
+        if (!c.lin_valid) {
+            lin(0.0, false, false, -1); __builtin_amdgcn_s_waitcnt(0); fence();
+            double o5[5];
+            rti_items<true, false>(0, o5, c.cur);
+            c.lin_cost = unid(o5[0]);
+        }
+        const int qs = ipm_solve<FT>(pb.qp_iter_max, &s.qp_iter, c.fast, nlp_prev, &c.cur);
+        SPROF_ADD(5, tq);
+        const bool ok = qs == 0 || qs == 1;
+        if (!ok) s.status = 4;                                         // ACADOS_QP_FAILURE, iterate untouched
+        __builtin_amdgcn_s_waitcnt(0);
+        SPROF_T0(tl);
+        lin(1.0, ok, false, c.cur);
+        __builtin_amdgcn_s_waitcnt(0);                                 // the records written lane by lane are complete before they are streamed
+        fence();
+        SPROF_ADD(8, tl);
+        SPROF_T0(tn);
+        if (defer) {
+            if (lane < NX) sm.vec[3][lane] = sm.xhat[lane];            // the x_hat this QP was solved for
+        } else {
+            double o5[5];
+            rti_items<true, false>(0, o5, c.cur);
+            s.cost = unid(o5[0]); s.res4[0] = o5[1]; s.res4[1] = o5[2]; s.res4[2] = o5[3]; s.res4[3] = o5[4];
+        }
+        SPROF_ADD(9, tn);
+        c.lin_valid = true;
+    } else {
+        // full SQP (acados ocp_nlp_sqp restated): linearise -> residuals / convergence test -> QP -> merit backtracking -> update;
+        // sqp_iter counts QPs
+        const double tol = P.tol, tol_eq = P.tol_eq, tol_in = P.tol_ineq, tol_co = P.tol_comp;
+        s.status = 2;                                                  // ACADOS_MAXITER unless decided otherwise
+        double alpha = 0.0;
+        bool pending = false;                                          // a step (alpha) waits to be applied by the next linearisation
+        for (s.sqp_iter = 0; s.sqp_iter < pb.max_iter; s.sqp_iter++) {
+            if (pending || !c.lin_valid || s.sqp_iter == 0) {
+                __builtin_amdgcn_s_waitcnt(0);
+                lin(alpha, pending, true, -1);
+                __builtin_amdgcn_s_waitcnt(0);
+                fence();
+                double o5[5];
+                rti_items<true, false, true>(0, o5);
+                s.cost = unid(o5[0]); s.res4[0] = unid(o5[1]); s.res4[1] = unid(o5[2]); s.res4[2] = unid(o5[3]); s.res4[3] = unid(o5[4]);
+                pending = false;
+                c.lin_valid = true;
+            }
+            if (s.res4[0] < tol && s.res4[1] < tol_eq && s.res4[2] < tol_in && s.res4[3] < tol_co) { s.status = 0; break; }
+            if (s.res4[0] != s.res4[0] || s.cost != s.cost) { s.status = 1; break; }
+            int it = 0;
+            const int qs = ipm_solve<FT>(pb.qp_iter_max, &it, c.fast);
+            s.qp_iter += it;
+            if (qs != 0 && qs != 1) { s.status = 4; break; }
+            __builtin_amdgcn_s_waitcnt(0);
+            fence();
+            alpha = pb.fixed_step ? 1.0 : search(s.sqp_iter);
+            pending = true;
+        }
+        if (pending) {   // max-iter exit: apply the last step; the residuals of the last check stay
+            __builtin_amdgcn_s_waitcnt(0);
+            lin(alpha, true, true, -1);
+            __builtin_amdgcn_s_waitcnt(0);
+            fence();
+            double o5[5];
+            rti_items<true, false, true>(0, o5);
+            s.cost = unid(o5[0]);
+            c.lin_valid = true;
+        }
+    }
+    c.lin_cost = s.cost;
+    __builtin_amdgcn_s_waitcnt(0);
+    fence();
+    return s;
+}
+
+// =============================================================================================== rollout and controller step
+// Simulator.run (simulator.py:199-241) for steps [step0, step1) of one simulation.
 template <class FT>
 SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                     const Outputs &out, int inst, int step0, int step1)
 {
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
-    // ragged batch: this simulation's own horizon (the workspace stride is sized for the longest)
-    const double nh = params[inst].n_hor;
-    const int N = uni(nh > 0.0 ? (int)nh : pb.N), Nsim = pb.Nsim, T1 = Nsim + 1;
-    {
-        const double *ps = reinterpret_cast<const double *>(params + inst);
-        double *pd = reinterpret_cast<double *>(&sm.P);
-        for (int e = lane; e < (int)(sizeof(InstParams) / sizeof(double)); e += WAVE) pd[e] = ps[e];
-        if (lane == 0) {
-            sm.rbp = rbp;
-            SWs ws = sws_carve<FT>(ws_base + (size_t)inst * ws_stride, N, pb.solver_type == 0);
-            ws.state = ws_base + (size_t)inst * ws_stride + (ws_stride - STATE_DOUBLES);   // at the end of the stride whatever this simulation's horizon
-            sm.w = ws;
-            sm.n_hor = N;
-        }
-    }
-    fence();
+    const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), Nsim = pb.Nsim, T1 = Nsim + 1;
     const InstParams &P = sm.P;
     const SWs w = sm.w;
     const size_t sbase = (size_t)inst * Nsim;
-    bool lin_valid = false;
+    Carry c;
     bool res_pending = false;          // SQP_RTI: cost / residual norms of the previous step are formed by this step's first pass
-    double lin_cost = 0.0;
-    int fast[2] = {0, 0};              // fast path: QPs left before the next attempt, length of the current suspension
-    int cur = 0;                       // SQP_RTI: slot of the stage records that holds the QP iterate (fast_commit comment)
     int log_lo = step0 == 0 ? 0 : step0 + 1;
     if (step0 == 0) {
-        // acados initial guess: x_k = x0, u_k = 0, all multipliers / QP memory 0
-        const size_t tot = sws_doubles_per_instance<FT>(N, pb.solver_type == 0) - STATE_DOUBLES;
-        for (size_t e = lane; e < tot; e += WAVE) w.G1[e] = 0.0;      // G1 is the workspace base
-        if (lane < STATE_DOUBLES) w.state[lane] = 0.0;
-        fence();
-        for (int e = lane; e < (N + 1) * NX; e += WAVE) {
-            const int k = e / NX, i = e - k * NX;
-            w.G1[(size_t)k * (w.ld / 8) + O_X + i] = i < 6 ? P.q0[i] : P.qdot0[i - 6];
-        }
         if (lane < NX) sm.xhat[lane] = lane < 6 ? P.q0[lane] : P.qdot0[lane - 6];
         if (lane < NU) sm.u0[lane] = P.qdot0[lane];                   // u[:,0] = qdot_0 (simulator.py:81)
-        __builtin_amdgcn_s_waitcnt(0);                                // the initial iterate is in memory before the first pass reads it
-        fence();
+        initial_guess<FT>(pb, N);
         log_lo = uni(log_state(out, inst, T1, 0, log_lo));
     } else {
-        if (lane < NX) sm.xhat[lane] = w.state[lane];
-        lin_cost = unid(w.state[12]);
-        lin_valid = uni(w.state[25] != 0.0 ? 1 : 0) != 0;
-        fast[0] = uni((int)w.state[26]); fast[1] = uni((int)w.state[27]); cur = uni((int)w.state[28]);
+        if (lane < NX) sm.xhat[lane] = w.state[ST_Z + lane];
+        c.load(w.state);
         fence();
     }
+    const auto lin = [](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass(alpha, do_update, sqp_mult, slot); };
+    const auto search = [](int sqp_iter) { return line_search(sqp_iter); };
     for (int i = step0; i < step1; i++) {
-        int qp_iter = 0, status = 0, sqp_iter = 1;
-        double res4[4] = {0, 0, 0, 0};
-        double cost = lin_cost;
         const double t0 = wclock();
-        if (pb.solver_type == 1) {
-            // SQP_RTI: one linearisation, one QP, full step (mpc_core.h nlp_step)
-#ifdef MPCB_STREAM_SEQ_RES
-            if (!lin_valid) { lin_pass(0.0, false); __builtin_amdgcn_s_waitcnt(0); fence(); lin_cost = unid(nlp_res_pass<false>(nullptr)); }
-#else
-            if (!lin_valid) {
-                lin_pass(0.0, false); __builtin_amdgcn_s_waitcnt(0); fence();
-                double o5[5];
-                rti_items<true, false>(0, o5, cur);
-                lin_cost = unid(o5[0]);
-            }
-#endif
-            double nlp_prev[5];
-            const int qs = ipm_solve<FT>(pb.qp_iter_max, &qp_iter, fast, res_pending ? nlp_prev : nullptr, &cur);
-            if (res_pending) {
-                // cost and residual norms of step i-1, evaluated by this step's first pass
-                if (lane == 8) out.cost[sbase + i - 1] = nlp_prev[0];
-                if (lane >= 12 && lane < 16) out.residuals[(sbase + i - 1) * 4 + (lane - 12)] =
-                    lane == 12 ? nlp_prev[1] : (lane == 13 ? nlp_prev[2] : (lane == 14 ? nlp_prev[3] : nlp_prev[4]));
-                res_pending = false;
-            }
-#ifdef MPCB_SPROF
-            if (lane == 0) { w.state[32 + 5] += wclock() - t0; }
-#endif
-            const bool ok = qs == 0 || qs == 1;
-            if (!ok) status = 4;                                       // ACADOS_QP_FAILURE, iterate untouched
-            __builtin_amdgcn_s_waitcnt(0);
-            SPROF_T0(tl);
-#ifdef MPCB_STREAM_SEQ_RES
-            lin_pass(1.0, ok);
-#else
-            lin_pass(1.0, ok, false, cur);
-#endif
-            __builtin_amdgcn_s_waitcnt(0);                             // the records written lane by lane are complete before they are streamed
-            fence();
-            SPROF_ADD(8, tl);
-            SPROF_T0(tn);
-            if (i + 1 < step1) {
-                // the next step's first pass streams the same records: it evaluates the defect, cost and residuals there
-                res_pending = true;
-                if (lane < NX) sm.vec[3][lane] = sm.xhat[lane];        // the x_hat this QP was solved for
-            } else {
-#ifdef MPCB_STREAM_SEQ_RES
-                cost = unid(nlp_res_pass<false>(res4));                // last step of this launch / work item
-#else
-                double o5[5];
-                rti_items<true, false>(0, o5, cur);                    // last step of this launch / work item
-                cost = unid(o5[0]); res4[0] = o5[1]; res4[1] = o5[2]; res4[2] = o5[3]; res4[3] = o5[4];
-#endif
-            }
-            SPROF_ADD(9, tn);
-            lin_valid = true;
-        } else {
-            // full SQP (acados ocp_nlp_sqp restated, mpc_core.h nlp_step): linearise -> residuals / convergence test -> QP ->
-            // merit backtracking -> update; sqp_iter counts QPs
-            const double tol = P.tol, tol_eq = P.tol_eq, tol_in = P.tol_ineq, tol_co = P.tol_comp;
-            status = 2;                                                // ACADOS_MAXITER unless decided otherwise
-            double alpha = 0.0;
-            bool pending = false;                                      // a step (alpha) waits to be applied by the next linearisation
-            for (sqp_iter = 0; sqp_iter < pb.max_iter; sqp_iter++) {
-                if (pending || !lin_valid || sqp_iter == 0) {
-                    __builtin_amdgcn_s_waitcnt(0);
-                    lin_pass(alpha, pending, true);
-                    __builtin_amdgcn_s_waitcnt(0);
-                    fence();
-#ifdef MPCB_STREAM_SEQ_RES
-                    cost = unid(nlp_res_pass<true>(res4));
-                    res4[0] = unid(res4[0]); res4[1] = unid(res4[1]); res4[2] = unid(res4[2]); res4[3] = unid(res4[3]);
-#else
-                    double o5[5];
-                    rti_items<true, false, true>(0, o5);
-                    cost = unid(o5[0]); res4[0] = unid(o5[1]); res4[1] = unid(o5[2]); res4[2] = unid(o5[3]); res4[3] = unid(o5[4]);
-#endif
-                    pending = false;
-                    lin_valid = true;
-                }
-                if (res4[0] < tol && res4[1] < tol_eq && res4[2] < tol_in && res4[3] < tol_co) { status = 0; break; }
-                if (res4[0] != res4[0] || cost != cost) { status = 1; break; }
-                int it = 0;
-                const int qs = ipm_solve<FT>(pb.qp_iter_max, &it, fast);
-                qp_iter += it;
-                if (qs != 0 && qs != 1) { status = 4; break; }
-                __builtin_amdgcn_s_waitcnt(0);
-                fence();
-                alpha = pb.fixed_step ? 1.0 : line_search(sqp_iter);
-                pending = true;
-            }
-            if (pending) {   // max-iter exit: apply the last step; the residuals of the last check stay
-                __builtin_amdgcn_s_waitcnt(0);
-                lin_pass(alpha, true, true);
-                __builtin_amdgcn_s_waitcnt(0);
-                fence();
-#ifdef MPCB_STREAM_SEQ_RES
-                cost = unid(nlp_res_pass<true>(nullptr));
-#else
-                double o5[5];
-                rti_items<true, false, true>(0, o5);
-                cost = unid(o5[0]);
-#endif
-                lin_valid = true;
-            }
+        // the last step of this launch / work item forms its own norms; the others leave them to the next step's first pass
+        const bool defer = pb.solver_type == 1 && i + 1 < step1;
+        double nlp_prev[5];
+        const StepStats s = mpc_step<FT>(pb, c, lin, search, res_pending ? nlp_prev : nullptr, defer);
+        if (res_pending) {
+            // cost and residual norms of step i-1, evaluated by this step's first pass
+            if (lane == 8) out.cost[sbase + i - 1] = nlp_prev[0];
+            if (lane >= 12 && lane < 16) out.residuals[(sbase + i - 1) * 4 + (lane - 12)] =
+                lane == 12 ? nlp_prev[1] : (lane == 13 ? nlp_prev[2] : (lane == 14 ? nlp_prev[3] : nlp_prev[4]));
         }
-        lin_cost = cost;
-        __builtin_amdgcn_s_waitcnt(0);
-        fence();
+        res_pending = defer;
         const double t1 = wclock();
 #ifdef MPCB_SPROF
-        if (lane == 0) { w.state[32 + 6] += t1 - t0; }
+        if (lane == 0) { w.state[ST_PROF + 6] += t1 - t0; }
 #endif
         // u = solver.get(0,'u'); plant step (simulation_model.py:93-117)
         if (lane < 6) {
@@ -2497,14 +2277,14 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
             sm.u0[j] = u;
         }
         if (lane == 8) {
-            out.status[sbase + i] = status;
-            out.sqp_iter[sbase + i] = sqp_iter;
-            out.qp_iter[sbase + i] = qp_iter;
-            if (!res_pending) out.cost[sbase + i] = cost;
+            out.status[sbase + i] = s.status;
+            out.sqp_iter[sbase + i] = s.sqp_iter;
+            out.qp_iter[sbase + i] = s.qp_iter;
+            if (!res_pending) out.cost[sbase + i] = s.cost;
             out.solver_time[sbase + i] = t1 - t0;
         }
         if (!res_pending && lane >= 12 && lane < 16) out.residuals[(sbase + i) * 4 + (lane - 12)] =
-            lane == 12 ? res4[0] : (lane == 13 ? res4[1] : (lane == 14 ? res4[2] : res4[3]));
+            lane == 12 ? s.res4[0] : (lane == 13 ? s.res4[1] : (lane == 14 ? s.res4[2] : s.res4[3]));
         fence();
         if (lane < NX) sm.xhat[lane] = sm.logv[24 + lane];
         fence();
@@ -2512,175 +2292,55 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         const double t2 = wclock();
         if (lane == 0) out.plant_time[sbase + i] = t2 - t1;
 #ifdef MPCB_SPROF
-        if (lane == 0) { w.state[32 + 14] += t2 - t1; }
+        if (lane == 0) { w.state[ST_PROF + 14] += t2 - t1; }
 #endif
     }
     if (log_lo <= step1) log_flush(out, inst, T1, log_lo, step1);
-    if (lane < NX) w.state[lane] = sm.xhat[lane];
-    if (lane == 12) { w.state[12] = lin_cost; w.state[25] = lin_valid ? 1.0 : 0.0; w.state[26] = fast[0]; w.state[27] = fast[1]; w.state[28] = cur; }
+    c.store(w.state);
 }
 
 // Controller step (mpcb_step, mpc_stream_step.hip): ONE step of rollout<FT>'s loop for simulation `inst`, from the caller's state
-// io.xhat, with no plant and no logs.  The solver memory carries over in the workspace as between two rollout launches (w.state:
-// [12] lin_cost, [25] lin_valid, [26..27] fast, [28] cur; the x_0 merit weights [13..24] in place); `reset` starts from the acados
-// initial guess instead (the rollout's step 0).  Every step is the last of its launch: its cost and residual norms are formed by a
-// trailing pass here, not deferred to the next step's first pass (res_pending), since the caller reads them when the launch returns.
+// io.xhat, with no plant and no logs.  The solver memory carries over in the workspace as between two rollout launches (Carry); `reset`
+// starts from the acados initial guess instead (the rollout's step 0).  Every step is the last of its launch: its cost and residual
+// norms are never deferred to the next step's first pass, since the caller reads them when the launch returns.
 template <class FT>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
-    // ragged batch: this simulation's own horizon (the workspace stride is sized for the longest)
-    const double nh = params[inst].n_hor;
-    const int N = uni(nh > 0.0 ? (int)nh : pb.N), NMAX = pb.N;
-    {
-        const double *ps = reinterpret_cast<const double *>(params + inst);
-        double *pd = reinterpret_cast<double *>(&sm.P);
-        for (int e = lane; e < (int)(sizeof(InstParams) / sizeof(double)); e += WAVE) pd[e] = ps[e];
-        if (lane == 0) {
-            sm.rbp = rbp;
-            SWs ws = sws_carve<FT>(ws_base + (size_t)inst * ws_stride, N, pb.solver_type == 0);
-            ws.state = ws_base + (size_t)inst * ws_stride + (ws_stride - STATE_DOUBLES);
-            sm.w = ws;
-            sm.n_hor = N;
-        }
-    }
-    fence();
-    const InstParams &P = sm.P;
+    const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), NMAX = pb.N;
     const SWs w = sm.w;
-    bool lin_valid = false;
-    double lin_cost = 0.0;
-    int fast[2] = {0, 0};
-    int cur = 0;
-    if (uni(reset ? 1 : 0)) {
-        // acados initial guess: x_k = x0, u_k = 0, all multipliers / QP memory 0
-        const size_t tot = sws_doubles_per_instance<FT>(N, pb.solver_type == 0) - STATE_DOUBLES;
-        for (size_t e = lane; e < tot; e += WAVE) w.G1[e] = 0.0;      // G1 is the workspace base
-        if (lane < STATE_DOUBLES) w.state[lane] = 0.0;
-        fence();
-        for (int e = lane; e < (N + 1) * NX; e += WAVE) {
-            const int k = e / NX, i = e - k * NX;
-            w.G1[(size_t)k * (w.ld / 8) + O_X + i] = i < 6 ? P.q0[i] : P.qdot0[i - 6];
-        }
-        __builtin_amdgcn_s_waitcnt(0);                                // the initial iterate is in memory before the first pass reads it
-        fence();
-    } else {
-        lin_cost = unid(w.state[12]);
-        lin_valid = uni(w.state[25] != 0.0 ? 1 : 0) != 0;
-        fast[0] = uni((int)w.state[26]); fast[1] = uni((int)w.state[27]); cur = uni((int)w.state[28]);
-    }
+    Carry c;
+    if (uni(reset ? 1 : 0)) initial_guess<FT>(pb, N);
+    else c.load(w.state);
     // a new task reference: the carried linearisation was formed against the old one -- linearise again (everything else carries).
     // The reference rows are strided by the batch's longest horizon; rows past this simulation's own are never read.
-    if (io.ref_changed) lin_valid = false;
+    if (io.ref_changed) c.lin_valid = false;
     const TaskRef ref{io.yref ? io.yref + (size_t)inst * NMAX * NTASK : nullptr};
-    // (without a reference the passes of the packed g_ref: the step of mpcb_step as it was)
+    // (without a reference the passes of the packed g_ref: the rollout's)
     const auto lin = [&](double alpha, bool do_update, bool sqp_mult, int slot) {
         if (ref.y) lin_pass<true>(alpha, do_update, sqp_mult, slot, ref);
         else lin_pass(alpha, do_update, sqp_mult, slot);
     };
+    const auto search = [&](int sqp_iter) { return ref.y ? line_search<true>(sqp_iter, ref) : line_search(sqp_iter); };
     if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
     fence();
-    int qp_iter = 0, status = 0, sqp_iter = 1;
-    double res4[4] = {0, 0, 0, 0};
-    double cost = lin_cost;
     const double t0 = wclock();
-    if (pb.solver_type == 1) {
-        // SQP_RTI: one linearisation, one QP, full step -- rollout<FT>'s step with res_pending false on entry and on exit
-#ifdef MPCB_STREAM_SEQ_RES
-        if (!lin_valid) { lin(0.0, false, false, -1); __builtin_amdgcn_s_waitcnt(0); fence(); lin_cost = unid(nlp_res_pass<false>(nullptr)); }
-#else
-        if (!lin_valid) {
-            lin(0.0, false, false, -1); __builtin_amdgcn_s_waitcnt(0); fence();
-            double o5[5];
-            rti_items<true, false>(0, o5, cur);
-            lin_cost = unid(o5[0]);
-        }
-#endif
-        const int qs = ipm_solve<FT>(pb.qp_iter_max, &qp_iter, fast, nullptr, &cur);
-        const bool ok = qs == 0 || qs == 1;
-        if (!ok) status = 4;                                           // ACADOS_QP_FAILURE, iterate untouched
-        __builtin_amdgcn_s_waitcnt(0);
-#ifdef MPCB_STREAM_SEQ_RES
-        lin(1.0, ok, false, -1);
-#else
-        lin(1.0, ok, false, cur);
-#endif
-        __builtin_amdgcn_s_waitcnt(0);                                 // the records written lane by lane are complete before they are streamed
-        fence();
-#ifdef MPCB_STREAM_SEQ_RES
-        cost = unid(nlp_res_pass<false>(res4));
-#else
-        double o5[5];
-        rti_items<true, false>(0, o5, cur);                            // the caller reads the norms when this launch returns
-        cost = unid(o5[0]); res4[0] = o5[1]; res4[1] = o5[2]; res4[2] = o5[3]; res4[3] = o5[4];
-#endif
-        lin_valid = true;
-    } else {
-        // full SQP: rollout<FT>'s step as it stands (its norms are never deferred)
-        const double tol = P.tol, tol_eq = P.tol_eq, tol_in = P.tol_ineq, tol_co = P.tol_comp;
-        status = 2;
-        double alpha = 0.0;
-        bool pending = false;
-        for (sqp_iter = 0; sqp_iter < pb.max_iter; sqp_iter++) {
-            if (pending || !lin_valid || sqp_iter == 0) {
-                __builtin_amdgcn_s_waitcnt(0);
-                lin(alpha, pending, true, -1);
-                __builtin_amdgcn_s_waitcnt(0);
-                fence();
-#ifdef MPCB_STREAM_SEQ_RES
-                cost = unid(nlp_res_pass<true>(res4));
-                res4[0] = unid(res4[0]); res4[1] = unid(res4[1]); res4[2] = unid(res4[2]); res4[3] = unid(res4[3]);
-#else
-                double o5[5];
-                rti_items<true, false, true>(0, o5);
-                cost = unid(o5[0]); res4[0] = unid(o5[1]); res4[1] = unid(o5[2]); res4[2] = unid(o5[3]); res4[3] = unid(o5[4]);
-#endif
-                pending = false;
-                lin_valid = true;
-            }
-            if (res4[0] < tol && res4[1] < tol_eq && res4[2] < tol_in && res4[3] < tol_co) { status = 0; break; }
-            if (res4[0] != res4[0] || cost != cost) { status = 1; break; }
-            int it = 0;
-            const int qs = ipm_solve<FT>(pb.qp_iter_max, &it, fast);
-            qp_iter += it;
-            if (qs != 0 && qs != 1) { status = 4; break; }
-            __builtin_amdgcn_s_waitcnt(0);
-            fence();
-            alpha = pb.fixed_step ? 1.0 : (ref.y ? line_search<true>(sqp_iter, ref) : line_search(sqp_iter));
-            pending = true;
-        }
-        if (pending) {   // max-iter exit: apply the last step; the residuals of the last check stay
-            __builtin_amdgcn_s_waitcnt(0);
-            lin(alpha, true, true, -1);
-            __builtin_amdgcn_s_waitcnt(0);
-            fence();
-#ifdef MPCB_STREAM_SEQ_RES
-            cost = unid(nlp_res_pass<true>(nullptr));
-#else
-            double o5[5];
-            rti_items<true, false, true>(0, o5);
-            cost = unid(o5[0]);
-#endif
-            lin_valid = true;
-        }
-    }
-    lin_cost = cost;
-    __builtin_amdgcn_s_waitcnt(0);
-    fence();
+    const StepStats s = mpc_step<FT>(pb, c, lin, search, nullptr, false);
     const double t1 = wclock();
     // solver.get(0,'u') and the step's statistics.  The NLP iterate lives in G1 [X | U] whichever slot `cur` names (that is the QP
     // iterate's: the step lin_pass has just applied).
     if (lane < NU) io.u0[(size_t)inst * NU + lane] = w.G1[O_U + lane];
     if (lane == 8) {
-        io.status[inst] = status;
-        io.sqp_iter[inst] = sqp_iter;
-        io.qp_iter[inst] = qp_iter;
-        io.cost[inst] = cost;
+        io.status[inst] = s.status;
+        io.sqp_iter[inst] = s.sqp_iter;
+        io.qp_iter[inst] = s.qp_iter;
+        io.cost[inst] = s.cost;
         io.solver_time[inst] = t1 - t0;
     }
     if (lane >= 12 && lane < 16) io.residuals[(size_t)inst * 4 + (lane - 12)] =
-        lane == 12 ? res4[0] : (lane == 13 ? res4[1] : (lane == 14 ? res4[2] : res4[3]));
+        lane == 12 ? s.res4[0] : (lane == 13 ? s.res4[1] : (lane == 14 ? s.res4[2] : s.res4[3]));
     // the predicted trajectory x_0..x_N, u_0..u_{N-1} (orc_solver_get_iterate), in rows sized for the longest horizon of the batch: the
     // rows beyond this simulation's own horizon are NaN, so that nothing stale passes for a prediction
     const int LD = w.ld / 8;
@@ -2698,8 +2358,7 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
             up[e] = k < N ? w.G1[(size_t)k * LD + O_U + j] : __builtin_nan("");
         }
     }
-    if (lane < NX) w.state[lane] = sm.xhat[lane];
-    if (lane == 12) { w.state[12] = lin_cost; w.state[25] = lin_valid ? 1.0 : 0.0; w.state[26] = fast[0]; w.state[27] = fast[1]; w.state[28] = cur; }
+    c.store(w.state);
 }
 #endif  // __HIP_DEVICE_COMPILE__
 
