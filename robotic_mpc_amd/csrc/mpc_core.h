@@ -31,6 +31,7 @@
 #pragma once
 #include "mpc_kin.h"
 #include "mpc_ipm.h"
+#include "mpc_nlp.h"
 
 // 16-way manual unrolling with individually named registers (see Engine::copy_lanes)
 #define MPC_REP16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
@@ -51,7 +52,6 @@ constexpr int L2N = 62;
 // (912 B = 3 x 256 + 9 x 16: sixteen consecutive stages fall on sixteen different 16-byte bank groups)
 constexpr int L2W = 114;
 
-#define NLP_PASS nlp_direct
 // 1 (default): SQP_RTI folds the fast path's commit and right-hand-side item passes into the NLP pass; 0: separate passes (A/B builds)
 #ifndef MPCB_FUSE
 #define MPCB_FUSE 1
@@ -423,32 +423,6 @@ struct Engine {
     // Jacobian per stage (lane <-> stage), dynamics defect, cost = sum_k dt/2 r'Wr (acados
     // get_cost(), simulator.py:221) -- and evaluates acados' ocp_nlp_res_compute inf-norms
     // [stat, eq, ineq, comp] with the NLP multipliers (RTI: the QP's; SQP: the blended ones).
-    // One joint of the plant step (simulation_model.py:93-117): Euler / RK2 (midpoint) / RK3 / RK4 of z' = [qdot; -W (qdot - u)]
-    MPC_HD static void plant_rk(const InstParams &P, int j, double q, double v, double u, double &qn, double &vn)
-    {
-        const double wc = P.wcv[j], dt = P.dt;
-        const int integ = (int)P.integ;
-        const double k1q = v, k1v = -wc * v + wc * u;
-        const double v2 = v + 0.5 * dt * k1v;
-        const double k2q = v2, k2v = -wc * v2 + wc * u;
-        if (integ == 1) {
-            qn = q + dt * k1q; vn = v + dt * k1v;
-        } else if (integ == 2) {
-            qn = q + dt * k2q; vn = v + dt * k2v;
-        } else if (integ == 3) {
-            const double v3 = v - dt * k1v + 2.0 * dt * k2v;
-            const double k3q = v3, k3v = -wc * v3 + wc * u;
-            qn = q + (dt / 6) * (k1q + 4.0 * k2q + k3q); vn = v + (dt / 6) * (k1v + 4.0 * k2v + k3v);
-        } else {
-            const double v3 = v + 0.5 * dt * k2v;
-            const double k3q = v3, k3v = -wc * v3 + wc * u;
-            const double v4 = v + dt * k3v;
-            const double k4q = v4, k4v = -wc * v4 + wc * u;
-            qn = q + (dt / 6) * k1q + (dt / 3) * k2q + (dt / 3) * k3q + (dt / 6) * k4q;
-            vn = v + (dt / 6) * k1v + (dt / 3) * k2v + (dt / 3) * k3v + (dt / 6) * k4v;
-        }
-    }
-
     // Item-parallel (any horizon): the iterate is updated IN PLACE in HBM by 16-byte items, every
     // lane linearises one stage from operands it loads itself, and the residual norms are joint items (u_j, q_j, v_j together) --
     // no staging of the 96-column iterate record through LDS (81 KB per pass at N = 100), no copy-back.  The linearisation records
@@ -662,7 +636,7 @@ struct Engine {
                     double zn[12];
                     for (int j = 0; j < 6; j++) {
                         const double u = gld(G1 + O_U + j);                 // (stage 0, after the update above)
-                        plant_rk(P, j, sm.xhat[j], sm.xhat[6 + j], u, zn[j], zn[6 + j]);
+                        nlp::plant_rk(P, j, sm.xhat[j], sm.xhat[6 + j], u, zn[j], zn[6 + j]);
                         sm.u0[j] = u;
                         sm.logv[24 + j] = zn[j]; sm.logv[30 + j] = zn[6 + j];
                     }
@@ -2699,6 +2673,47 @@ struct Engine {
     }
 
     // =========================================================================== IPM driver
+    // The four families of solve sweeps, by where the Riccati factor of the horizon lives while they run: the first that holds,
+    // the chunked streaming sweeps when none does.  Decided once per QP; the three routers below are the only callers of the sweeps
+    // and the only place that spells their template arguments.  (Flags, not an enumeration: a family that a geometry never takes is
+    // a compile-time `false` here, and its sweeps are then not instantiated for that geometry.)
+    struct Sweeps {
+        bool res;    // the horizon's factor fits the LDS pool: resident sweeps
+        bool reg;    // no room in LDS (half a pool, or a long horizon): segment by segment with K in registers, the rest straight from HBM
+        bool seg;    // a segment of the factor fits (whole pool of a CU): segment-resident sweeps
+    };
+    MPC_HD Sweeps sweep_family() const
+    {
+        const bool res = resident_ok(), reg = reg_ok();
+        return Sweeps{res, reg, !reg && segment_ok()};
+    }
+    // factorisation sweep: fact_pass_t<MODE>, 1 leaves the factor resident in LDS, 2 serves the segmented families, 0 streams
+    MPC_HD void factorise(const Sweeps &sw)
+    {
+        if (sw.res) fact_pass_t<1>();
+        else if (sw.reg || sw.seg) fact_pass_t<2>();
+        else fact_pass_t<0>();
+    }
+    // forward sweep + step lengths; returns the step length (FAST: > 0.5 where the fast path's candidate is accepted).
+    // AFFINE: the predictor (also forms the centering sums), FAST: the fast path's candidate.  fwd_resident<AFFINE, SEG, KREG, FAST>:
+    // SEG = one segment of the factor at a time, KREG = that segment's K in registers.
+    template <bool AFFINE, bool FAST = false>
+    MPC_HD double forward_sweep(const Sweeps &sw)
+    {
+        if (sw.res) return fwd_resident<AFFINE, false, false, FAST>();
+        if (sw.reg) return fwd_resident<AFFINE, true, true, FAST>();
+        if (sw.seg) return fwd_resident<AFFINE, true, false, FAST>();
+        return forward_step_pass<AFFINE, FAST>();
+    }
+    // centering corrector + backward solve: corr_resident<SEG, KREG> as above
+    MPC_HD void corrector(const Sweeps &sw, double sigma_mu)
+    {
+        if (sw.res) corr_resident<false, false>(sigma_mu);
+        else if (sw.reg) corr_resident<true, true>(sigma_mu);
+        else if (sw.seg) corr_resident<true, false>(sigma_mu);
+        else corrector_bwd_pass(sigma_mu);
+    }
+
     // Restates HPIPM's d_ocp_qp_ipm_solve main loop (see oracle/mpc_oracle.c ipm_solve).
     // Returns HPIPM status 0 ok / 1 max-iter / 2 min-step / 3 NaN.
     // `defer_commit` (SQP_RTI): an accepted fast-path candidate is left in the Newton-step slots with commit_pending set; the NLP pass
@@ -2707,11 +2722,9 @@ struct Engine {
     {
         const double tol = ex.smem().P.qp_tol;
         Smem &sm = ex.smem();
-        const bool res = resident_ok();   // the horizon's factor fits the LDS pool: resident sweeps
-        const bool reg = reg_ok();        // no room in LDS (half a pool, or a long horizon): the factor in registers / straight from HBM
-        const bool seg = !reg && segment_ok();    // a segment of the factor fits (whole pool of a CU): segment-resident sweeps
+        const Sweeps sw = sweep_family();
 #ifdef MPC_EMU_TRACE
-        { static int once = 0; if (!once) { once = 1; fprintf(stderr, "[emu] res %d reg %d seg %d pool %d\n", (int)res, (int)reg, (int)seg, (int)ex.smem().pool_n); } }
+        { static int once = 0; if (!once) { once = 1; fprintf(stderr, "[emu] res %d reg %d seg %d pool %d\n", (int)sw.res, (int)sw.reg, (int)sw.seg, (int)ex.smem().pool_n); } }
 #endif
         // bound-inactive fast path first (mpc_ipm.h; oracle solve_qp): `iters_out` counts Riccati factorisations
         int tried = 0;
@@ -2721,11 +2734,8 @@ struct Engine {
                 tried = 1;
                 if (!rhs_valid) fast_rhs();   // (SQP_RTI: normally formed by the previous step's NLP pass, nlp_direct want_rhs)
                 rhs_valid = false;
-                double ok;
-                if (res) { fact_pass_t<1>(); ok = fwd_resident<false, false, false, true>(); }
-                else if (reg) { fact_pass_t<2>(); ok = fwd_resident<false, true, true, true>(); }
-                else if (seg) { fact_pass_t<2>(); ok = fwd_resident<false, true, false, true>(); }
-                else { fact_pass_t<0>(); ok = forward_step_pass<false, true>(); }
+                factorise(sw);
+                const double ok = forward_sweep<false, true>(sw);
                 if (ex.uni(ok > 0.5)) {
                     if (defer_commit) commit_pending = true;
                     else fast_commit();
@@ -2748,42 +2758,22 @@ struct Engine {
         double alpha = 1.0;
         for (;; it++) {
             // every lane holds the same scalars; the decision is made uniform explicitly (scalar branch)
-            const double n0 = sm.ret[0], n1 = sm.ret[1], n2 = sm.ret[2], n3 = sm.ret[3];
-            int stop = -1;
-            if (n0 != n0 || n1 != n1 || n2 != n2 || n3 != n3) stop = 3;
-            else if (!(n0 > tol || n1 > tol || n2 > tol || n3 > tol)) stop = 0;
-            else if (it >= c.pb->qp_iter_max) stop = 1;
-            else if (!(alpha > 1e-12)) stop = 2;
-            stop = ex.uni(stop);
+            int stop = ex.uni(ipm::stop_test(sm.ret[0], sm.ret[1], sm.ret[2], sm.ret[3], tol, it, c.pb->qp_iter_max, alpha));
 #ifdef MPCB_DIAG_FIXED_IT   // timing-only diagnostic builds: the same work whatever the (possibly knocked-out) arithmetic
             stop = it >= MPCB_DIAG_FIXED_IT ? 0 : -1;
 #endif
             if (stop >= 0) { status = stop; break; }
             const bool has_bounds = ex.uni(nc > 0);
-            double a_aff;
-            if (res) {
-                fact_pass_t<1>();
-                a_aff = has_bounds ? fwd_resident<true, false>() : fwd_resident<false, false>();
-            } else if (reg) {
-                fact_pass_t<2>();
-                a_aff = has_bounds ? fwd_resident<true, true, true>() : fwd_resident<false, true, true>();
-            } else if (seg) {
-                fact_pass_t<2>();
-                a_aff = has_bounds ? fwd_resident<true, true>() : fwd_resident<false, true>();
-            } else {
-                fact_pass_t<0>();
-                a_aff = has_bounds ? forward_step_pass<true>() : forward_step_pass<false>();
-            }
+            factorise(sw);
+            const double a_aff = has_bounds ? forward_sweep<true>(sw) : forward_sweep<false>(sw);
             if (has_bounds) {
-                const bool rs = res || seg || reg;
+                const bool rs = sw.res || sw.seg || sw.reg;    // (their sweeps leave the centering sums in sm.cen)
                 const double S0 = rs ? ex.uni(sm.cen[1]) : ex.get1(sm.red[1]), S1 = rs ? ex.uni(sm.cen[2]) : ex.get1(sm.red[2]),
                              S2 = rs ? ex.uni(sm.cen[3]) : ex.get1(sm.red[3]);
                 const double mu_aff = (S0 + a_aff * (S1 + a_aff * S2)) / nc;
                 const double sigma = ipm::sigma(mu_aff, mu);
-                if (res) { corr_resident<false>(sigma * mu); alpha = fwd_resident<false, false>(); }
-                else if (reg) { corr_resident<true, true>(sigma * mu); alpha = fwd_resident<false, true, true>(); }
-                else if (seg) { corr_resident<true>(sigma * mu); alpha = fwd_resident<false, true>(); }
-                else { corrector_bwd_pass(sigma * mu); alpha = forward_step_pass<false>(); }
+                corrector(sw, sigma * mu);
+                alpha = forward_sweep<false>(sw);
             } else {
                 alpha = a_aff;
             }
@@ -2848,7 +2838,7 @@ struct Engine {
                         const double *r1 = v1 + (size_t)s * L1;
                         const double a = i < 12 ? fabs(r1[O_QPI + i]) : fabs(r1[O_QLAM + i - 12]);
                         double *mw = vm + (size_t)s * LMW + i;
-                        *mw = sqp_iter == 0 ? a : fmax(a, 0.5 * (*mw + a));
+                        *mw = nlp::merit_weight(sqp_iter, *mw, a);
                     }
                 });
                 copy_rect<WMW, O_MW, W5, LMW, false>(vm, ex.smem().w.G5, k0, k1);
@@ -2876,39 +2866,16 @@ struct Engine {
 #pragma unroll
                         for (int i = 0; i < 6; i++) uu[i] = r1[O_U + i] + alpha * r1[O_QW + i];
                         task_lin<false, double *, REF>(rb, P, xx, xx + 6, rec, rec);
-                        double s = 0.0;
+                        const auto xnext = [&](int i) { return rn[O_X + i] + alpha * rn[O_QW + 6 + i]; };
                         if constexpr (REF) {
                             double t[NTASK];
                             task_targets(ref, k, t);
-#pragma unroll
-                            for (int i = 0; i < NTASK; i++) {
-                                const double r = rec[O_R + i] - t[i];
-                                s += P.w_task[i] * r * r;
-                            }
+                            nlp::merit_stage(acc, P, xx, uu, [&](int i) { return rec[O_R + i] - t[i]; }, xnext, mw, k);
                         } else {
-#pragma unroll
-                        for (int i = 0; i < NTASK; i++) s += P.w_task[i] * rec[O_R + i] * rec[O_R + i];
+                            nlp::merit_stage(acc, P, xx, uu, [&](int i) { return rec[O_R + i]; }, xnext, mw, k);
                         }
-#pragma unroll
-                        for (int j = 0; j < 6; j++) {
-                            const double qdd = P.cq[j] * (uu[j] - xx[6 + j]);
-                            s += 2.0 * P.w_u * uu[j] * uu[j] + P.w_qddot * qdd * qdd;
-                            const double xnq = rn[O_X + j] + alpha * rn[O_QW + 6 + j];
-                            const double xnv = rn[O_X + 6 + j] + alpha * rn[O_QW + 12 + j];
-                            acc += mw[j] * fabs((xx[j] + P.a12[j] * xx[6 + j] + P.b1[j] * uu[j]) - xnq);
-                            acc += mw[6 + j] * fabs((P.a22[j] * xx[6 + j] + P.b2[j] * uu[j]) - xnv);
-                            // branch-free (every lane-dependent branch costs a saved exec mask: this phase ran out of SGPRs)
-                            const double vl = P.umin[j] - uu[j], vu = uu[j] - P.umax[j];
-                            acc += mw[12 + j] * fmax(vl, 0.0) + mw[24 + j] * fmax(vu, 0.0);
-                            const double ql = P.qmin[j] - xx[j], qu = xx[j] - P.qmax[j], on = k >= 1 ? 1.0 : 0.0;
-                            acc += on * (mw[18 + j] * fmax(ql, 0.0) + mw[30 + j] * fmax(qu, 0.0));
-                        }
-                        acc += 0.5 * P.dt * s;
                     }
-                    if (k == 0) {
-#pragma unroll
-                        for (int i = 0; i < 12; i++) acc += sm.w.state[13 + i] * fabs(sm.xhat[i] - xx[i]);
-                    }
+                    if (k == 0) nlp::merit_x0(acc, sm.w.state + ST_X0_MW, sm.xhat, xx);
                 }
                 }
                 ex.put_wsum(sm.red[0], lane_, acc);     // one partial per wavefront: a trial point's are consecutive
@@ -2930,70 +2897,34 @@ struct Engine {
         Smem &sm = ex.smem();
         ex.par([&](int lane) {
             if (lane < NX) {
-                const InstParams &P = sm.P;
                 const double *r1 = ex.smem().w.G1, *r2 = ex.smem().w.G2;  // stage 0 records in HBM (y holds W(r + G delta))
-                double v;
-                if (lane < 6) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int i = 0; i < NTASK; i++) s += r2[O_GQ + i * 6 + lane] * r2[O_Y + i];
-                    v = P.dt * s + r1[O_QPI + lane] + P.dt * P.lm * r1[O_QW + 6 + lane];
-                } else {
-                    const int jj = lane - 6;
-                    const double uj = r1[O_U + jj] + r1[O_QW + jj], vj = r1[O_X + 6 + jj] + r1[O_QW + 12 + jj];
-                    const double c2 = P.w_qddot * P.cq[jj] * P.cq[jj];
-                    v = P.dt * (r2[O_GV + jj] * r2[O_Y + 4] + c2 * (vj - uj)) + P.a12[jj] * r1[O_QPI + jj] +
-                        P.a22[jj] * r1[O_QPI + 6 + jj] + P.dt * P.lm * r1[O_QW + 12 + jj];
-                }
-                const double a = fabs(v);
-                double *mw = &ex.smem().w.state[13 + lane];
-                *mw = sqp_iter == 0 ? a : fmax(a, 0.5 * (*mw + a));
+                const double a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2));
+                double *mw = &ex.smem().w.state[ST_X0_MW + lane];
+                *mw = nlp::merit_weight(sqp_iter, *mw, a);
             }
         });
     }
 
-    // MERIT_BACKTRACKING (trajectory_optimizer.py:68; acados alpha_reduction 0.7, alpha_min 0.05)
-    MPC_HD double line_search(int sqp_iter)
+    // MERIT_BACKTRACKING (nlp::LS_REDUCTION, LS_ALPHA_MIN).  REF (the controller step): against the task reference `ref`.
+    template <bool REF = false>
+    MPC_HD double line_search(int sqp_iter, TaskRef ref = TaskRef{nullptr})
     {
         update_x0_weights(sqp_iter);
         const int G = merit_groups();
         // the backtracking sequence is fixed (1, 0.7, 0.49, ...): G trial points per pass, the reference point 0 in the first
         double al[MERIT_MAX], m[MERIT_MAX], m0 = 0.0, alpha = 1.0;
         bool first = true;
-        while (alpha >= 0.05) {
+        while (alpha >= nlp::LS_ALPHA_MIN) {
             int na = 0;
             if (first) al[na++] = 0.0;
             double a = alpha;
-            while (na < G && a >= 0.05) { al[na++] = a; a *= 0.7; }
-            merit_pass(al, na, first, sqp_iter, m);
+            while (na < G && a >= nlp::LS_ALPHA_MIN) { al[na++] = a; a *= nlp::LS_REDUCTION; }
+            merit_pass<REF>(al, na, first, sqp_iter, m, ref);
             int j = 0;
             if (first) { m0 = m[0]; j = 1; first = false; }
             for (; j < na; j++) {
                 if (ex.uni(m[j] < m0)) return al[j];
-                alpha = al[j] * 0.7;
-            }
-        }
-        return alpha;
-    }
-    // ... and the controller step's, against the task reference `ref`
-    MPC_HD double line_search(int sqp_iter, TaskRef ref)
-    {
-        update_x0_weights(sqp_iter);
-        const int G = merit_groups();
-        // the backtracking sequence is fixed (1, 0.7, 0.49, ...): G trial points per pass, the reference point 0 in the first
-        double al[MERIT_MAX], m[MERIT_MAX], m0 = 0.0, alpha = 1.0;
-        bool first = true;
-        while (alpha >= 0.05) {
-            int na = 0;
-            if (first) al[na++] = 0.0;
-            double a = alpha;
-            while (na < G && a >= 0.05) { al[na++] = a; a *= 0.7; }
-            merit_pass<true>(al, na, first, sqp_iter, m, ref);
-            int j = 0;
-            if (first) { m0 = m[0]; j = 1; first = false; }
-            for (; j < na; j++) {
-                if (ex.uni(m[j] < m0)) return al[j];
-                alpha = al[j] * 0.7;
+                alpha = al[j] * nlp::LS_REDUCTION;
             }
         }
         return alpha;
@@ -3005,18 +2936,13 @@ struct Engine {
     // `plant_done` (out): the plant step and the log of the new state were done inside the last NLP pass (SQP_RTI)
     // PLANT = false (control_step: the caller owns the plant): the last NLP pass of SQP_RTI runs no plant lane and forms no fast-path
     // right-hand side -- there is no next state to form it for; the next step's QP forms it itself (ipm_solve, !rhs_valid).
-    // The controller step's passes (PLANT = false) also form the task residuals against the caller's task reference `ref` (REF
-    // instantiations of nlp_direct / merit_pass); the rollout's keep the packed g_ref.
-    template <bool PLANT = true>
-    MPC_HD int nlp_step(bool &lin_valid, int *sqp_iter_out, int *qp_iter_out, double *res4, double *cost_out, bool *plant_done,
-                        TaskRef ref = TaskRef{nullptr})
+    // The callers bring their NLP pass and line search, as those of se::mpc_step do -- `lin(alpha, do_update, sqp_mult, res4, do_plant,
+    // fuse_commit, want_rhs)`: nlp_direct, `search(sqp_iter)`: line_search; the rollout's keep the packed g_ref, the controller
+    // step's are the REF instantiations against the caller's task reference when there is one.
+    template <bool PLANT, class Lin, class Search>
+    MPC_HD int nlp_step(bool &lin_valid, int *sqp_iter_out, int *qp_iter_out, double *res4, double *cost_out, bool *plant_done, Lin &&lin,
+                        Search &&search)
     {
-        constexpr bool REF = !PLANT;
-        // (without a reference the controller step runs the passes of the packed g_ref: the step of mpcb_step as it was)
-        const auto ctl_pass = [&](double alpha, bool do_update, bool sqp_mult, double *r4, bool fuse_commit) {
-            if (ex.uni(ref.y != nullptr)) return nlp_direct<true>(alpha, do_update, sqp_mult, r4, false, fuse_commit, false, ref);
-            return NLP_PASS(alpha, do_update, sqp_mult, r4, false, fuse_commit, false);
-        };
         *plant_done = false;
         PROF_T0(t0);
         int status = 0, sqp_iter = 0, qp_iter = 0, it = 0;
@@ -3024,8 +2950,7 @@ struct Engine {
         if (c.pb->solver_type == 1) {
             // SQP_RTI: one linearisation, one QP, full step
             if (!lin_valid) {
-                if constexpr (REF) cost = ctl_pass(0.0, false, false, nullptr, false);
-                else cost = NLP_PASS(0.0, false, false, nullptr);
+                cost = lin(0.0, false, false, nullptr, false, false, false);
                 rhs_valid = false;
             }
             commit_pending = false;
@@ -3037,15 +2962,10 @@ struct Engine {
             // residuals / cost are evaluated at the new iterate (acados get_residuals() for RTI,
             // get_cost()); this linearisation is reused by the next solve() call -- and so is the fast path's right-hand side,
             // formed by the same pass when the next QP will try the fast path (ipm_solve: fast_off == 0 and no suspension left)
-            if constexpr (PLANT) {
-                const bool next_fast = ex.uni(MPCB_FUSE != 0 && ex.smem().P.fast_off == 0.0 && fast_skip == 0);
-                cost = NLP_PASS(1.0, ok, false, res4, true, commit_pending, next_fast);
-                rhs_valid = next_fast;
-                *plant_done = true;
-            } else {
-                cost = ctl_pass(1.0, ok, false, res4, commit_pending);
-                rhs_valid = false;
-            }
+            const bool next_fast = PLANT && ex.uni(MPCB_FUSE != 0 && ex.smem().P.fast_off == 0.0 && fast_skip == 0);
+            cost = lin(1.0, ok, false, res4, PLANT, commit_pending, next_fast);
+            rhs_valid = next_fast;
+            *plant_done = PLANT;
             commit_pending = false;
             lin_valid = true;
         } else {
@@ -3055,8 +2975,7 @@ struct Engine {
             bool pending = false;  // a step (alpha) waits to be applied by the next nlp_pass
             for (sqp_iter = 0; sqp_iter < c.pb->max_iter; sqp_iter++) {
                 if (pending || !lin_valid || sqp_iter == 0) {
-                    if constexpr (REF) cost = ctl_pass(alpha, pending, true, res4, false);
-                    else cost = NLP_PASS(alpha, pending, true, res4);
+                    cost = lin(alpha, pending, true, res4, false, false, false);
                     pending = false;
                     lin_valid = true;
                 }
@@ -3065,13 +2984,11 @@ struct Engine {
                 const int qs = ipm_solve(&it);
                 qp_iter += it;
                 if (qs != 0 && qs != 1) { status = 4; break; }
-                if constexpr (REF) alpha = c.pb->fixed_step ? 1.0 : ex.uni(ref.y != nullptr) ? line_search(sqp_iter, ref) : line_search(sqp_iter);
-                else alpha = c.pb->fixed_step ? 1.0 : line_search(sqp_iter);
+                alpha = c.pb->fixed_step ? 1.0 : search(sqp_iter);
                 pending = true;
             }
             if (pending) {   // max-iter exit: residuals of the last check stay
-                if constexpr (REF) cost = ctl_pass(alpha, true, true, nullptr, false);
-                else cost = NLP_PASS(alpha, true, true, nullptr);
+                cost = lin(alpha, true, true, nullptr, false, false, false);
                 lin_valid = true;
             }
         }
@@ -3099,16 +3016,20 @@ struct Engine {
             log_lo = ex.uni(log_state(out, inst, 0, log_lo, false));
         } else {
             ex.par([&](int lane) {
-                if (lane < NX) sm.xhat[lane] = w.state[lane];
+                if (lane < NX) sm.xhat[lane] = w.state[ST_Z + lane];
             });
             load_carry(lin_valid);
         }
+        const auto lin = [&](double alpha, bool do_update, bool sqp_mult, double *r4, bool do_plant, bool fuse_commit, bool want_rhs) {
+            return nlp_direct(alpha, do_update, sqp_mult, r4, do_plant, fuse_commit, want_rhs);
+        };
+        const auto search = [&](int sqp_iter) { return line_search(sqp_iter); };
         for (int i = step0; i < step1; i++) {
             int sqp_iter = 0, qp_iter = 0;
             double res4[4] = {0, 0, 0, 0}, cost = 0.0;
             const double t0 = ex.clock();
             bool plant_done = false;
-            const int status = nlp_step(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done);
+            const int status = nlp_step<true>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
             const double t1 = ex.clock();
             PROF_T0(tp);
             // u = solver.get(0,'u'); RK4 plant step (simulation_model.py:111-117) -- unless the last NLP pass has done it
@@ -3117,23 +3038,16 @@ struct Engine {
                     const int j = lane;
                     const double u = w.G1[O_U + j];
                     double qn, vn;
-                    plant_rk(P, j, sm.xhat[j], sm.xhat[6 + j], u, qn, vn);
+                    nlp::plant_rk(P, j, sm.xhat[j], sm.xhat[6 + j], u, qn, vn);
                     sm.logv[24 + j] = qn;
                     sm.logv[30 + j] = vn;
                     sm.u0[j] = u;
                 }
-                if (lane == 8) {
-                    out.status[sb + i] = status;
-                    out.sqp_iter[sb + i] = sqp_iter;
-                    out.qp_iter[sb + i] = qp_iter;
-                    out.cost[sb + i] = cost;
-                    // (SQP_RTI: the plant step and its log ran on a spare lane INSIDE the last NLP pass, i.e. inside [t0, t1]: its time is
-                    // reported as plant_time and taken out here, so that solver_time is the solve alone -- acados time_tot,
-                    // simulator.py:220 -- and the two columns do not count the same microseconds twice)
-                    out.solver_time[sb + i] = (t1 - t0) - (plant_done ? sm.ret[6] : 0.0);
-                }
-                if (lane >= 12 && lane < 16) out.residuals[(sb + i) * 4 + (lane - 12)] =
-                    lane == 12 ? res4[0] : (lane == 13 ? res4[1] : (lane == 14 ? res4[2] : res4[3]));
+                // (SQP_RTI: the plant step and its log ran on a spare lane INSIDE the last NLP pass, i.e. inside [t0, t1]: its time is
+                // reported as plant_time and taken out here, so that solver_time is the solve alone -- acados time_tot,
+                // simulator.py:220 -- and the two columns do not count the same microseconds twice)
+                nlp::put_solve(out, sb + i, lane, status, sqp_iter, qp_iter, (t1 - t0) - (plant_done ? sm.ret[6] : 0.0));
+                nlp::put_nlp(out, sb + i, lane, cost, res4[0], res4[1], res4[2], res4[3]);
             });
             ex.par([&](int lane) {
                 if (lane < NX) sm.xhat[lane] = sm.logv[24 + lane];
@@ -3168,29 +3082,30 @@ struct Engine {
         });
     }
 
-    // Solver memory carried from one launch to the next in w.state (besides the workspace records): [0..11] the last feedback state,
-    // [12] lin_cost, [25] lin_valid, [26] fast_skip, [27] fast_back (the x_0 merit weights [13..24] are read and written in place)
+    // Solver memory carried from one launch to the next in w.state (besides the workspace records; slots: ST_* in mpc_layout.h):
+    // ST_Z the last feedback state, ST_LIN_COST, ST_LIN_VALID, ST_FAST fast_skip | fast_back (the x_0 merit weights ST_X0_MW are
+    // read and written in place)
     MPC_HD void load_carry(bool &lin_valid)
     {
         Ws &w = c.w;
-        lin_cost = w.state[12];
-        lin_valid = ex.uni(w.state[25] != 0.0);
+        lin_cost = w.state[ST_LIN_COST];
+        lin_valid = ex.uni(w.state[ST_LIN_VALID] != 0.0);
         rhs_valid = false;     // (not carried across launches: the first fast attempt of a launch forms its right-hand side itself)
-        fast_skip = ex.uni((int)w.state[26]); fast_back = ex.uni((int)w.state[27]);
+        fast_skip = ex.uni((int)w.state[ST_FAST]); fast_back = ex.uni((int)w.state[ST_FAST + 1]);
     }
     MPC_HD void store_carry(bool lin_valid)
     {
         Smem &sm = ex.smem();
         Ws &w = c.w;
         ex.par([&](int lane) {
-            if (lane < NX) w.state[lane] = sm.xhat[lane];
-            if (lane == 12) { w.state[12] = lin_cost; w.state[25] = lin_valid ? 1.0 : 0.0; w.state[26] = fast_skip; w.state[27] = fast_back; }
+            if (lane < NX) w.state[ST_Z + lane] = sm.xhat[lane];
+            if (lane == 12) { w.state[ST_LIN_COST] = lin_cost; w.state[ST_LIN_VALID] = lin_valid ? 1.0 : 0.0; w.state[ST_FAST] = fast_skip; w.state[ST_FAST + 1] = fast_back; }
 #ifdef MPCB_PROFILE
             if (lane < NPROF) {
                 double v = prof[0];
 #pragma unroll
                 for (int j = 1; j < NPROF; j++) v = lane == j ? prof[j] : v;
-                w.state[32 + lane] += v;
+                w.state[ST_PROF + lane] += v;
             }
 #endif
         });
@@ -3214,36 +3129,23 @@ struct Engine {
         ex.par([&](int lane) {
             if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
         });
+        // (without a reference the passes of the packed g_ref: the rollout's)
+        const auto lin = [&](double alpha, bool do_update, bool sqp_mult, double *r4, bool do_plant, bool fuse_commit, bool want_rhs) {
+            if (ex.uni(ref.y != nullptr)) return nlp_direct<true>(alpha, do_update, sqp_mult, r4, do_plant, fuse_commit, want_rhs, ref);
+            return nlp_direct(alpha, do_update, sqp_mult, r4, do_plant, fuse_commit, want_rhs);
+        };
+        const auto search = [&](int sqp_iter) { return ex.uni(ref.y != nullptr) ? line_search<true>(sqp_iter, ref) : line_search(sqp_iter); };
         int sqp_iter = 0, qp_iter = 0;
         double res4[4] = {0, 0, 0, 0}, cost = 0.0;
         const double t0 = ex.clock();
         bool plant_done = false;
-        const int status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, ref);
+        const int status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
         const double t1 = ex.clock();
         ex.par([&](int lane) {
             if (lane < NU) io.u0[(size_t)inst * NU + lane] = w.G1[O_U + lane];   // solver.get(0,'u')
-            if (lane == 8) {
-                io.status[inst] = status;
-                io.sqp_iter[inst] = sqp_iter;
-                io.qp_iter[inst] = qp_iter;
-                io.cost[inst] = cost;
-                io.solver_time[inst] = t1 - t0;
-            }
-            if (lane >= 12 && lane < 16) io.residuals[(size_t)inst * 4 + (lane - 12)] =
-                lane == 12 ? res4[0] : (lane == 13 ? res4[1] : (lane == 14 ? res4[2] : res4[3]));
-            // the predicted trajectory: the iterate's x_0..x_N and u_0..u_{N-1} (orc_solver_get_iterate)
-            if (io.x_pred) {
-                for (int e = lane; e < (N + 1) * NX; e += NT) {
-                    const int k = e / NX, i = e - k * NX;
-                    io.x_pred[(size_t)inst * (N + 1) * NX + e] = w.G1[(size_t)k * W1 + O_X + i];
-                }
-            }
-            if (io.u_pred) {
-                for (int e = lane; e < N * NU; e += NT) {
-                    const int k = e / NU, j = e - k * NU;
-                    io.u_pred[(size_t)inst * N * NU + e] = w.G1[(size_t)k * W1 + O_U + j];
-                }
-            }
+            nlp::put_solve(io, inst, lane, status, sqp_iter, qp_iter, t1 - t0);
+            nlp::put_nlp(io, inst, lane, cost, res4[0], res4[1], res4[2], res4[3]);
+            nlp::put_prediction(io, inst, lane, NT, w.G1, W1, N, N);   // (every simulation of a launch has the launch's horizon here)
         });
         store_carry(lin_valid);
     }
@@ -3266,15 +3168,7 @@ struct Engine {
             }
         });
         ex.par([&](int lane) {
-            if (lane < LOG_ROWS) {
-                const double v = lane < 12 ? sm.xhat[lane]
-                               : lane < 18 ? sm.u0[lane - 12]
-                               : lane < 30 ? sm.logv[lane - 18]
-                               : lane < 33 ? sm.logv[12 + (lane - 30)]
-                               : lane < 39 ? sm.logv[15 + (lane - 33)]
-                                           : sm.logv[36 + (lane - 39)];
-                sm.logbuf[lane][col & (LOGB - 1)] = v;
-            }
+            if (lane < LOG_ROWS) sm.logbuf[lane][col & (LOGB - 1)] = nlp::log_value(lane, sm.xhat, sm.u0, sm.logv);
         });
         col = ex.uni(col); log_lo = ex.uni(log_lo);   // wave-uniform: scalar branch
         if ((col & (LOGB - 1)) == LOGB - 1) { log_flush(out, inst, log_lo, col); log_lo = col + 1; }
@@ -3290,13 +3184,7 @@ struct Engine {
             for (int e = lane; e < LOG_ROWS * LOGB; e += NT) {
                 const int row = e / LOGB, cc = (c_hi & ~(LOGB - 1)) + (e & (LOGB - 1));
                 if (cc < c_lo || cc > c_hi) continue;
-                double *dst = row < 12 ? out.z + ((size_t)inst * 12 + row) * T1
-                            : row < 18 ? out.u + ((size_t)inst * 6 + (row - 12)) * T1
-                            : row < 30 ? out.ee_pose + ((size_t)inst * 12 + (row - 18)) * T1
-                            : row < 33 ? out.ee_rpy + ((size_t)inst * 3 + (row - 30)) * T1
-                            : row < 39 ? out.ee_vel + ((size_t)inst * 6 + (row - 33)) * T1
-                                       : out.errors + ((size_t)inst * 7 + (row - 39)) * T1;
-                dst[cc] = sm.logbuf[row][e & (LOGB - 1)];
+                nlp::log_row(out, inst, row, T1)[cc] = sm.logbuf[row][e & (LOGB - 1)];
             }
         });
     }

@@ -1,6 +1,7 @@
 // mpc_ipm.h -- the interior-point formulas BOTH engines use (latency engine mpc_core.h, throughput engine mpc_stream.h), in one
 // place: a change to HPIPM's step rules (oracle/mpc_oracle.c ipm_solve is the restatement they follow) lands here once.
 // Everything is a small inline function of scalars; the callers own the data movement (LDS rows, registers, HBM items).
+// What the engines share above the QP -- plant step, merit function, log layout -- is in mpc_nlp.h, in the same style.
 // Reference being restated: acados/HPIPM behind trajectory_optimizer.py:183-186 (d_ocp_qp_ipm_solve: warm start 2, update_var,
 // compute_lam_t, compute_alpha, compute_centering_correction), semantics as listed in SURVEY.md A.7.
 #pragma once
@@ -40,6 +41,16 @@ MPC_HD double step_scale(double alpha) { return alpha * ((1.0 - alpha) * 0.99 + 
 
 // Mehrotra centering parameter sigma = (mu_aff / mu)^3
 MPC_HD double sigma(double mu_aff, double mu) { const double tmp = mu_aff / mu; return tmp * tmp * tmp; }
+
+// Stop test at the top of an iteration of d_ocp_qp_ipm_solve: n0..n3 the inf-norms of the residuals [g, b, d, m], `it` iterations
+// done, alpha the last step length.  HPIPM status 3 NaN / 0 solved to tol / 1 max-iter / 2 min-step, or -1: iterate on.
+MPC_HD int stop_test(double n0, double n1, double n2, double n3, double tol, int it, int iter_max, double alpha)
+{
+    if (n0 != n0 || n1 != n1 || n2 != n2 || n3 != n3) return 3;
+    if (!(n0 > tol || n1 > tol || n2 > tol || n3 > tol)) return 0;
+    if (it >= iter_max) return 1;
+    return !(alpha > 1e-12) ? 2 : -1;
+}
 
 // One bound side of compute_lam_t + compute_alpha + the centering sums, branch-free: `sdv` is +dv for a lower, -dv for an upper
 // bound.  An absent side (on = false) holds lam = 0, t = 1, rd = rm = 0: its dt is forced to 0 and everything else vanishes by

@@ -1,0 +1,160 @@
+// mpc_nlp.h -- the formulas ABOVE the QP that BOTH engines use (latency engine mpc_core.h, throughput engine mpc_stream.h), in one
+// place, as mpc_ipm.h holds the interior-point ones: the plant step, the L1 merit function of the SQP line search and its weights,
+// the layout of the trajectory log, the writers of a step's statistics.  oracle/mpc_oracle.c stays an independent restatement.
+// Small inline functions of scalars and of ACCESSORS: the callers own the data movement, and every operand keeps the address space
+// the caller gave it (an LDS row, an MPC_GLOBAL pointer, a register array) because the operand types are template parameters -- a
+// plain `const double *` here would turn them into flat loads (comment above struct Ctx) or push a register array into scratch.
+// Everything compiles on the host (tests/emu).
+#pragma once
+#include <math.h>
+
+#include "mpc_layout.h"
+
+namespace mpcb {
+namespace nlp {
+
+// One joint of the plant step (simulation_model.py:93-117): Euler / RK2 (midpoint) / RK3 / RK4 of z' = [qdot; -W (qdot - u)]
+MPC_HD void plant_rk(const InstParams &P, int j, double q, double v, double u, double &qn, double &vn)
+{
+    const double wc = P.wcv[j], dt = P.dt;
+    const int integ = (int)P.integ;
+    const double k1q = v, k1v = -wc * v + wc * u;
+    const double v2 = v + 0.5 * dt * k1v;
+    const double k2q = v2, k2v = -wc * v2 + wc * u;
+    if (integ == 1) {
+        qn = q + dt * k1q; vn = v + dt * k1v;
+    } else if (integ == 2) {
+        qn = q + dt * k2q; vn = v + dt * k2v;
+    } else if (integ == 3) {
+        const double v3 = v - dt * k1v + 2.0 * dt * k2v;
+        const double k3q = v3, k3v = -wc * v3 + wc * u;
+        qn = q + (dt / 6) * (k1q + 4.0 * k2q + k3q); vn = v + (dt / 6) * (k1v + 4.0 * k2v + k3v);
+    } else {
+        const double v3 = v + 0.5 * dt * k2v;
+        const double k3q = v3, k3v = -wc * v3 + wc * u;
+        const double v4 = v + dt * k3v;
+        const double k4q = v4, k4v = -wc * v4 + wc * u;
+        qn = q + (dt / 6) * k1q + (dt / 3) * k2q + (dt / 3) * k3q + (dt / 6) * k4q;
+        vn = v + (dt / 6) * k1v + (dt / 3) * k2v + (dt / 3) * k3v + (dt / 6) * k4v;
+    }
+}
+
+// ---- SQP line search: MERIT_BACKTRACKING (trajectory_optimizer.py:68; acados alpha_reduction, alpha_min) -------------------------
+// trial steps 1, 0.7, 0.49, ... while >= 0.05
+constexpr double LS_REDUCTION = 0.7, LS_ALPHA_MIN = 0.05;
+
+// Leineweber's rule for a merit weight (acados merit_backtracking_*_weights): `a` = |multiplier| of the QP just solved, `w` the
+// weight so far (not read by the first QP of a solve)
+MPC_HD double merit_weight(int sqp_iter, double w, double a) { return sqp_iter == 0 ? a : fmax(a, 0.5 * (w + a)); }
+
+// Stationarity of the QP at stage 0 with respect to x_0 component i (q: i < 6, qdot: i >= 6); its absolute value is the multiplier
+// of the eliminated x_0 constraint, which the x_0 merit weights follow.  r1, r2: the stage-0 records of G1 and G2, O_Y holding
+// W (r + G delta).
+template <class R1, class R2>
+MPC_HD double x0_stationarity(const InstParams &P, int i, R1 r1, R2 r2)
+{
+    if (i < 6) {
+        double s = 0.0;
+#pragma unroll
+        for (int t = 0; t < NTASK; t++) s += r2[O_GQ + t * 6 + i] * r2[O_Y + t];
+        return P.dt * s + r1[O_QPI + i] + P.dt * P.lm * r1[O_QW + 6 + i];
+    }
+    const int jj = i - 6;
+    const double uj = r1[O_U + jj] + r1[O_QW + jj], vj = r1[O_X + 6 + jj] + r1[O_QW + 12 + jj];
+    const double c2 = P.w_qddot * P.cq[jj] * P.cq[jj];
+    return P.dt * (r2[O_GV + jj] * r2[O_Y + 4] + c2 * (vj - uj)) + P.a12[jj] * r1[O_QPI + jj] + P.a22[jj] * r1[O_QPI + 6 + jj] +
+           P.dt * P.lm * r1[O_QW + 12 + jj];
+}
+
+// L1 merit function (acados ocp_nlp_evaluate_merit_fun restated), stage k < N at a trial point: stage cost, weighted dynamics
+// defect against the next stage's trial state, weighted bound violations, added to `acc` term by term (a lane that sums several
+// stages keeps one running sum).  xx[12] | uu[6]: trial state and input; res(i): task residual i, any reference subtracted;
+// xnext(i): component i of the next stage's trial state; mw[36]: merit weights, dynamics 12 | lower 12 (u 6, q 6) | upper 12.
+// Branch-free (every lane-dependent branch costs a saved exec mask: the latency engine's pass ran out of SGPRs).
+template <class X, class U, class Res, class Xn, class Mw>
+MPC_HD void merit_stage(double &acc, const InstParams &P, const X &xx, const U &uu, Res &&res, Xn &&xnext, const Mw &mw, int k)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NTASK; i++) {
+        const double r = res(i);
+        s += P.w_task[i] * r * r;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        const double qdd = P.cq[j] * (uu[j] - xx[6 + j]);
+        s += 2.0 * P.w_u * uu[j] * uu[j] + P.w_qddot * qdd * qdd;
+        const double xnq = xnext(j), xnv = xnext(6 + j);
+        acc += mw[j] * fabs((xx[j] + P.a12[j] * xx[6 + j] + P.b1[j] * uu[j]) - xnq);
+        acc += mw[6 + j] * fabs((P.a22[j] * xx[6 + j] + P.b2[j] * uu[j]) - xnv);
+        const double vl = P.umin[j] - uu[j], vu = uu[j] - P.umax[j];
+        acc += mw[12 + j] * fmax(vl, 0.0) + mw[24 + j] * fmax(vu, 0.0);
+        const double ql = P.qmin[j] - xx[j], qu = xx[j] - P.qmax[j], on = k >= 1 ? 1.0 : 0.0;
+        acc += on * (mw[18 + j] * fmax(ql, 0.0) + mw[30 + j] * fmax(qu, 0.0));
+    }
+    acc += 0.5 * P.dt * s;
+}
+// ... and the term of the eliminated constraint x_0 = x_hat (stage 0 only): w0[12] its merit weights
+template <class W0, class Xh, class X>
+MPC_HD void merit_x0(double &acc, const W0 &w0, const Xh &xhat, const X &xx)
+{
+#pragma unroll
+    for (int i = 0; i < 12; i++) acc += w0[i] * fabs(xhat[i] - xx[i]);
+}
+
+// ---- trajectory log (mpc_layout.h LOG_ROWS): z 12 | u 6 | ee_pose 12 | ee_rpy 3 | ee_vel 6 | errors 7 ------------------------------
+// the value of log row `row`: xhat[12] the plant state, u0[6] its input, logv = [pose 12 | rpy 3 | J qdot 6 | ... | errors 7 at 36]
+template <class Xh, class U0, class Lv>
+MPC_HD double log_value(int row, const Xh &xhat, const U0 &u0, const Lv &logv)
+{
+    return row < 12 ? xhat[row] : row < 18 ? u0[row - 12] : row < 30 ? logv[row - 18] : row < 33 ? logv[12 + (row - 30)]
+         : row < 39 ? logv[15 + (row - 33)] : logv[36 + (row - 39)];
+}
+// where log row `row` of instance `inst` goes: its [T1] columns in the arrays of `out`
+MPC_HD double *log_row(const Outputs &out, int inst, int row, size_t T1)
+{
+    return row < 12 ? out.z + ((size_t)inst * 12 + row) * T1
+         : row < 18 ? out.u + ((size_t)inst * 6 + (row - 12)) * T1
+         : row < 30 ? out.ee_pose + ((size_t)inst * 12 + (row - 18)) * T1
+         : row < 33 ? out.ee_rpy + ((size_t)inst * 3 + (row - 30)) * T1
+         : row < 39 ? out.ee_vel + ((size_t)inst * 6 + (row - 33)) * T1
+                    : out.errors + ((size_t)inst * 7 + (row - 39)) * T1;
+}
+
+// ---- a step's statistics, to entry `at` of the arrays of O = Outputs or StepIO: one lane each --------------------------------------
+template <class O>
+MPC_HD void put_solve(const O &o, size_t at, int lane, int status, int sqp_iter, int qp_iter, double solver_time)
+{
+    if (lane == 8) { o.status[at] = status; o.sqp_iter[at] = sqp_iter; o.qp_iter[at] = qp_iter; o.solver_time[at] = solver_time; }
+}
+// cost and acados' residual norms [stat, eq, ineq, comp] of the iterate a step leaves
+template <class O>
+MPC_HD void put_nlp(const O &o, size_t at, int lane, double cost, double r0, double r1, double r2, double r3)
+{
+    if (lane == 8) o.cost[at] = cost;
+    if (lane >= 12 && lane < 16) o.residuals[at * 4 + (lane - 12)] = lane == 12 ? r0 : (lane == 13 ? r1 : (lane == 14 ? r2 : r3));
+}
+// The predicted trajectory of a controller step (orc_solver_get_iterate): x_0..x_N and u_0..u_{N-1} of the iterate, G1 records
+// `ld` doubles apart, into rows sized for the batch's longest horizon NMAX; the rows beyond this simulation's own are NaN, so that
+// nothing stale passes for a prediction.  `nt` lanes.
+template <class G>
+MPC_HD void put_prediction(const StepIO &io, int inst, int lane, int nt, G g1, size_t ld, int N, int NMAX)
+{
+    if (io.x_pred) {
+        double *xp = io.x_pred + (size_t)inst * (NMAX + 1) * NX;
+        for (int e = lane; e < (NMAX + 1) * NX; e += nt) {
+            const int k = e / NX, i = e - k * NX;
+            xp[e] = k <= N ? g1[(size_t)k * ld + O_X + i] : __builtin_nan("");
+        }
+    }
+    if (io.u_pred) {
+        double *up = io.u_pred + (size_t)inst * NMAX * NU;
+        for (int e = lane; e < NMAX * NU; e += nt) {
+            const int k = e / NU, j = e - k * NU;
+            up[e] = k < N ? g1[(size_t)k * ld + O_U + j] : __builtin_nan("");
+        }
+    }
+}
+
+}  // namespace nlp
+}  // namespace mpcb

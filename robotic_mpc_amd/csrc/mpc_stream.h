@@ -1708,13 +1708,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
     int it = 0, status = 1;
     double alpha = 1.0;
     for (;; it++) {
-        const double n0 = unid(r.ng), n1 = unid(r.nb), n2 = unid(r.nd), n3 = unid(r.nm);
-        int stop = -1;
-        if (n0 != n0 || n1 != n1 || n2 != n2 || n3 != n3) stop = 3;
-        else if (!(n0 > tol || n1 > tol || n2 > tol || n3 > tol)) stop = 0;
-        else if (it >= qp_iter_max) stop = 1;
-        else if (!(alpha > 1e-12)) stop = 2;
-        stop = uni(stop);
+        int stop = uni(ipm::stop_test(unid(r.ng), unid(r.nb), unid(r.nd), unid(r.nm), tol, it, qp_iter_max, alpha));
 #if defined(MPCB_NOCOMPUTE) || defined(MPCB_FIXED_IT)
         stop = it >= 3 ? 0 : -1;     // timing builds: three iterations per QP, whatever the (meaningless) norms say
 #endif
@@ -1864,7 +1858,7 @@ SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int s
 }
 
 // =============================================================================================== SQP line search
-// L1 merit function at the trial point (X,U) + alpha (dX,dU) (acados ocp_nlp_evaluate_merit_fun restated;
+// L1 merit function at the trial point (X,U) + alpha (dX,dU) (the stage terms: mpc_nlp.h merit_stage / merit_x0, shared with
 // mpc_core.h merit_pass).  lane <-> stage, straight from HBM.  With `update_weights` the merit weights (G5 MW) are
 // first refreshed from the QP multipliers by Leineweber's rule.
 template <bool REF = false>
@@ -1892,15 +1886,14 @@ SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskR
             double a_[36];
 #pragma unroll
             for (int i = 0; i < 36; i++) a_[i] = i < 12 ? fabs(r1[O_QPI + i]) : fabs(r1[O_QLAM + i - 12]);
-            if (sqp_iter == 0) {
 #pragma unroll
-                for (int i = 0; i < 36; i++) mwv[i] = a_[i];
-            } else {
+            for (int i = 0; i < 36; i++) mwv[i] = 0.0;
+            if (sqp_iter != 0) {      // (the first QP's weights do not read the old ones)
 #pragma unroll
                 for (int i = 0; i < 36; i++) mwv[i] = mw[i];
-#pragma unroll
-                for (int i = 0; i < 36; i++) mwv[i] = fmax(a_[i], 0.5 * (mwv[i] + a_[i]));
             }
+#pragma unroll
+            for (int i = 0; i < 36; i++) mwv[i] = nlp::merit_weight(sqp_iter, mwv[i], a_[i]);
 #pragma unroll
             for (int i = 0; i < 36; i++) mw[i] = mwv[i];
         } else {
@@ -1920,33 +1913,15 @@ SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskR
 #pragma unroll
                 for (int i = 0; i < NTASK; i++) rec[O_R + i] -= t[i];
             }
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < NTASK; i++) s += P.w_task[i] * rec[O_R + i] * rec[O_R + i];
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const double qdd = P.cq[j] * (uu[j] - xx[6 + j]);
-                s += 2.0 * P.w_u * uu[j] * uu[j] + P.w_qddot * qdd * qdd;
-                const double xnq = rn[O_X + j] + alpha * rn[O_QW + 6 + j];
-                const double xnv = rn[O_X + 6 + j] + alpha * rn[O_QW + 12 + j];
-                acc += mwv[j] * fabs((xx[j] + P.a12[j] * xx[6 + j] + P.b1[j] * uu[j]) - xnq);
-                acc += mwv[6 + j] * fabs((P.a22[j] * xx[6 + j] + P.b2[j] * uu[j]) - xnv);
-                const double vl = P.umin[j] - uu[j], vu = uu[j] - P.umax[j];
-                acc += mwv[12 + j] * fmax(vl, 0.0) + mwv[24 + j] * fmax(vu, 0.0);
-                const double ql = P.qmin[j] - xx[j], qu = xx[j] - P.qmax[j], on = k >= 1 ? 1.0 : 0.0;
-                acc += on * (mwv[18 + j] * fmax(ql, 0.0) + mwv[30 + j] * fmax(qu, 0.0));
-            }
-            acc += 0.5 * P.dt * s;
+            nlp::merit_stage(acc, P, xx, uu, [&](int i) { return rec[O_R + i]; },
+                             [&](int i) { return rn[O_X + i] + alpha * rn[O_QW + 6 + i]; }, mwv, k);
         }
-        if (k == 0) {
-#pragma unroll
-            for (int i = 0; i < 12; i++) acc += w.state[ST_X0_MW + i] * fabs(sm.xhat[i] - xx[i]);
-        }
+        if (k == 0) nlp::merit_x0(acc, w.state + ST_X0_MW, sm.xhat, xx);
     }
     return wsum(acc);
 }
 
-// Merit weight of the eliminated x_0 constraint: |stage-0 stationarity of the QP wrt x_0| (mpc_core.h update_x0_weights)
+// Merit weight of the eliminated x_0 constraint: |stage-0 stationarity of the QP wrt x_0| (mpc_nlp.h)
 SE_PASS void update_x0_weights(int sqp_iter)
 {
     SSmem &sm = g_ssm;
@@ -1955,28 +1930,15 @@ SE_PASS void update_x0_weights(int sqp_iter)
     const SWs w = sm.w;
     if (lane < NX) {
         const double *r1 = w.G1, *r2 = w.G2;      // stage 0 records (y holds W(r + G delta) of the last residual pass)
-        double v;
-        if (lane < 6) {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < NTASK; i++) s += r2[O_GQ + i * 6 + lane] * r2[O_Y + i];
-            v = P.dt * s + r1[O_QPI + lane] + P.dt * P.lm * r1[O_QW + 6 + lane];
-        } else {
-            const int jj = lane - 6;
-            const double uj = r1[O_U + jj] + r1[O_QW + jj], vj = r1[O_X + 6 + jj] + r1[O_QW + 12 + jj];
-            const double c2 = P.w_qddot * P.cq[jj] * P.cq[jj];
-            v = P.dt * (r2[O_GV + jj] * r2[O_Y + 4] + c2 * (vj - uj)) + P.a12[jj] * r1[O_QPI + jj] +
-                P.a22[jj] * r1[O_QPI + 6 + jj] + P.dt * P.lm * r1[O_QW + 12 + jj];
-        }
-        const double a = fabs(v);
+        const double a = fabs(nlp::x0_stationarity(P, lane, r1, r2));
         double *mwp = &w.state[ST_X0_MW + lane];
-        *mwp = sqp_iter == 0 ? a : fmax(a, 0.5 * (*mwp + a));
+        *mwp = nlp::merit_weight(sqp_iter, *mwp, a);
     }
     __builtin_amdgcn_s_waitcnt(0);
     fence();
 }
 
-// MERIT_BACKTRACKING (trajectory_optimizer.py:68; acados alpha_reduction 0.7, alpha_min 0.05).  REF: against the task reference `ref`.
+// MERIT_BACKTRACKING (nlp::LS_REDUCTION, LS_ALPHA_MIN).  REF: against the task reference `ref`.
 template <bool REF = false>
 SE_DEV double line_search(int sqp_iter, TaskRef ref = TaskRef{nullptr})
 {
@@ -1989,9 +1951,9 @@ SE_DEV double line_search(int sqp_iter, TaskRef ref = TaskRef{nullptr})
     __builtin_amdgcn_s_waitcnt(0);
     fence();
     double alpha = 1.0;
-    while (alpha >= 0.05) {
+    while (alpha >= nlp::LS_ALPHA_MIN) {
         if (uni(unid(merit(alpha, false)) < m0 ? 1 : 0)) break;
-        alpha *= 0.7;
+        alpha *= nlp::LS_REDUCTION;
     }
     return alpha;
 }
@@ -2004,13 +1966,7 @@ SE_DEV void log_flush(const Outputs &out, int inst, int T1, int c_lo, int c_hi)
     for (int e = lane; e < LOG_ROWS * SLOGB; e += WAVE) {
         const int row = e / SLOGB, cc = (c_hi & ~(SLOGB - 1)) + (e & (SLOGB - 1));
         if (cc < c_lo || cc > c_hi) continue;
-        double *dst = row < 12 ? out.z + ((size_t)inst * 12 + row) * T1
-                    : row < 18 ? out.u + ((size_t)inst * 6 + (row - 12)) * T1
-                    : row < 30 ? out.ee_pose + ((size_t)inst * 12 + (row - 18)) * T1
-                    : row < 33 ? out.ee_rpy + ((size_t)inst * 3 + (row - 30)) * T1
-                    : row < 39 ? out.ee_vel + ((size_t)inst * 6 + (row - 33)) * T1
-                               : out.errors + ((size_t)inst * 7 + (row - 39)) * T1;
-        dst[cc] = sm.logbuf[row][e & (SLOGB - 1)];
+        nlp::log_row(out, inst, row, T1)[cc] = sm.logbuf[row][e & (SLOGB - 1)];
     }
     fence();
 }
@@ -2028,15 +1984,7 @@ SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo)
         task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
     }
     fence();
-    if (lane < LOG_ROWS) {
-        const double v = lane < 12 ? sm.xhat[lane]
-                       : lane < 18 ? sm.u0[lane - 12]
-                       : lane < 30 ? sm.logv[lane - 18]
-                       : lane < 33 ? sm.logv[12 + (lane - 30)]
-                       : lane < 39 ? sm.logv[15 + (lane - 33)]
-                                   : sm.logv[36 + (lane - 39)];
-        sm.logbuf[lane][col & (SLOGB - 1)] = v;
-    }
+    if (lane < LOG_ROWS) sm.logbuf[lane][col & (SLOGB - 1)] = nlp::log_value(lane, sm.xhat, sm.u0, sm.logv);
     fence();
     col = uni(col); log_lo = uni(log_lo);
     if ((col & (SLOGB - 1)) == SLOGB - 1) { log_flush(out, inst, T1, log_lo, col); log_lo = col + 1; }
@@ -2235,12 +2183,8 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         const bool defer = pb.solver_type == 1 && i + 1 < step1;
         double nlp_prev[5];
         const StepStats s = mpc_step<FT>(pb, c, lin, search, res_pending ? nlp_prev : nullptr, defer);
-        if (res_pending) {
-            // cost and residual norms of step i-1, evaluated by this step's first pass
-            if (lane == 8) out.cost[sbase + i - 1] = nlp_prev[0];
-            if (lane >= 12 && lane < 16) out.residuals[(sbase + i - 1) * 4 + (lane - 12)] =
-                lane == 12 ? nlp_prev[1] : (lane == 13 ? nlp_prev[2] : (lane == 14 ? nlp_prev[3] : nlp_prev[4]));
-        }
+        // cost and residual norms of step i-1, evaluated by this step's first pass
+        if (res_pending) nlp::put_nlp(out, sbase + i - 1, lane, nlp_prev[0], nlp_prev[1], nlp_prev[2], nlp_prev[3], nlp_prev[4]);
         res_pending = defer;
         const double t1 = wclock();
 #ifdef MPCB_SPROF
@@ -2249,42 +2193,15 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         // u = solver.get(0,'u'); plant step (simulation_model.py:93-117)
         if (lane < 6) {
             const int j = lane;
-            const double u = w.G1[O_U + j], wc = P.wcv[j], dt = P.dt;
-            const double q = sm.xhat[j], v = sm.xhat[6 + j];
-            const int integ = (int)P.integ;
-            const double k1q = v, k1v = -wc * v + wc * u;
-            const double v2 = v + 0.5 * dt * k1v;
-            const double k2q = v2, k2v = -wc * v2 + wc * u;
+            const double u = w.G1[O_U + j];
             double qn, vn;
-            if (integ == 1) {
-                qn = q + dt * k1q; vn = v + dt * k1v;
-            } else if (integ == 2) {
-                qn = q + dt * k2q; vn = v + dt * k2v;
-            } else if (integ == 3) {
-                const double v3 = v - dt * k1v + 2.0 * dt * k2v;
-                const double k3q = v3, k3v = -wc * v3 + wc * u;
-                qn = q + (dt / 6) * (k1q + 4.0 * k2q + k3q); vn = v + (dt / 6) * (k1v + 4.0 * k2v + k3v);
-            } else {
-                const double v3 = v + 0.5 * dt * k2v;
-                const double k3q = v3, k3v = -wc * v3 + wc * u;
-                const double v4 = v + dt * k3v;
-                const double k4q = v4, k4v = -wc * v4 + wc * u;
-                qn = q + (dt / 6) * k1q + (dt / 3) * k2q + (dt / 3) * k3q + (dt / 6) * k4q;
-                vn = v + (dt / 6) * k1v + (dt / 3) * k2v + (dt / 3) * k3v + (dt / 6) * k4v;
-            }
+            nlp::plant_rk(P, j, sm.xhat[j], sm.xhat[6 + j], u, qn, vn);
             sm.logv[24 + j] = qn;
             sm.logv[30 + j] = vn;
             sm.u0[j] = u;
         }
-        if (lane == 8) {
-            out.status[sbase + i] = s.status;
-            out.sqp_iter[sbase + i] = s.sqp_iter;
-            out.qp_iter[sbase + i] = s.qp_iter;
-            if (!res_pending) out.cost[sbase + i] = s.cost;
-            out.solver_time[sbase + i] = t1 - t0;
-        }
-        if (!res_pending && lane >= 12 && lane < 16) out.residuals[(sbase + i) * 4 + (lane - 12)] =
-            lane == 12 ? s.res4[0] : (lane == 13 ? s.res4[1] : (lane == 14 ? s.res4[2] : s.res4[3]));
+        nlp::put_solve(out, sbase + i, lane, s.status, s.sqp_iter, s.qp_iter, t1 - t0);
+        if (!res_pending) nlp::put_nlp(out, sbase + i, lane, s.cost, s.res4[0], s.res4[1], s.res4[2], s.res4[3]);
         fence();
         if (lane < NX) sm.xhat[lane] = sm.logv[24 + lane];
         fence();
@@ -2332,32 +2249,10 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
     // solver.get(0,'u') and the step's statistics.  The NLP iterate lives in G1 [X | U] whichever slot `cur` names (that is the QP
     // iterate's: the step lin_pass has just applied).
     if (lane < NU) io.u0[(size_t)inst * NU + lane] = w.G1[O_U + lane];
-    if (lane == 8) {
-        io.status[inst] = s.status;
-        io.sqp_iter[inst] = s.sqp_iter;
-        io.qp_iter[inst] = s.qp_iter;
-        io.cost[inst] = s.cost;
-        io.solver_time[inst] = t1 - t0;
-    }
-    if (lane >= 12 && lane < 16) io.residuals[(size_t)inst * 4 + (lane - 12)] =
-        lane == 12 ? s.res4[0] : (lane == 13 ? s.res4[1] : (lane == 14 ? s.res4[2] : s.res4[3]));
-    // the predicted trajectory x_0..x_N, u_0..u_{N-1} (orc_solver_get_iterate), in rows sized for the longest horizon of the batch: the
-    // rows beyond this simulation's own horizon are NaN, so that nothing stale passes for a prediction
-    const int LD = w.ld / 8;
-    if (io.x_pred) {
-        double *xp = io.x_pred + (size_t)inst * (NMAX + 1) * NX;
-        for (int e = lane; e < (NMAX + 1) * NX; e += WAVE) {
-            const int k = e / NX, i = e - k * NX;
-            xp[e] = k <= N ? w.G1[(size_t)k * LD + O_X + i] : __builtin_nan("");
-        }
-    }
-    if (io.u_pred) {
-        double *up = io.u_pred + (size_t)inst * NMAX * NU;
-        for (int e = lane; e < NMAX * NU; e += WAVE) {
-            const int k = e / NU, j = e - k * NU;
-            up[e] = k < N ? w.G1[(size_t)k * LD + O_U + j] : __builtin_nan("");
-        }
-    }
+    nlp::put_solve(io, inst, lane, s.status, s.sqp_iter, s.qp_iter, t1 - t0);
+    nlp::put_nlp(io, inst, lane, s.cost, s.res4[0], s.res4[1], s.res4[2], s.res4[3]);
+    // (the rows beyond this simulation's own horizon, in rows sized for the longest of the batch, are NaN)
+    nlp::put_prediction(io, inst, lane, WAVE, w.G1, w.ld / 8, N, NMAX);
     c.store(w.state);
 }
 #endif  // __HIP_DEVICE_COMPILE__

@@ -149,7 +149,7 @@ extern "C" int emu_run(const Problem *pb, const double *robot105, const double *
 }
 
 // Which implementation the device takes at horizon N with a chunk pool of `pool_doubles` and `waves` wavefronts per simulation --
-// through the Engine's own predicates (the same three lines as Engine::ipm_solve), for tests/test_boundaries.py:
+// through the Engine's own decision (Engine::sweep_family, what ipm_solve routes its sweeps by), for tests/test_boundaries.py:
 //   o[0] sweep of ipm_solve: 0 resident, 1 register, 2 segment, 3 streaming     o[1] merit_lanes()   o[2] merit_groups()
 //   o[3] lane groups of the resident sweeps      o[4] transitions per segment (seg_map)   o[5] transitions per segment (reg_map)
 //   o[6] lanes per simulation
@@ -164,10 +164,8 @@ static void emu_paths_t(int N, int pool_doubles, int *o)
     HostExec<NWV> ex{&sm, pool.data()};
     Ctx c{&pb, Ws{}, pool_doubles, N};
     Engine<HostExec<NWV>> eng(ex, c);
-    const bool res = eng.resident_ok();
-    const bool reg = eng.reg_ok();
-    const bool seg = !reg && eng.segment_ok();
-    o[0] = res ? 0 : reg ? 1 : seg ? 2 : 3;
+    const auto sw = eng.sweep_family();
+    o[0] = sw.res ? 0 : sw.reg ? 1 : sw.seg ? 2 : 3;
     o[1] = eng.merit_lanes();
     o[2] = eng.merit_groups();
     o[3] = Engine<HostExec<NWV>>::RS_GROUPS;
