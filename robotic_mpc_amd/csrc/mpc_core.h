@@ -1273,8 +1273,14 @@ struct Engine {
                     // terminal stage: no cost, no bounds -> P_N = lm I (0 without levenberg_marquardt) ; R~, S~ of stage N-1
                     ex.seq([&](int lane) {
                         const double lmN = ex.smem().P.lm;
-                        for (int e = lane; e < NPM; e += WAVE) fac[O_PM + e] = 0.0;
-                        if (lane < NX) fac[O_PM + tri(lane, lane)] = lmN;   // (same wavefront, program order: after the zero fill)
+                        // every entry written once, by one lane: a diagonal write after a zero fill by OTHER lanes holds only while
+                        // the wavefront runs in lockstep (the host emulation runs the lanes one after the other and lost the diagonal)
+                        for (int e = lane; e < NPM; e += WAVE) {
+                            double v = 0.0;
+#pragma unroll
+                            for (int i = 0; i < NX; i++) v = e == tri(i, i) ? lmN : v;
+                            fac[O_PM + e] = v;
+                        }
                         if (lane < 36) {
                             FactLane &f = fl.at(lane);
                             f.mqv = f.mvq = 0.0;

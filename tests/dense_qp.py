@@ -1,0 +1,281 @@
+"""A reference for ONE Gauss-Newton QP of the MPC step that shares no code and no algorithm with the engines or the oracle.
+
+Plain numpy / scipy; nothing from oracle/ or robotic_mpc_amd/csrc is imported.
+
+  * assemble(): the QP at an iterate.  The 17-row stage residual comes from the 4x4 homogeneous-transform chain (the model of
+    tests/helpers.fk_homogeneous / task_g_numpy, written dtype-generic here) and its Jacobian by complex-step differentiation,
+    which is exact to rounding -- no analytic derivative is restated.  Weights, the dt scaling, the Levenberg-Marquardt terms and
+    the shifted bounds follow the reference (trajectory_optimizer.py:142-171, acados' "Ts * levenberg_marquardt * eye()").
+  * solve_equality(): the equality-constrained QP through a pivoted sparse LU of the whole KKT system (no Riccati recursion),
+    refined with an extended-precision residual.
+  * certify(): for a QP with bounds, an exact active-set certificate of a candidate solution.
+
+Variables per stage k < N: w_k = [du_k (6); dx_k (12)], x = [q; qdot]; the last stage has dx_N only.
+"""
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+NU, NX, NW, NR = 6, 12, 18, 17
+BIG = 1e30          # "no bound", as the engines' QP records write it
+H_STEP = 1e-30      # complex step
+
+
+# --------------------------------------------------------------------------------------------------------------- the model
+def _rot_axis(a, th):
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]], dtype=float)
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def _fk(chain, q):
+    """4x4 chain product in q's dtype: T_ee, joint origins and joint axes in the world frame."""
+    dtype = np.result_type(q.dtype, float)
+    T = np.eye(4, dtype=dtype)
+    origins, axes = [], []
+    for i in range(6):
+        M = np.eye(4)
+        M[:3, :3] = np.asarray(chain.place[i, :9]).reshape(3, 3)
+        M[:3, 3] = chain.place[i, 9:]
+        T = T @ M
+        origins.append(T[:3, 3].copy())
+        axes.append(T[:3, :3] @ np.asarray(chain.axis[i], dtype=float))
+        Rj = np.eye(4, dtype=dtype)
+        Rj[:3, :3] = _rot_axis(chain.axis[i], q[i])
+        T = T @ Rj
+    M = np.eye(4)
+    M[:3, :3] = np.asarray(chain.place[6, :9]).reshape(3, 3)
+    M[:3, 3] = chain.place[6, 9:]
+    return T @ M, origins, axes
+
+
+def task_outputs(chain, coeffs, t_ee, x):
+    """g1..g5 of trajectory_optimizer.py:120-124 at x = [q; qdot] (real or complex)."""
+    q, qd = x[:6], x[6:]
+    T, origins, axes = _fk(chain, q)
+    R, p = T[:3, :3], T[:3, 3]
+    tw = R @ np.asarray(t_ee, dtype=float)
+    pt = p + tw
+    a, b, c, d, e, f = coeffs
+    X, Y = pt[0], pt[1]
+    S = a * X * X + b * Y * Y + c * X * Y + d * X + e * Y + f
+    m = np.array([2 * a * X + c * Y + d, 2 * b * Y + c * X + e, -1.0 + 0 * X])
+    n = m / np.sqrt(m @ m)             # not np.linalg.norm: that takes absolute values and breaks the complex step
+    vl = sum(np.cross(o, z) * v for o, z, v in zip(origins, axes, qd))      # spatial velocity, world frame
+    om = sum(z * v for z, v in zip(axes, qd))
+    vt = R.T @ (vl + np.cross(om, tw))
+    return np.array([S - pt[2], n @ R[:, 2], R[0, 1], pt[0], vt[1]])
+
+
+def lti(wcv, Ts):
+    """Ad, Bd of prediction_model.py:87-115."""
+    wcv = np.asarray(wcv, dtype=float)
+    a22 = np.exp(-wcv * Ts)
+    a12 = (1.0 - a22) / wcv
+    A = np.eye(12)
+    A[:6, 6:] = np.diag(a12)
+    A[6:, 6:] = np.diag(a22)
+    B = np.zeros((12, 6))
+    B[:6] = np.diag(Ts - a12)
+    B[6:] = np.diag(1.0 - a22)
+    return A, B
+
+
+def weights(cfg):
+    """diag W of trajectory_optimizer.py:142-152 without the zero-weight manipulability row."""
+    return np.concatenate([np.asarray(cfg["w_task"], float), np.full(6, 2.0 * cfg["w_u"]), np.full(6, float(cfg["w_qddot"]))])
+
+
+def packed_reference(cfg):
+    return np.array([0.0, 1.0, 0.0, cfg["px_ref"], cfg["vy_ref"]])
+
+
+def stage_residual(chain, cfg, x, u, yref_k=None):
+    """r [17] = [g - yref (5); u (6); qddot (6)] and Jr [17, 18] = d r / d [u; q; qdot]: the task rows by complex step, the
+    input and acceleration rows linear (qddot = (qdot_next - qdot) / Ts with the discrete model, prediction_model.py:322-326)."""
+    x, u = np.asarray(x, float), np.asarray(u, float)
+    A, B = lti(cfg["wcv"], cfg["dt"])
+    y = packed_reference(cfg) if yref_k is None else np.asarray(yref_k, float)
+    Sel = np.zeros((6, 12))
+    Sel[:, 6:] = np.eye(6)
+    Dx, Du = (Sel @ A - Sel) / cfg["dt"], (Sel @ B) / cfg["dt"]
+    r = np.concatenate([task_outputs(chain, cfg["coeffs"], cfg["t_ee"], x) - y, u, Dx @ x + Du @ u])
+    Jr = np.zeros((NR, NW))
+    for j in range(12):
+        xc = x.astype(complex)
+        xc[j] += 1j * H_STEP
+        Jr[:5, 6 + j] = task_outputs(chain, cfg["coeffs"], cfg["t_ee"], xc).imag / H_STEP
+    Jr[5:11, :6] = np.eye(6)
+    Jr[11:, :6] = Du
+    Jr[11:, 6:] = Dx
+    return r, Jr
+
+
+# ------------------------------------------------------------------------------------------------------------------ the QP
+class QP:
+    """H [N+1, 18, 18], g [N+1, 18], b [N, 12], A, B, lb / ub [N+1, 12] over (du, dq) (+-BIG where there is none), dx0 [12]."""
+
+    def __init__(self, H, g, b, A, B, lb, ub, dx0):
+        self.H, self.g, self.b, self.A, self.B, self.lb, self.ub, self.dx0 = H, g, b, A, B, lb, ub, dx0
+        self.N = H.shape[0] - 1
+
+    def split(self, w):
+        """Flat solution -> (dX [N+1, 12], dU [N, 6])."""
+        N = self.N
+        ws = w[:NW * N].reshape(N, NW)
+        return np.vstack([ws[:, 6:], w[NW * N:][None]]), ws[:, :6].copy()
+
+    def join(self, dX, dU):
+        return np.concatenate([np.hstack([dU, dX[:-1]]).ravel(), dX[-1]])
+
+    def bounded(self):
+        """Flat indices of the components with a bound, their lower and upper bounds."""
+        idx, lo, hi = [], [], []
+        for k in range(self.N):
+            for j in range(12):
+                if self.lb[k, j] > -BIG / 2 or self.ub[k, j] < BIG / 2:
+                    idx.append(NW * k + j); lo.append(self.lb[k, j]); hi.append(self.ub[k, j])
+        return np.array(idx, dtype=int), np.array(lo), np.array(hi)
+
+    def value(self, w):
+        """The QP's model value 1/2 w'Hw + g'w at a flat point."""
+        N, v = self.N, 0.0
+        for k in range(N):
+            wk = w[NW * k:NW * k + NW]
+            v += 0.5 * wk @ self.H[k] @ wk + self.g[k] @ wk
+        wk = w[NW * N:]
+        return v + 0.5 * wk @ self.H[N][6:, 6:] @ wk + self.g[N][6:] @ wk
+
+
+def assemble(chain, cfg, X, U, xhat, yref=None):
+    """The Gauss-Newton QP of one MPC step at the iterate (X [N+1, 12], U [N, 6]) with feedback state xhat: stage Hessians
+    dt Jr'WJr + dt lm I (terminal: lm I on the states), gradients dt Jr'W r, dynamics defects, bounds shifted by the iterate (lbu /
+    ubu on stages 0..N-1, lbx / ubx on the joint angles of stages 1..N-1; trajectory_optimizer.py:164-171)."""
+    X, U = np.asarray(X, float), np.asarray(U, float)
+    N, dt, lm = U.shape[0], float(cfg["dt"]), float(cfg.get("levenberg_marquardt", 0.0))
+    assert X.shape == (N + 1, 12)
+    W = weights(cfg)
+    A, B = lti(cfg["wcv"], cfg["dt"])
+    H = np.zeros((N + 1, NW, NW)); g = np.zeros((N + 1, NW)); b = np.zeros((N, 12))
+    lb = np.full((N + 1, 12), -BIG); ub = np.full((N + 1, 12), BIG)
+    memo = {}
+    for k in range(N):
+        yk = None if yref is None else np.asarray(yref[k], float)
+        key = (X[k].tobytes(), U[k].tobytes(), None if yk is None else yk.tobytes())
+        if key not in memo:
+            memo[key] = stage_residual(chain, cfg, X[k], U[k], yk)
+        r, Jr = memo[key]
+        H[k] = dt * Jr.T @ (W[:, None] * Jr) + dt * lm * np.eye(NW)
+        g[k] = dt * Jr.T @ (W * r)
+        b[k] = A @ X[k] + B @ U[k] - X[k + 1]
+        lb[k, :6] = np.asarray(cfg["umin"], float) - U[k]; ub[k, :6] = np.asarray(cfg["umax"], float) - U[k]
+        if k >= 1:
+            lb[k, 6:] = np.asarray(cfg["qmin"], float) - X[k, :6]; ub[k, 6:] = np.asarray(cfg["qmax"], float) - X[k, :6]
+    H[N, 6:, 6:] = lm * np.eye(12)
+    return QP(H, g, b, A, B, lb, ub, np.asarray(xhat, float) - X[0])
+
+
+def nlp_cost(chain, cfg, X, U, yref=None):
+    """sum_k dt 1/2 r'W r at (X, U): what acados' get_cost() returns after the step."""
+    W = weights(cfg)
+    c = 0.0
+    for k in range(U.shape[0]):
+        xc, uc = np.asarray(X[k], float), np.asarray(U[k], float)
+        A, B = lti(cfg["wcv"], cfg["dt"])
+        y = packed_reference(cfg) if yref is None else np.asarray(yref[k], float)
+        r = np.concatenate([task_outputs(chain, cfg["coeffs"], cfg["t_ee"], xc) - y, uc, ((A @ xc + B @ uc)[6:] - xc[6:]) / cfg["dt"]])
+        c += 0.5 * cfg["dt"] * float(W @ (r * r))
+    return c
+
+
+def _kkt(qp, fixed_idx, fixed_val):
+    N = qp.N
+    n = NW * N + 12
+    rows, cols, vals = [], [], []
+
+    def block(r0, c0, M):
+        rr, cc = np.nonzero(M)
+        rows.extend((r0 + rr).tolist()); cols.extend((c0 + cc).tolist()); vals.extend(M[rr, cc].tolist())
+
+    for k in range(N):
+        block(NW * k, NW * k, qp.H[k])
+    block(NW * N, NW * N, qp.H[N][6:, 6:])
+    m = 12 * (N + 1) + len(fixed_idx)
+    C_r, C_c, C_v = [], [], []
+    d = np.zeros(m)
+
+    def cblock(r0, c0, M):
+        rr, cc = np.nonzero(M)
+        C_r.extend((r0 + rr).tolist()); C_c.extend((c0 + cc).tolist()); C_v.extend(M[rr, cc].tolist())
+
+    cblock(0, 6, np.eye(12))                               # dx_0 = xhat - X_0
+    d[:12] = qp.dx0
+    for k in range(N):                                     # A dx_k + B du_k - dx_{k+1} = -b_k
+        r0 = 12 * (k + 1)
+        cblock(r0, NW * k, qp.B)
+        cblock(r0, NW * k + 6, qp.A)
+        cblock(r0, NW * (k + 1) + (6 if k + 1 < N else 0), -np.eye(12))
+        d[r0:r0 + 12] = -qp.b[k]
+    for i, (j, v) in enumerate(zip(fixed_idx, fixed_val)):
+        C_r.append(12 * (N + 1) + i); C_c.append(int(j)); C_v.append(1.0)
+        d[12 * (N + 1) + i] = v
+    rows += [n + r for r in C_r] + C_c
+    cols += C_c + [n + r for r in C_r]
+    vals += C_v + C_v
+    K = sp.coo_matrix((vals, (rows, cols)), shape=(n + m, n + m))
+    K.sum_duplicates()
+    gflat = np.concatenate([qp.g[:N].ravel(), qp.g[N][6:]])
+    return K, np.concatenate([-gflat, d]), n
+
+
+def solve_equality(qp, fixed_idx=(), fixed_val=()):
+    """The minimiser of the QP under its equalities (dynamics, dx_0) with the flat components `fixed_idx` held at `fixed_val`
+    and every other bound ignored.  Pivoted sparse LU of the full KKT matrix, then iterative refinement with the residual in
+    np.longdouble until the correction is below 1e-15 relative or three steps are taken.  Returns dict(w: flat solution,
+    dX, dU, mult: multipliers of the fixed components (sign of the Lagrangian 1/2 w'Hw + g'w + mult (w_j - v)),
+    lu_vs_refined: max |plain LU - refined| on w, the conditioning estimate)."""
+    fixed_idx = np.asarray(fixed_idx, dtype=int)
+    K, rhs, n = _kkt(qp, fixed_idx, np.asarray(fixed_val, float))
+    lu = spla.splu(K.tocsc())
+    z0 = lu.solve(rhs)
+    z = z0.astype(np.longdouble)
+    Kc = K.tocoo()
+    r_, c_, v_ = Kc.row, Kc.col, Kc.data.astype(np.longdouble)
+    rhs_l = rhs.astype(np.longdouble)
+    for _ in range(3):
+        res = rhs_l.copy()
+        np.subtract.at(res, r_, v_ * z[c_])
+        dz = lu.solve(res.astype(np.float64))
+        z = z + dz.astype(np.longdouble)
+        if np.abs(dz).max() <= 1e-15 * max(float(np.abs(z).max()), 1e-300):
+            break
+    zf = z.astype(np.float64)
+    w = zf[:n]
+    dX, dU = qp.split(w)
+    return dict(w=w, dX=dX, dU=dU, mult=zf[n + 12 * (qp.N + 1):], lu_vs_refined=float(np.abs(z0[:n] - w).max()))
+
+
+ACTIVE_TOL = 1e-6
+
+
+def certify(qp, dX, dU):
+    """An active-set certificate of the candidate (dX, dU) for the QP WITH its bounds.  The active set is read off the candidate
+    (bounded components within ACTIVE_TOL of a bound), the QP is solved with those held at their bounds, and the result says how
+    far the candidate is from that solution (`distance`), the smallest multiplier of a held component in the convention
+    "lambda >= 0 at an optimum" (`min_multiplier`, +inf with no active bound) and the smallest slack to a bound over the free
+    bounded components of the dense solution (`min_slack`).  The dense solution is THE optimum iff min_multiplier >= 0 and
+    min_slack >= 0 (the QP is strictly convex on its feasible subspace); the candidate is optimal iff, besides, distance is within
+    rounding."""
+    w = qp.join(np.asarray(dX, float), np.asarray(dU, float))
+    idx, lo, hi = qp.bounded()
+    at_lo = np.abs(w[idx] - lo) <= ACTIVE_TOL
+    at_hi = (np.abs(hi - w[idx]) <= ACTIVE_TOL) & ~at_lo
+    act = at_lo | at_hi
+    sol = solve_equality(qp, idx[act], np.where(at_lo, lo, hi)[act])
+    lam = np.where(at_lo[act], -sol["mult"], sol["mult"])
+    free = ~act
+    slack = np.minimum(sol["w"][idx[free]] - lo[free], hi[free] - sol["w"][idx[free]])
+    cand_slack = np.minimum(w[idx[free]] - lo[free], hi[free] - w[idx[free]])
+    return dict(sol, distance=float(np.abs(sol["w"] - w).max()), n_active=int(act.sum()),
+                min_multiplier=float(lam.min()) if act.any() else float("inf"),
+                min_slack=float(slack.min()) if free.any() else float("inf"),
+                candidate_min_slack=float(cand_slack.min()) if free.any() else float("inf"))

@@ -1,5 +1,6 @@
 """Independent checks of the controller step against a task reference, shared by the emulation and the device tests: the
-Gauss-Newton QP step at a given iterate built from the oracle's primitives, and a dense least-squares solve of the NLP."""
+Gauss-Newton QP step at a given iterate (from the oracle's primitives, or independently of the oracle through tests/dense_qp.py),
+and a dense least-squares solve of the NLP."""
 import numpy as np
 
 
@@ -28,9 +29,9 @@ def stage_residual(orc, rb, p, cfg, x, u, yref_k):
     return r, Jr
 
 
-def gn_qp_step(orc, rb, cfg, X, U, xhat, yref):
-    """The iterate after one full Gauss-Newton QP step from (X [N+1,12], U [N,6]) under the reference yref [N,5], solved by the
-    bound-inactive fast path (orc.qp_fast); None when the fast path rejects the QP."""
+def oracle_qp(orc, rb, cfg, X, U, xhat, yref):
+    """The Gauss-Newton QP at the iterate (X [N+1,12], U [N,6]) under the reference yref [N,5], built from the oracle's
+    primitives: (H, g, b, A, B, lb, ub, dx0) as orc.qp_fast / orc.qp_ipm take them."""
     p = orc.make_params(cfg)
     N, dt, lm = cfg["N"], cfg["dt"], float(cfg.get("levenberg_marquardt", 0.0))
     W = _weights(cfg)
@@ -46,10 +47,28 @@ def gn_qp_step(orc, rb, cfg, X, U, xhat, yref):
         if k >= 1:
             lb[k, 6:] = np.asarray(cfg["qmin"]) - X[k, :6]; ub[k, 6:] = np.asarray(cfg["qmax"]) - X[k, :6]
     H[N, 6:, 6:] += lm * np.eye(12)
-    q = orc.qp_fast(H, g, b, A, B, lb, ub, xhat - X[0])
+    return H, g, b, A, B, lb, ub, xhat - X[0]
+
+
+def gn_qp_step(orc, rb, cfg, X, U, xhat, yref, backend="oracle", chain=None, candidate=None):
+    """The iterate after one full Gauss-Newton QP step from (X [N+1,12], U [N,6]) under the reference yref [N,5].
+
+    backend "oracle": the QP from the oracle's primitives, solved by the bound-inactive fast path (orc.qp_fast); None when the
+    fast path rejects the QP.
+    backend "dense": the QP by the independent assembly of tests/dense_qp.py (`chain`: the kinematic chain), solved with the
+    active set read off `candidate` = (x_pred, u_pred) -- the exact active-set certificate of dense_qp.certify, whatever the
+    engine's QP solver did; the certificate's multipliers and slacks are asserted here, the caller compares the iterate."""
+    if backend == "dense":
+        import dense_qp as dq
+
+        qp = dq.assemble(chain, cfg, X, U, xhat, yref)
+        cert = dq.certify(qp, candidate[0] - X, candidate[1] - U)
+        assert cert["min_multiplier"] >= 0 and cert["min_slack"] >= 0, cert
+        return X + cert["dX"], U + cert["dU"]
+    q = orc.qp_fast(*oracle_qp(orc, rb, cfg, X, U, xhat, yref))
     if not q["accepted"]:
         return None
-    return X + q["w"][:, 6:], U + q["w"][:N, :6]
+    return X + q["w"][:, 6:], U + q["w"][:cfg["N"], :6]
 
 
 def dense_nlp_solve(orc, rb, cfg, xhat, yref, u_init):

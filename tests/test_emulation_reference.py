@@ -71,8 +71,11 @@ def test_rti_step_after_a_reference_change_is_the_exact_qp_step(orc, ur10, ur10_
     import emu_ref
 
     N, steps = 20, 12
-    cfgs = [_cfg(prediction_horizon=N, simulation_time=0.01 * steps, q_0=_q0()),
-            _cfg(prediction_horizon=N, simulation_time=0.01 * steps, w_u=0.002)]
+    # qp_tol 1e-14: an interior-point step (fast path rejected) stops with its active components qp_tol / lam off their bounds,
+    # which the 1e-10 below has to cover for multipliers down to 1e-4
+    so = {"nlp_solver_type": "SQP_RTI", "qp_tol": 1e-14, "qp_solver_iter_max": 200}
+    cfgs = [_cfg(prediction_horizon=N, simulation_time=0.01 * steps, q_0=_q0(), solver_options=so),
+            _cfg(prediction_horizon=N, simulation_time=0.01 * steps, w_u=0.002, solver_options=so)]
     ctl = emu_ref.Controller(cfgs, ur10, waves=4)
     rng = np.random.default_rng(5)
     plants = [_plant(orc, c, rng) for c in cfgs]
@@ -86,15 +89,19 @@ def test_rti_step_after_a_reference_change_is_the_exact_qp_step(orc, ur10, ur10_
         if prev is not None and k >= 4:
             for i, c in enumerate(cfgs):
                 if out["qp_iter"][i] != 1:
-                    continue                                   # the fast path rejected: an interior-point solve, not checked here
-                want = rc.gn_qp_step(orc, ur10_rb, c, prev["x_pred"][i], prev["u_pred"][i], x[i], y[i])
-                assert want is not None, f"step {k} sim {i}: the engine took the fast path, the oracle's rejects"
+                    # the fast path rejected: an interior-point solve, held against the exact active-set certificate of the
+                    # independently assembled QP (tests/dense_qp.py)
+                    want = rc.gn_qp_step(orc, ur10_rb, c, prev["x_pred"][i], prev["u_pred"][i], x[i], y[i], backend="dense",
+                                         chain=ur10, candidate=(out["x_pred"][i], out["u_pred"][i]))
+                else:
+                    want = rc.gn_qp_step(orc, ur10_rb, c, prev["x_pred"][i], prev["u_pred"][i], x[i], y[i])
+                    assert want is not None, f"step {k} sim {i}: the engine took the fast path, the oracle's rejects"
                 np.testing.assert_allclose(out["x_pred"][i], want[0], atol=1e-10, rtol=0, err_msg=f"step {k} sim {i}")
                 np.testing.assert_allclose(out["u_pred"][i], want[1], atol=1e-10, rtol=0, err_msg=f"step {k} sim {i}")
                 checked += 1
         prev = out
         x = np.stack([plants[i](x[i], out["u0"][i]) for i in range(len(cfgs))])
-    assert checked >= 8
+    assert checked == (steps - 4) * len(cfgs)
 
 
 def test_full_sqp_converges_to_the_nlp_of_the_reference(orc, ur10, ur10_rb):
