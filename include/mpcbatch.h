@@ -240,6 +240,28 @@ int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream);
  * mpcb_step(h, io, reset, s) == mpcb_step_ref(h, io, NULL, 0, reset, s).  MPCB_ESTATE on a handle not set up as a controller. */
 int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, int reset, void *stream);
 
+/* ---- the controller step with a warm start chosen per simulation ---- */
+#define MPCB_WARM_CARRY 0        /* iterate, linearisation and QP memory carry over (mpcb_step)                       */
+#define MPCB_WARM_RESET 1        /* this simulation starts from the initial guess, as `reset` does for the whole batch  */
+#define MPCB_WARM_SHIFT 2        /* the carried solver memory moves one stage towards stage 0 before the step           */
+/* mpcb_step_ref with one mode per simulation: `warm` is a DEVICE array [batch] of MPCB_WARM_* (any other value counts as
+ * MPCB_WARM_CARRY), read during the launch only; NULL means MPCB_WARM_CARRY for all, and then this is mpcb_step_ref exactly:
+ * mpcb_step_ref(h, io, y, rc, reset, s) == mpcb_step_warm(h, io, y, rc, NULL, reset, s).
+ * MPCB_WARM_SHIFT is the shift initialisation of a receding horizon whose schedule moves one stage per step: the previous solution
+ * at stage k + 1 is the guess for stage k.  For a simulation of horizon N (its own horizon on a ragged batch):
+ *   u_k <- u_{k+1} for k = 0..N-2, u_{N-1} is held;  x_k <- x_{k+1} for k = 0..N-1;
+ *   x_N <- Ad x_N + Bd u_{N-1} from the old x_N and the held input, so the tail stays dynamically feasible;
+ *   every other quantity carried between steps and indexed by stage moves with its stage, the last stage's duplicated: the equality
+ *   multipliers (stages 0..N), the bound multipliers and slacks of the QP memory and the per-stage merit weights (stages 0..N-1);
+ *   stage 0 has no state bounds, so what arrives there from stage 1's state bounds is zeroed;
+ *   what is kept per simulation stays (the last feedback state, the fast-path suspension, the x_0 merit weights);
+ *   the carried linearisation of a shifted simulation is stale: that simulation linearises again at the start of the step, as
+ *   after ref_changed, and its neighbours keep theirs;  rows past a simulation's own horizon are not touched.
+ * N = 1 is legal (nothing moves in u, x_0 <- x_1, x_1 is propagated again).  On the first step after mpcb_setup_controller, or with
+ * `reset` != 0, every mode is a reset.  MPCB_ESTATE on a handle not set up as a controller. */
+int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed,
+                   const int *warm /* DEVICE [batch] or NULL */, int reset, void *stream);
+
 /* ---- the controller step on either kernel family ---- */
 #define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
 #define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */

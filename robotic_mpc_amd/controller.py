@@ -15,6 +15,11 @@ acados does.
 A controller regulates to the task reference packed from each configuration (``px_ref``, ``vy_ref``) unless it is given one
 with ``set_reference`` / ``step(..., yref=...)``: per simulation and per stage of the horizon, like acados'
 ``set(k, 'yref', ...)`` between solves, and in force until it is changed (``default_reference()`` is the packed one).
+
+Each simulation chooses per step how its solver memory enters the step: ``step(..., shift=True)`` (or a [B] bool mask) moves
+the previous solution one stage towards stage 0 first -- the shift initialisation of a receding horizon whose schedule
+advances one stage per step -- and ``reset(mask)`` restarts the masked simulations alone (an episode that ended, a solve that
+failed) while the others keep their warm start.
 """
 from __future__ import annotations
 
@@ -23,7 +28,7 @@ from typing import Dict, Mapping, Optional, Sequence
 import numpy as np
 
 from . import config as cfgmod, packing
-from .engine import CONTROLLER_ENGINES, STEP_FIELDS, MpcBatchEngine
+from .engine import CONTROLLER_ENGINES, STEP_FIELDS, WARM_RESET, WARM_SHIFT, MpcBatchEngine
 
 NREF = 5    # task outputs with a reference (MPCB_NREF, include/mpcbatch.h)
 
@@ -90,6 +95,29 @@ class BatchController:
         self._ref_changed = False
         self._ref_stream = None
         self._step_stream = None
+        # per-simulation warm start: the simulations reset(mask) marked for the next step ([B] bool, host or device), and the
+        # controller's own int32 [B] mode buffer the step composes on its stream
+        self._reset_mask = None
+        self._warm = None
+
+    def _check_mask(self, mask, name):
+        """Validates a per-simulation mask ([B] bool, a numpy array or a tensor on the controller's device) without touching the
+        device; returns it."""
+        import torch
+
+        if isinstance(mask, np.ndarray):
+            shape, dtype_ok = tuple(mask.shape), mask.dtype == np.bool_
+        elif isinstance(mask, torch.Tensor):
+            shape, dtype_ok = tuple(mask.shape), mask.dtype == torch.bool
+            if mask.device.type != "cuda" or mask.device.index != self.device:
+                raise ValueError(f"{name} must live on cuda:{self.device}, got {mask.device}")
+        else:
+            raise ValueError(f"{name} must be a bool torch tensor or numpy array of shape ({self.batch},), got {type(mask).__name__}")
+        if shape != (self.batch,):
+            raise ValueError(f"{name} must have shape ({self.batch},), got {shape}")
+        if not dtype_ok:
+            raise ValueError(f"{name} must be bool, got {mask.dtype}")
+        return mask
 
     def _buffers(self, predict: bool):
         """The output buffers of a step; x_pred / u_pred ([B, N+1, 12] + [B, N, 6], N the longest horizon) only from the first step
@@ -182,7 +210,7 @@ class BatchController:
         self._ref_stream = cur
         self._ref_on, self._ref_changed = True, True
 
-    def step(self, xhat, predict: bool = False, yref=None) -> Dict:
+    def step(self, xhat, predict: bool = False, yref=None, shift=False) -> Dict:
         """One MPC step of every controller from the feedback states ``xhat`` ([B, 12] q; qdot, float64: a tensor on the
         controller's device, or a numpy array that is copied there).
 
@@ -192,19 +220,34 @@ class BatchController:
         is synchronised.  The returned tensors are the controller's own buffers: the next ``step`` overwrites them, so clone
         what must outlive it.
 
-        ``yref`` (optional) is ``set_reference(yref)`` before the step: the reference then stays in force for later steps."""
+        ``yref`` (optional) is ``set_reference(yref)`` before the step: the reference then stays in force for later steps.
+
+        ``shift``: ``True`` starts every simulation that is not being reset from its previous solution moved one stage towards
+        stage 0 (u_k <- u_{k+1} with the last input held, x_k <- x_{k+1} with x_N propagated by the model, multipliers and QP
+        memory moved with their stages; include/mpcbatch.h, MPCB_WARM_SHIFT) and linearises there; a [B] bool mask (numpy, or a
+        tensor on the controller's device) shifts those simulations only.  It applies to this step alone.  On the first step
+        and after ``reset()`` there is nothing to shift: the step starts from the initial guess."""
         import torch
 
         if yref is not None:
             self._check_reference(yref)
+        shift_all = isinstance(shift, (bool, np.bool_))
+        if not shift_all:
+            self._check_mask(shift, "shift")
         x = self._xhat(xhat)
         io = dict(self._buffers(predict), xhat=x)
         if yref is not None:
             self.set_reference(yref)
         stream = torch.cuda.current_stream(self.device)
-        if self._ref_on or self._ref_changed:
-            if self._ref_on and self._ref_stream is not None and self._ref_stream != stream:
-                stream.wait_stream(self._ref_stream)      # the copy of the reference lands before the step reads it
+        warm = None
+        if self._reset_mask is not None or not shift_all or bool(shift):
+            warm = self._compose_warm(shift, shift_all, stream)
+        if self._ref_on and self._ref_stream is not None and self._ref_stream != stream:
+            stream.wait_stream(self._ref_stream)      # the copy of the reference lands before the step reads it
+        if warm is not None:
+            self.engine.step_warm(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm,
+                                  reset=self._reset, stream=stream.cuda_stream)
+        elif self._ref_on or self._ref_changed:
             self.engine.step_ref(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, reset=self._reset,
                                  stream=stream.cuda_stream)
         else:
@@ -212,12 +255,48 @@ class BatchController:
         self._step_stream = stream
         self._reset = False
         self._ref_changed = False
+        self._reset_mask = None
         return {k: v for k, v in io.items() if k != "xhat"}
 
-    def reset(self):
+    def _compose_warm(self, shift, shift_all, stream):
+        """The int32 [B] modes of the next step in the controller's own buffer, written on the step's stream: reset where
+        ``reset(mask)`` marked, shift where asked among the others, carry elsewhere."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        if self._warm is None:
+            self._warm = torch.empty((self.batch,), dtype=torch.int32, device=dev)
+        if self._step_stream is not None and self._step_stream != stream:
+            stream.wait_stream(self._step_stream)         # a step still reading the buffer on another stream finishes first
+        on_dev = lambda m: torch.from_numpy(np.ascontiguousarray(m)).to(dev) if isinstance(m, np.ndarray) else m
+        if shift_all:
+            self._warm.fill_(WARM_SHIFT if shift else 0)
+        else:
+            self._warm.copy_(on_dev(shift).to(torch.int32) * WARM_SHIFT)
+        if self._reset_mask is not None:
+            self._warm.masked_fill_(on_dev(self._reset_mask), WARM_RESET)
+        return self._warm
+
+    def reset(self, mask=None):
         """The next step starts from the initial guess (x_k = [q_0; qdot_0], u_k = 0, multipliers 0) again.  The task
-        reference in force stays."""
-        self._reset = True
+        reference in force stays.
+
+        ``mask`` (a [B] bool numpy array, or tensor on the controller's device) restarts the marked simulations only; the others
+        keep their warm start.  Masks given before the next step accumulate."""
+        if mask is None:
+            self._reset = True
+            return
+        import torch
+
+        mask = self._check_mask(mask, "mask")
+        if self._reset_mask is None:
+            self._reset_mask = mask.copy() if isinstance(mask, np.ndarray) else mask.clone()
+        elif isinstance(self._reset_mask, np.ndarray) and isinstance(mask, np.ndarray):
+            self._reset_mask |= mask
+        else:
+            dev = torch.device("cuda", self.device)
+            as_t = lambda m: torch.from_numpy(m).to(dev) if isinstance(m, np.ndarray) else m
+            self._reset_mask = as_t(self._reset_mask) | as_t(mask)
 
     def launch_info(self) -> Dict[str, int]:
         """Geometry of the step kernel: kernel family (0 latency, 1 throughput engine), wavefronts per simulation, LDS pool."""

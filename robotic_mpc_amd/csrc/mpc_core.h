@@ -3118,17 +3118,68 @@ struct Engine {
     }
 
     // ==================================================================== controller step
+    // WARM_SHIFT (mpc_layout.h, shift_class_*): the carried records of stages 1..N move to stages 0..N-1, in place.  Stage k reads stage
+    // k + 1, which another lane overwrites: a block of stages goes HBM -> chunk pool in one phase and pool -> HBM in the next, the
+    // workgroup barrier of the phase between them, blocks in ascending order (a block's source rows lie above everything written so far).
+    // Correct for any number of wavefronts and any pool size; the host executor runs the same two phases.
+    template <int W, class Cls>
+    MPC_HD void shift_group(double *G, int Nl, Cls &&cls)
+    {
+        double *const buf = ex.pool();
+        const int CH = ex.uni(imax(1, imin(ex.smem().pool_n / W, Nl)));   // destination stages per block
+        for (int k0 = 0; k0 < Nl; k0 += CH) {
+            const int n = imin(CH, Nl - k0) * W;                          // stages k0 .. <- k0 + 1 ..
+            ex.par([&](int lane) {
+                for (int e = lane; e < n; e += NT) buf[e] = gld(G + (size_t)(k0 + 1) * W + e);
+            });
+            ex.par([&](int lane) {
+                for (int e = lane; e < n; e += NT) {
+                    const int r = e / W, col = e - r * W, k = k0 + r, cl = cls(col);
+                    if (shift_moves(cl, k, Nl)) gst(G + (size_t)k0 * W + e, cl == SH_Q && k == 0 ? 0.0 : buf[e]);
+                }
+            });
+        }
+    }
+    MPC_PASS void shift_pass()
+    {
+        Smem &sm = ex.smem();
+        const int Nl = ex.uni(sm.n_hor);
+        shift_group<W1>(sm.w.G1, Nl, [](int col) { return shift_class_g1(col); });
+        // (SQP_RTI keeps nothing in G5)
+        if (c.pb->solver_type == 0) shift_group<W5>(sm.w.G5, Nl, [](int col) { return shift_class_g5(col); });
+        // x_N <- Ad x_N + Bd u_{N-1}: the old x_N and the held input
+        double *const buf = ex.pool();
+        ex.par([&](int lane) {
+            if (lane < NX) buf[lane] = gld(sm.w.G1 + (size_t)Nl * W1 + O_X + lane);
+            if (lane >= 16 && lane < 16 + NU) buf[lane] = gld(sm.w.G1 + (size_t)(Nl - 1) * W1 + O_U + lane - 16);
+        });
+        ex.par([&](int lane) {
+            if (lane < NX) gst(sm.w.G1 + (size_t)Nl * W1 + O_X + lane, shift_tail(sm.P, lane, buf, buf + 16));
+        });
+    }
+
     // One solver.solve() from the caller's feedback state (mpcb_step; acados set(0,'lbx'|'ubx',x), solve(), get(0,'u'),
     // simulator.py:210-221) for instance `inst`: the iterate, the linearisation and the fast-path suspension carry over from the
     // previous step in the workspace as between two rollout launches; `reset` starts from the initial guess instead.  No plant step,
     // no log columns: io.u0 is the plant's input, the caller's plant produces the next io.xhat.
+    // WARM (the kernels of mpcb_step_warm): io.warm gives this simulation's own mode -- WARM_RESET is `reset` for it alone, WARM_SHIFT
+    // moves its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
+    template <bool WARM = false>
     MPC_HD void control_step(const StepIO &io, int inst, bool reset)
     {
         Smem &sm = ex.smem();
         Ws &w = c.w;
         bool lin_valid = false;
-        if (reset) initial_guess();
+        int mode = WARM_CARRY;
+        if constexpr (WARM) {
+            if (!reset && io.warm != nullptr) mode = ex.uni(io.warm[inst]);   // (with the batch-wide reset every mode is a reset)
+        }
+        if (reset || mode == WARM_RESET) initial_guess();
         else load_carry(lin_valid);
+        if constexpr (WARM) {
+            // the linearisation carried with a shifted iterate was formed at the unshifted one: linearise again, like after a new reference
+            if (mode == WARM_SHIFT) { shift_pass(); lin_valid = false; }
+        }
         // a new task reference: the carried linearisation was formed against the old one -- linearise again (everything else carries)
         if (io.ref_changed) lin_valid = false;
         const TaskRef ref{io.yref ? io.yref + (size_t)inst * N * NTASK : nullptr};

@@ -39,6 +39,12 @@ void launch_step(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t 
 const void *stream_step_kernel();
 void launch_stream_step(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
                         size_t ws_stride, const StepIO &io, int reset);
+// ... and the kernels of both engines that read a per-simulation warm-start mode (mpcb_step_warm): mpc_step_warm.hip, mpc_stream_step_warm.hip
+const void *step_warm_kernel(int waves_per_sim, int wpe);
+void launch_step_warm(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                      const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
+void launch_stream_step_warm(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                             size_t ws_stride, const StepIO &io, int reset);
 }  // namespace mpcb
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
@@ -495,10 +501,11 @@ static const void *latency_kernel(const mpcb_handle *h)
 
 // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
 // handle can ask for, right before the launch
-static int raise_lds_limit(mpcb_handle *h)
+static int raise_lds_limit(mpcb_handle *h, bool warm = false)
 {
     static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(latency_kernel(h), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    HIPCHK(h, hipFuncSetAttribute(warm ? step_warm_kernel(h->waves_per_sim, h->wpe) : latency_kernel(h),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     return MPCB_OK;
 }
 
@@ -605,6 +612,12 @@ int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream)
 
 int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, int reset, void *stream)
 {
+    return mpcb_step_warm(h, io, yref, ref_changed, nullptr, reset, stream);
+}
+
+// (warm == NULL: the kernels of mpcb_step / mpcb_step_ref, which know no modes; otherwise the warm-start kernels)
+int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset, void *stream)
+{
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
     if (!h->controller) return fail(h, MPCB_ESTATE, "mpcb_step needs a handle set up by mpcb_setup_controller");
@@ -617,11 +630,13 @@ int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, in
     std::memcpy(&sio, io, sizeof(mpcb_step_io));
     sio.yref = yref;
     sio.ref_changed = ref_changed != 0 ? 1 : 0;
+    sio.warm = warm;
     const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
     if (h->engine == MPCB_ENGINE_STREAM) {
         // throughput engine: one wavefront per simulation, static LDS only, no work queue
         HIPCHK(h, hipEventRecord(h->ev0, s));
-        launch_stream_step(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        if (warm) launch_stream_step_warm(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        else launch_stream_step(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipEventRecord(h->ev1, s));
         h->last_stream = s;
@@ -631,10 +646,14 @@ int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, in
         return MPCB_OK;
     }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    if (int rc = raise_lds_limit(h)) return rc;
+    if (int rc = raise_lds_limit(h, warm != nullptr)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
-    launch_step(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio, rs,
-                h->pool_doubles);
+    if (warm)
+        launch_step_warm(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
+                         rs, h->pool_doubles);
+    else
+        launch_step(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio, rs,
+                    h->pool_doubles);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev1, s));
     h->last_stream = s;

@@ -142,7 +142,8 @@ struct Outputs {
 
 // Device pointers of one controller step (mpcb_step_io, then the task reference of mpcb_step_ref): the caller's feedback states in,
 // solver.get(0,'u') and the step's statistics out, batch-major.  x_pred / u_pred may be null (not written).  The members past
-// u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged".
+// u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged", one that stops
+// at ref_changed "every simulation carries its solver memory".
 struct StepIO {
     const double *xhat;  // [batch][12]
     double *u0;          // [batch][6]
@@ -156,7 +157,36 @@ struct StepIO {
     double *u_pred;      // [batch][N][6] or null
     const double *yref = nullptr;   // [batch][N][NTASK] targets of g1..g5 at stages 0..N-1, or null: each instance's packed g_ref
     int ref_changed = 0;            // != 0: the reference differs from the previous step's (the carried linearisation is stale)
+    const int *warm = nullptr;      // [batch] WARM_* of each simulation (mpcb_step_warm), or null: WARM_CARRY for all
 };
+
+// How a simulation's solver memory enters a controller step (MPCB_WARM_*); any other value is WARM_CARRY.
+constexpr int WARM_CARRY = 0, WARM_RESET = 1, WARM_SHIFT = 2;
+// WARM_SHIFT moves the carried solver memory of a simulation of horizon N one stage towards stage 0.  Which stages hold a column of
+// a stage record decides how it moves:
+//   SH_X  a quantity of stages 0..N (states, state steps, equality multipliers): k <- k + 1 for k < N, stage N's stays (duplicated)
+//   SH_U  a quantity of stages 0..N-1 (inputs, input steps, input-bound multipliers and slacks): k <- k + 1 for k < N - 1, stage N-1's
+//         stays (the input is held)
+//   SH_Q  as SH_U, of the state bounds (stages 1..N-1): stage 0 has none, so what arrives there is zeroed
+// Afterwards x_N <- Ad x_N + Bd u_{N-1} from the old x_N and the held input (shift_tail): the tail stays dynamically feasible.
+constexpr int SH_X = 0, SH_U = 1, SH_Q = 2;
+MPC_HD int shift_class_bounds(int q) { return q % 12 < 6 ? SH_U : SH_Q; }   // q: column in [lower 12 | upper 12] x n, each u 6 | q 6
+// column c of a G1 record (and of the QP iterate's second home on the throughput engine, G3 [O_DW, W3) = G1 [O_QW, W1))
+MPC_HD int shift_class_g1(int c) { return c < O_U ? SH_X : c < O_QW + NU ? SH_U : c < O_QLAM ? SH_X : shift_class_bounds(c - O_QLAM); }
+// column c of a G5 record: NLP multipliers, trial point, merit weights
+MPC_HD int shift_class_g5(int c)
+{
+    return c < O_NLAM ? SH_X : c < O_TX ? shift_class_bounds(c - O_NLAM) : c < O_TU ? SH_X : c < O_MW ? SH_U
+         : c < O_MW + 12 ? SH_X : c < O_MW + 36 ? shift_class_bounds(c - O_MW - 12) : SH_X;
+}
+// does stage k of a column of class cl take stage k + 1's value?
+MPC_HD bool shift_moves(int cl, int k, int N) { return k < (cl == SH_X ? N : N - 1); }
+// component i of the new x_N: x [12] the old x_N, u [6] the held u_{N-1}
+template <class X, class U>
+MPC_HD double shift_tail(const InstParams &P, int i, const X &x, const U &u)
+{
+    return i < 6 ? x[i] + P.a12[i] * x[6 + i] + P.b1[i] * u[i] : P.a22[i - 6] * x[i] + P.b2[i - 6] * u[i - 6];
+}
 
 // The task reference of one instance in a controller step: its [N][NTASK] rows of StepIO::yref, or null for the packed
 // g_ref = [0, 1, 0, px_ref, vy_ref].  Also the tag that selects the reference-tracking variant of a pass (an overload taking

@@ -2216,11 +2216,65 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
     c.store(w.state);
 }
 
+// WARM_SHIFT (mpc_layout.h, shift_class_*): this simulation's carried records of stages 1..N move to stages 0..N-1 of its own horizon,
+// in place -- the G1 record, the QP iterate's second home G3 [O_DW, W3) (Carry::cur says which of the two is live; the other one is
+// scratch, moved along rather than told apart), and with full SQP the G5 record.  A plain copy in 16-byte items (every column class
+// spans whole items), SH_R items per lane in flight: the pass moves ~1.4 KB per stage once, a fraction of what one lin_pass streams,
+// and has no use for the ring.  One wavefront issues its vector-memory operations in order: all loads of a block are issued before
+// its stores, a later block loads only rows above everything stored so far, and the row it stores into was loaded by the block
+// before -- no wait between blocks.  The passes that follow fetch these records through the ring: stores drained first.
+constexpr int SH_R = 12;
+template <bool SQP>
+SE_PASS void shift_pass(int N)
+{
+    SSmem &sm = g_ssm;
+    const SWs w = sm.w;
+    const int lane = threadIdx.x;
+    constexpr int I1 = W1 / 2, I3 = (W3 - O_DW) / 2, IPS = I1 + I3 + (SQP ? W5 / 2 : 0);   // 16-byte items per stage
+    static_assert(W1 % 2 == 0 && O_DW % 2 == 0 && W3 % 2 == 0 && W5 % 2 == 0 && (W1 + W2) % 2 == 0, "shift items");
+    const int ldd = w.ld / 8, c3 = (int)(w.G3 - w.G1) + O_DW, c5 = SQP ? (int)(w.G5 - w.G1) : 0;
+    MPC_GLOBAL double *const g = (MPC_GLOBAL double *)w.G1;
+    // item i of a stage: its column in the stage record and its class
+    const auto col_of = [&](int i) { return i < I1 ? 2 * i : i < I1 + I3 ? c3 + 2 * (i - I1) : c5 + 2 * (i - I1 - I3); };
+    const auto cls_of = [&](int i) {
+        return i < I1 ? shift_class_g1(2 * i) : i < I1 + I3 ? shift_class_g1(O_QW + 2 * (i - I1)) : shift_class_g5(2 * (i - I1 - I3));
+    };
+    const int items = N * IPS;                                   // destination stages 0..N-1
+    for (int base = 0; base < items; base += SH_R * WAVE) {
+        D2 v[SH_R];
+#pragma unroll
+        for (int r = 0; r < SH_R; r++) {
+            const int e = imin(base + r * WAVE + lane, items - 1), k = e / IPS, i = e - k * IPS;
+            v[r] = *(MPC_GLOBAL const D2 *)(g + (size_t)(k + 1) * ldd + col_of(i));
+        }
+#pragma unroll
+        for (int r = 0; r < SH_R; r++) {
+            const int e = base + r * WAVE + lane;
+            if (e < items) {
+                const int k = e / IPS, i = e - k * IPS, cl = cls_of(i);
+                if (cl == SH_Q && k == 0) v[r] = D2{0.0, 0.0};
+                if (shift_moves(cl, k, N)) *(MPC_GLOBAL D2 *)(g + (size_t)k * ldd + col_of(i)) = v[r];
+            }
+        }
+    }
+    // x_N <- Ad x_N + Bd u_{N-1}: the old x_N (no store above touches row N) and the held input (nor u of row N-1)
+    double xn = 0.0;
+    if (lane < NX) {
+        const MPC_GLOBAL double *x = g + (size_t)N * ldd + O_X, *u = g + (size_t)(N - 1) * ldd + O_U;
+        xn = shift_tail(sm.P, lane, x, u);
+    }
+    if (lane < NX) g[(size_t)N * ldd + O_X + lane] = xn;
+    __builtin_amdgcn_s_waitcnt(0);                                // the shifted records are in memory before the first pass reads them
+    fence();
+}
+
 // Controller step (mpcb_step, mpc_stream_step.hip): ONE step of rollout<FT>'s loop for simulation `inst`, from the caller's state
 // io.xhat, with no plant and no logs.  The solver memory carries over in the workspace as between two rollout launches (Carry); `reset`
 // starts from the acados initial guess instead (the rollout's step 0).  Every step is the last of its launch: its cost and residual
 // norms are never deferred to the next step's first pass, since the caller reads them when the launch returns.
-template <class FT>
+// WARM (the kernel of mpcb_step_warm): io.warm gives this simulation's own mode -- WARM_RESET is `reset` for it alone, WARM_SHIFT moves
+// its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
+template <class FT, bool WARM = false>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
@@ -2229,8 +2283,20 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
     const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), NMAX = pb.N;
     const SWs w = sm.w;
     Carry c;
-    if (uni(reset ? 1 : 0)) initial_guess<FT>(pb, N);
+    int mode = WARM_CARRY;
+    if constexpr (WARM) {
+        if (!reset && io.warm != nullptr) mode = uni(io.warm[inst]);          // (with the batch-wide reset every mode is a reset)
+    }
+    if (uni(reset || mode == WARM_RESET ? 1 : 0)) initial_guess<FT>(pb, N);
     else c.load(w.state);
+    if constexpr (WARM) {
+        // the linearisation carried with a shifted iterate was formed at the unshifted one: linearise again, like after a new reference
+        if (mode == WARM_SHIFT) {
+            if (pb.solver_type == 0) shift_pass<true>(N);
+            else shift_pass<false>(N);
+            c.lin_valid = false;
+        }
+    }
     // a new task reference: the carried linearisation was formed against the old one -- linearise again (everything else carries).
     // The reference rows are strided by the batch's longest horizon; rows past this simulation's own are never read.
     if (io.ref_changed) c.lin_valid = false;

@@ -70,6 +70,10 @@ STEP_FIELDS = (
 CONTROLLER_ENGINES = {"auto": -1, "latency": 0, "stream": 1}
 
 
+# warm-start modes of step_warm (MPCB_WARM_*, include/mpcbatch.h)
+WARM_CARRY, WARM_RESET, WARM_SHIFT = 0, 1, 2
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -78,7 +82,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
-            "mpcb_step_ref")
+            "mpcb_step_ref", "mpcb_step_warm")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -124,6 +128,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_setup_controller_on.argtypes = [C.c_void_p, C.POINTER(MpcbProblem), _dp, _dp, C.c_int]
     lib.mpcb_controller_engine_for.argtypes = [C.POINTER(MpcbProblem), C.c_int]
     lib.mpcb_step_ref.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, C.c_int, C.c_void_p]
+    lib.mpcb_step_warm.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -312,6 +317,19 @@ class MpcBatchEngine:
         yp = C.cast(C.c_void_p(yref.data_ptr()), _dp) if yref is not None else None
         self._check(self.lib.mpcb_step_ref(self._h, C.byref(r), yp, int(bool(ref_changed)), int(bool(reset)), C.c_void_p(stream)),
                     "mpcb_step_ref")
+
+    def step_warm(self, io, yref=None, ref_changed: bool = False, warm=None, reset: bool = False, stream: Optional[int] = None):
+        """mpcb_step_warm: step_ref() with one warm-start mode per simulation -- `warm` a contiguous int32 device tensor [batch] of
+        WARM_CARRY / WARM_RESET / WARM_SHIFT, or None: every simulation carries, which is step_ref() exactly."""
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._step_struct(io)
+        yp = C.cast(C.c_void_p(yref.data_ptr()), _dp) if yref is not None else None
+        wp = C.cast(C.c_void_p(warm.data_ptr()), _ip) if warm is not None else None
+        self._check(self.lib.mpcb_step_warm(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), C.c_void_p(stream)),
+                    "mpcb_step_warm")
 
     def debug_task_lin(self, cfgs: Sequence[Dict], chain, x: np.ndarray) -> np.ndarray:
         """Diagnostic: the device linearisation at points x[i] = [q; qdot] with the parameters of cfgs[i];

@@ -11,9 +11,13 @@ per (batch, engine) pair.
 sizes: every batch runs on each engine in turn, alternating, in one process.  The rollout is timed on the same family
 (MPCB_ENGINE) unless --skip-rollout.  `--ref` takes one or more task-reference modes: none (the packed reference), once (a
 per-stage tracking reference set before the loop) and every (a new one every step: the copy and one more linearisation per step).
+`--warm` takes one or more warm starts: carry (step k starts from step k-1's iterate at the same stages) and shift (from that
+iterate moved one stage, BatchController.step(shift=True): the shift pass and one more linearisation per step).  When it is given,
+each line also reports the closed-loop effect on a schedule that slides one stage per step (row j of step k is stage k + j of one
+ramp): the medians over steps 100.. of the stationarity residual and of max |u_pred - the previous step's u_pred|.
 
     python scripts/controller_rate.py [--batch 256 ...] [--engine latency|stream ...] [--N 100] [--steps 600] [--solver SQP_RTI]
-                                      [--skip-rollout] [--ref none|once|every ...]
+                                      [--skip-rollout] [--ref none|once|every ...] [--warm carry|shift ...]
 """
 import argparse
 import json
@@ -62,14 +66,40 @@ def main():
     ap.add_argument("--skip-rollout", action="store_true")
     # task reference: none (the packed one), set once before the loop, or a new one every step (one more linearisation per step)
     ap.add_argument("--ref", nargs="+", choices=("none", "once", "every"), default=["none"])
+    # warm start of every step: the previous iterate as it is, or moved one stage (the shift pass + one more linearisation per step)
+    ap.add_argument("--warm", nargs="+", choices=("carry", "shift"), default=None)
     args = ap.parse_args()
     for B in args.batch:
         for eng in args.engine:
             for ref in args.ref:
-                measure(args, B, eng, ref)
+                for warm in args.warm or ["carry"]:
+                    measure(args, B, eng, ref, warm, sliding=args.warm is not None)
 
 
-def measure(args, B, eng, ref="none"):
+def sliding_medians(ctl, plant, x0, S, shift, lo=100):
+    """The closed loop on a schedule that slides one stage per step: medians over steps lo.. (and over the batch) of the
+    stationarity residual and of max |u_pred - previous u_pred|."""
+    import torch
+
+    base = ctl.default_reference()
+    t = torch.arange(ctl.N + S, dtype=torch.float64, device=base.device)
+    px = base[:, :1, 3] - 0.01 + 0.0002 * t[None, :]
+    vy = base[:, :1, 4] + 0.01 * torch.sin(0.3 * t)[None, :]
+    ctl.reset()
+    x, prev, res, du = x0, None, [], []
+    for k in range(S):
+        y = base.clone()
+        y[:, :, 3], y[:, :, 4] = px[:, k:k + ctl.N], vy[:, k:k + ctl.N]
+        out = ctl.step(x, predict=True, yref=y, shift=shift)
+        if k >= lo:
+            res.append(out["residuals"][:, 0].clone())
+            du.append((out["u_pred"] - prev).abs().amax(dim=(1, 2)))
+        prev = out["u_pred"].clone()
+        x = plant(x, out["u0"])
+    return dict(steps=[lo, S], residual_stat_median=float(torch.stack(res).median()), du_pred_median=float(torch.stack(du).median()))
+
+
+def measure(args, B, eng, ref="none", warm="carry", sliding=False):
     import numpy as np
     import torch
 
@@ -103,7 +133,10 @@ def measure(args, B, eng, ref="none"):
             if events is not None:
                 events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
                 events[-1][0].record()
-            u = ctl.step(x, yref=sched[k % 2] if ref == "every" else None)["u0"]
+            if warm == "shift":
+                u = ctl.step(x, yref=sched[k % 2] if ref == "every" else None, shift=True)["u0"]
+            else:
+                u = ctl.step(x, yref=sched[k % 2] if ref == "every" else None)["u0"]
             if events is not None:
                 events[-1][1].record()
             x = plant(x, u)
@@ -121,10 +154,12 @@ def measure(args, B, eng, ref="none"):
     closed_loop(ev)
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
-    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, step_loop_ms=round(loop_ms, 3),
+    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, step_loop_ms=round(loop_ms, 3),
                step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
                step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
                launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
+    if sliding and S > 110:
+        out.update(sliding_schedule=sliding_medians(ctl, plant, x0, S, warm == "shift"))
     if not args.skip_rollout:
         bc = bench.workload_configs(B, args.N, 0.01 * S, seed=0, solver=args.solver)
         os.environ["MPCB_ENGINE"] = eng                 # the rollout on the same kernel family
