@@ -262,6 +262,28 @@ int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, in
 int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed,
                    const int *warm /* DEVICE [batch] or NULL */, int reset, void *stream);
 
+/* ---- the controller step with the feedback gain and the reference sensitivity of u0 ---- */
+/* For an SQP_RTI step whose QP was solved by an accepted bound-inactive fast-path attempt (status 0), u0 = U_0 + du_0 with du the
+ * solution of the bound-free Gauss-Newton QP at the carried linearisation point: an affine function of the feedback state xhat and of
+ * the task reference.  Its exact Jacobians, the linearisation point held fixed (the derivatives of this step's QP):
+ *   du0_dx[i]        = d u0 / d xhat            6 x 12 (minus the stage-0 Riccati gain)
+ *   du0_dyref[i][k]  = (d u0 / d yref_k)'       5 x 6, k = 0 .. N-1, N the longest horizon of the batch
+ * Row k = 0 is exactly zero (x_0 is pinned to xhat); on a ragged batch so are the rows k >= the simulation's own horizon.
+ * Where they do not exist -- the QP went through the interior-point loop (fast path off, attempt rejected, attempt skipped during a
+ * back-off suspension) or status != 0 -- every entry of both arrays of that simulation is NaN and valid[i] = 0.  Sensitivities through
+ * active bounds, and of x_pred / u_pred, are not provided. */
+typedef struct {
+    double *du0_dx;     /* [batch][6][12]                          */
+    double *du0_dyref;  /* [batch][N][5][6], N the longest horizon; may be NULL */
+    int    *valid;      /* [batch] 1: exact sensitivities written, 0: NaN */
+} mpcb_step_sens_out;   /* device pointers */
+/* mpcb_step_warm that also writes the sensitivities.  sens == NULL is mpcb_step_warm exactly (the same kernel, bit-identical outputs):
+ * mpcb_step_warm(h, io, y, rc, w, reset, s) == mpcb_step_sens(h, io, y, rc, w, reset, NULL, s).  With sens the step itself (u0,
+ * statistics, prediction, solver memory) is what it is without.  MPCB_EINVAL on a full-SQP controller or with du0_dx or valid NULL;
+ * MPCB_ESTATE on a handle not set up as a controller. */
+int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const mpcb_step_sens_out *sens, void *stream);
+
 /* ---- the controller step on either kernel family ---- */
 #define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
 #define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */

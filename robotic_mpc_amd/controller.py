@@ -20,6 +20,10 @@ Each simulation chooses per step how its solver memory enters the step: ``step(.
 the previous solution one stage towards stage 0 first -- the shift initialisation of a receding horizon whose schedule
 advances one stage per step -- and ``reset(mask)`` restarts the masked simulations alone (an episode that ended, a solve that
 failed) while the others keep their warm start.
+
+``step(..., sens=True)`` also returns the local law behind ``u0``: the feedback gain ``du0_dx`` and the sensitivity to the task
+reference ``du0_dyref`` of the step's QP, exact wherever the bound-inactive fast path solved it (``sens_valid``);
+``robotic_mpc_amd.autograd.differentiable_step`` wraps them into a torch autograd function.
 """
 from __future__ import annotations
 
@@ -99,6 +103,8 @@ class BatchController:
         # controller's own int32 [B] mode buffer the step composes on its stream
         self._reset_mask = None
         self._warm = None
+        # sensitivities of u0 (step(sens=True)): the controller's own du0_dx / du0_dyref / sens_valid buffers, from the first use
+        self._sens = None
 
     def _check_mask(self, mask, name):
         """Validates a per-simulation mask ([B] bool, a numpy array or a tensor on the controller's device) without touching the
@@ -210,7 +216,7 @@ class BatchController:
         self._ref_stream = cur
         self._ref_on, self._ref_changed = True, True
 
-    def step(self, xhat, predict: bool = False, yref=None, shift=False) -> Dict:
+    def step(self, xhat, predict: bool = False, yref=None, shift=False, sens: bool = False) -> Dict:
         """One MPC step of every controller from the feedback states ``xhat`` ([B, 12] q; qdot, float64: a tensor on the
         controller's device, or a numpy array that is copied there).
 
@@ -226,9 +232,23 @@ class BatchController:
         stage 0 (u_k <- u_{k+1} with the last input held, x_k <- x_{k+1} with x_N propagated by the model, multipliers and QP
         memory moved with their stages; include/mpcbatch.h, MPCB_WARM_SHIFT) and linearises there; a [B] bool mask (numpy, or a
         tensor on the controller's device) shifts those simulations only.  It applies to this step alone.  On the first step
-        and after ``reset()`` there is nothing to shift: the step starts from the initial guess."""
+        and after ``reset()`` there is nothing to shift: the step starts from the initial guess.
+
+        ``sens=True`` (SQP_RTI only; ``ValueError`` on a full-SQP batch) adds ``du0_dx`` [B, 6, 12] = d u0 / d xhat,
+        ``du0_dyref`` [B, N, 5, 6] with ``du0_dyref[i, k]`` = (d u0 / d yref_k)' and ``sens_valid`` [B] int32 (the controller's
+        own buffers as well).  They are the exact Jacobians of this step's QP, the linearisation point held fixed, for every
+        simulation whose QP an accepted bound-inactive fast-path attempt solved (``sens_valid`` 1): ``u0 + du0_dx (x - xhat)``
+        is the local feedback law between two solves.  Row k = 0 of ``du0_dyref`` and, on a ragged batch, the rows past a
+        simulation's own horizon are exactly zero.  Where the QP went through the interior-point loop (fast path off, attempt
+        rejected or skipped during a back-off) or the status is not 0, ``sens_valid`` is 0 and every entry is NaN:
+        sensitivities through active bounds are not provided, nor those of ``x_pred`` / ``u_pred``.  The step itself is
+        unchanged by ``sens``.  The extra pass costs 12-20 % of the step rate at N = 100 (latency engine 13 / 15 / 20 % at batch 256 /
+        1024 / 4096, throughput engine 12-14 %; ``profiles/controller_step_rate_sens.txt``); a step without ``sens`` costs what
+        it did."""
         import torch
 
+        if sens and self.configs[0]["solver_type"] != packing.SOLVER_RTI:
+            raise ValueError("step(sens=True) needs an SQP_RTI controller: the sensitivities of u0 are those of one RTI step's QP")
         if yref is not None:
             self._check_reference(yref)
         shift_all = isinstance(shift, (bool, np.bool_))
@@ -244,7 +264,18 @@ class BatchController:
             warm = self._compose_warm(shift, shift_all, stream)
         if self._ref_on and self._ref_stream is not None and self._ref_stream != stream:
             stream.wait_stream(self._ref_stream)      # the copy of the reference lands before the step reads it
-        if warm is not None:
+        if sens:
+            if self._sens is None:
+                dev = torch.device("cuda", self.device)
+                self._sens = dict(du0_dx=torch.zeros((self.batch, 6, 12), dtype=torch.float64, device=dev),
+                                  du0_dyref=torch.zeros((self.batch, self.N, NREF, 6), dtype=torch.float64, device=dev),
+                                  sens_valid=torch.zeros((self.batch,), dtype=torch.int32, device=dev))
+            if self._step_stream is not None and self._step_stream != stream:
+                stream.wait_stream(self._step_stream)     # a step still writing the buffers on another stream finishes first
+            self.engine.step_sens(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm,
+                                  reset=self._reset, stream=stream.cuda_stream,
+                                  sens=dict(du0_dx=self._sens["du0_dx"], du0_dyref=self._sens["du0_dyref"], valid=self._sens["sens_valid"]))
+        elif warm is not None:
             self.engine.step_warm(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm,
                                   reset=self._reset, stream=stream.cuda_stream)
         elif self._ref_on or self._ref_changed:
@@ -256,7 +287,10 @@ class BatchController:
         self._reset = False
         self._ref_changed = False
         self._reset_mask = None
-        return {k: v for k, v in io.items() if k != "xhat"}
+        out = {k: v for k, v in io.items() if k != "xhat"}
+        if sens:
+            out.update(self._sens)
+        return out
 
     def _compose_warm(self, shift, shift_all, stream):
         """The int32 [B] modes of the next step in the controller's own buffer, written on the step's stream: reset where

@@ -29,6 +29,8 @@
 // of the recursion.  One IPM iteration is five passes: factorisation sweep, predictor sweep +
 // step lengths, corrector + backward solve, forward sweep + step lengths, update + residuals.
 #pragma once
+#include <type_traits>
+
 #include "mpc_kin.h"
 #include "mpc_ipm.h"
 #include "mpc_nlp.h"
@@ -2724,7 +2726,8 @@ struct Engine {
     // Returns HPIPM status 0 ok / 1 max-iter / 2 min-step / 3 NaN.
     // `defer_commit` (SQP_RTI): an accepted fast-path candidate is left in the Newton-step slots with commit_pending set; the NLP pass
     // that follows writes it to the QP iterate together with its own update (nlp_direct fuse_commit).
-    MPC_HD int ipm_solve(int *iters_out, bool defer_commit = false)
+    // `fast_accepted` (out, optional): whether this QP is the accepted fast-path candidate (nlp_step's hook asks).
+    MPC_HD int ipm_solve(int *iters_out, bool defer_commit = false, bool *fast_accepted = nullptr)
     {
         const double tol = ex.smem().P.qp_tol;
         Smem &sm = ex.smem();
@@ -2749,6 +2752,7 @@ struct Engine {
 #ifdef MPCB_PROFILE
                     prof[PF_COUNT_IPM] += 1;
 #endif
+                    if (fast_accepted) *fast_accepted = true;
                     *iters_out = 1;
                     return 0;
                 }
@@ -2945,10 +2949,15 @@ struct Engine {
     // The callers bring their NLP pass and line search, as those of se::mpc_step do -- `lin(alpha, do_update, sqp_mult, res4, do_plant,
     // fuse_commit, want_rhs)`: nlp_direct, `search(sqp_iter)`: line_search; the rollout's keep the packed g_ref, the controller
     // step's are the REF instantiations against the caller's task reference when there is one.
-    template <bool PLANT, class Lin, class Search>
+    // `after_qp(exact)` (SQP_RTI; only the kernels of mpcb_step_sens bring one): called between the QP solve and the closing
+    // linearisation, while G2 still holds the linearisation the QP was built from and the Riccati factor is where the sweeps left it;
+    // `exact`: the QP was solved by an accepted fast-path attempt, so the step is affine in x_hat and in the task reference.
+    struct NoHook {};
+    template <bool PLANT, class Lin, class Search, class AfterQp = NoHook>
     MPC_HD int nlp_step(bool &lin_valid, int *sqp_iter_out, int *qp_iter_out, double *res4, double *cost_out, bool *plant_done, Lin &&lin,
-                        Search &&search)
+                        Search &&search, AfterQp &&after_qp = AfterQp{})
     {
+        constexpr bool HOOK = !std::is_same<typename std::decay<AfterQp>::type, NoHook>::value;
         *plant_done = false;
         PROF_T0(t0);
         int status = 0, sqp_iter = 0, qp_iter = 0, it = 0;
@@ -2960,11 +2969,13 @@ struct Engine {
                 rhs_valid = false;
             }
             commit_pending = false;
-            const int qs = ipm_solve(&it, MPCB_FUSE != 0);
+            bool fast_accepted = false;
+            const int qs = ipm_solve(&it, MPCB_FUSE != 0, HOOK ? &fast_accepted : nullptr);
             qp_iter += it;
             sqp_iter = 1;
             const bool ok = qs == 0 || qs == 1;
             if (!ok) status = 4;  // ACADOS_QP_FAILURE, iterate untouched
+            if constexpr (HOOK) after_qp(fast_accepted && qs == 0);
             // residuals / cost are evaluated at the new iterate (acados get_residuals() for RTI,
             // get_cost()); this linearisation is reused by the next solve() call -- and so is the fast path's right-hand side,
             // formed by the same pass when the next QP will try the fast path (ipm_solve: fast_off == 0 and no suspension left)
@@ -3158,13 +3169,108 @@ struct Engine {
         });
     }
 
+    // The feedback gain and the reference sensitivity of u0 (mpcb_step_sens; formulas and lane roles: mpc_nlp.h sens_*) of the QP just
+    // solved -- `exact`: by an accepted fast-path attempt; otherwise u0 is not affine in its data and everything is NaN, valid = 0.
+    // Runs between the QP solve and the closing linearisation: K_k is still where the factorisation left it (the resident LDS array,
+    // or G4 in the streaming / segment / register geometries -- after the last sweep nothing else of the pool is live, so what the
+    // resident map calls scratch, or the whole pool, is free), R~_0^-1 is in G4, and G2 holds the Jacobians the QP was built from.
+    // The stage recursion is sequential: blocks of stages are staged HBM -> LDS by every lane (all loads of a block in flight together,
+    // no store between them), wavefront 0 runs the block from LDS with M (transposed, double-buffered) in LDS too, and the rows of
+    // the block leave as one contiguous run.  dx [6][12], dy [N][NTASK][6] or null, valid: this simulation's.
+    MPC_PASS void sens_pass(double *dx, double *dy, int *valid, bool exact)
+    {
+        Smem &sm = ex.smem();
+        const InstParams &P = sm.P;
+        const int Nl = ex.uni(sm.n_hor), NM = ex.uni(N);
+        if (!exact) {
+            ex.par([&](int lane) {
+                const double nan = __builtin_nan("");
+                for (int e = lane; e < NU * NX; e += NT) gst(dx + e, nan);
+                if (dy) for (int e = lane; e < NM * NTASK * NU; e += NT) gst(dy + e, nan);
+                if (lane == 0) *(MPC_GLOBAL int *)valid = 0;
+            });
+            return;
+        }
+        const bool res = resident_ok();
+        const ResMap rm = res_map();
+        double *const G2 = sm.w.G2, *const G4 = sm.w.G4;
+        constexpr int WG = 36, WO = NTASK * NU;                       // [GQ | GV] of a G2 record; a row of dy
+        static_assert(O_GV == O_GQ + 30, "GQ and GV are one run of the G2 record");
+        double *const Mt = ex.pool(), *const gb = Mt + 2 * 72;
+        const int per = WG + WO + (res ? 0 : 72);
+        const int CH = ex.uni(imax(1, imin(((res ? rm.scr_n : ex.uni(sm.pool_n)) - 2 * 72) / per, Nl)));
+        double *const kb = gb + (size_t)CH * WG, *const ob = kb + (res ? 0 : (size_t)CH * 72);
+        ex.par([&](int lane) {
+            double k0[(NU * NX + NT - 1) / NT];
+            double ri = 0.0;
+#pragma unroll
+            for (int r = 0; r < (NU * NX + NT - 1) / NT; r++) {
+                const int e = imin(lane + r * NT, NU * NX - 1);
+                k0[r] = res ? rm.K[e] : gld(G4 + O_K + e);
+            }
+            if (lane < 36) ri = gld(G4 + O_RI + lane);
+#pragma unroll
+            for (int r = 0; r < (NU * NX + NT - 1) / NT; r++) {
+                const int e = lane + r * NT;
+                if (e < NU * NX) gst(dx + e, -k0[r]);
+            }
+            if (lane < 36) {
+                const int j = lane / 6, cc = lane - j * 6;
+                double mq, mv;
+                nlp::sens_start(P, j, ri, mq, mv);
+                Mt[cc * 12 + j] = mq; Mt[cc * 12 + 6 + j] = mv;
+            }
+            // stage 0's reference row does not reach u0 (x_0 is pinned to x_hat); nor do rows past the horizon
+            if (dy) {
+                for (int e = lane; e < WO; e += NT) gst(dy + e, 0.0);
+                for (int e = Nl * WO + lane; e < NM * WO; e += NT) gst(dy + e, 0.0);
+            }
+            if (lane == 0) *(MPC_GLOBAL int *)valid = 1;
+        });
+        if (!dy) return;
+        int cur = 0;
+        for (int k0 = 1; k0 < Nl; k0 += CH) {
+            const int n = imin(CH, Nl - k0);
+            ex.par([&](int lane) {
+                for (int e = lane; e < n * WG; e += NT) {
+                    const int r = e / WG;
+                    gb[e] = gld(G2 + (size_t)(k0 + r) * W2 + O_GQ + (e - r * WG));
+                }
+                if (!res) for (int e = lane; e < n * 72; e += NT) {
+                    const int r = e / 72;
+                    kb[e] = gld(G4 + (size_t)(k0 + r) * W4 + O_K + (e - r * 72));
+                }
+            });
+            for (int r = 0; r < n; r++) {
+                const double *kk = res ? rm.K + (size_t)(k0 + r) * 72 : kb + (size_t)r * 72;
+                const double *m = Mt + cur * 72, *g = gb + (size_t)r * WG;
+                double *mn = Mt + (cur ^ 1) * 72, *o = ob + (size_t)r * WO;
+                ex.seq([&](int lane) {
+                    if (lane < 36) {
+                        const int j = lane / 6, cc = lane - j * 6;
+                        if (j < NTASK) o[j * 6 + cc] = nlp::sens_project(P, j, cc, g, m);
+                        double mq, mv;
+                        nlp::sens_advance(P, j, cc, kk, m, mq, mv);
+                        mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+                    }
+                });
+                cur ^= 1;
+            }
+            ex.barrier();
+            ex.par([&](int lane) {
+                for (int e = lane; e < n * WO; e += NT) gst(dy + (size_t)k0 * WO + e, ob[e]);
+            });
+        }
+    }
+
     // One solver.solve() from the caller's feedback state (mpcb_step; acados set(0,'lbx'|'ubx',x), solve(), get(0,'u'),
     // simulator.py:210-221) for instance `inst`: the iterate, the linearisation and the fast-path suspension carry over from the
     // previous step in the workspace as between two rollout launches; `reset` starts from the initial guess instead.  No plant step,
     // no log columns: io.u0 is the plant's input, the caller's plant produces the next io.xhat.
     // WARM (the kernels of mpcb_step_warm): io.warm gives this simulation's own mode -- WARM_RESET is `reset` for it alone, WARM_SHIFT
     // moves its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
-    template <bool WARM = false>
+    // SENS (the kernels of mpcb_step_sens, SQP_RTI): the sensitivities of u0 leave through io.du0_dx / du0_dyref / sens_valid (sens_pass).
+    template <bool WARM = false, bool SENS = false>
     MPC_HD void control_step(const StepIO &io, int inst, bool reset)
     {
         Smem &sm = ex.smem();
@@ -3196,7 +3302,15 @@ struct Engine {
         double res4[4] = {0, 0, 0, 0}, cost = 0.0;
         const double t0 = ex.clock();
         bool plant_done = false;
-        const int status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
+        int status;
+        if constexpr (SENS) {
+            status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search, [&](bool exact) {
+                sens_pass(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * N * NTASK * NU : nullptr,
+                          io.sens_valid + inst, exact);
+            });
+        } else {
+            status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
+        }
         const double t1 = ex.clock();
         ex.par([&](int lane) {
             if (lane < NU) io.u0[(size_t)inst * NU + lane] = w.G1[O_U + lane];   // solver.get(0,'u')

@@ -45,6 +45,12 @@ void launch_step_warm(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStre
                       const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
 void launch_stream_step_warm(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
                              size_t ws_stride, const StepIO &io, int reset);
+// ... and those that also write the sensitivities of u0 (mpcb_step_sens): mpc_step_sens.hip, mpc_stream_step_sens.hip
+const void *step_sens_kernel(int waves_per_sim, int wpe);
+void launch_step_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                      const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
+void launch_stream_step_sens(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                             size_t ws_stride, const StepIO &io, int reset);
 }  // namespace mpcb
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
@@ -501,10 +507,12 @@ static const void *latency_kernel(const mpcb_handle *h)
 
 // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
 // handle can ask for, right before the launch
-static int raise_lds_limit(mpcb_handle *h, bool warm = false)
+// (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens)
+static int raise_lds_limit(mpcb_handle *h, int step = 0)
 {
     static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(warm ? step_warm_kernel(h->waves_per_sim, h->wpe) : latency_kernel(h),
+    HIPCHK(h, hipFuncSetAttribute(step == 2 ? step_sens_kernel(h->waves_per_sim, h->wpe)
+                                  : step == 1 ? step_warm_kernel(h->waves_per_sim, h->wpe) : latency_kernel(h),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     return MPCB_OK;
 }
@@ -615,8 +623,15 @@ int mpcb_step_ref(mpcb_handle *h, const mpcb_step_io *io, const double *yref, in
     return mpcb_step_warm(h, io, yref, ref_changed, nullptr, reset, stream);
 }
 
-// (warm == NULL: the kernels of mpcb_step / mpcb_step_ref, which know no modes; otherwise the warm-start kernels)
 int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset, void *stream)
+{
+    return mpcb_step_sens(h, io, yref, ref_changed, warm, reset, nullptr, stream);
+}
+
+// (sens == NULL and warm == NULL: the kernels of mpcb_step / mpcb_step_ref, which know no modes; sens == NULL: the warm-start kernels;
+// otherwise the kernels that run the sensitivity pass, which are supersets of the warm-start ones)
+int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const mpcb_step_sens_out *sens, void *stream)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
@@ -624,6 +639,12 @@ int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
     if (!io) return fail(h, MPCB_EINVAL, "step io pointer is NULL");
     if (!io->xhat || !io->u0 || !io->status || !io->sqp_iter || !io->qp_iter || !io->residuals || !io->cost || !io->solver_time)
         return fail(h, MPCB_EINVAL, "every step array but x_pred / u_pred must be provided");
+    if (sens) {
+        if (h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+            return fail(h, MPCB_EINVAL, "mpcb_step_sens: the sensitivities of u0 are those of an SQP_RTI step's QP; this controller runs full SQP");
+        if (!sens->du0_dx || !sens->valid) return fail(h, MPCB_EINVAL, "mpcb_step_sens: du0_dx and valid must be provided");
+    }
+    const int variant = sens ? 2 : warm ? 1 : 0;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     StepIO sio;
@@ -631,11 +652,13 @@ int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
     sio.yref = yref;
     sio.ref_changed = ref_changed != 0 ? 1 : 0;
     sio.warm = warm;
+    if (sens) { sio.du0_dx = sens->du0_dx; sio.du0_dyref = sens->du0_dyref; sio.sens_valid = sens->valid; }
     const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
     if (h->engine == MPCB_ENGINE_STREAM) {
         // throughput engine: one wavefront per simulation, static LDS only, no work queue
         HIPCHK(h, hipEventRecord(h->ev0, s));
-        if (warm) launch_stream_step_warm(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        if (variant == 2) launch_stream_step_sens(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        else if (variant == 1) launch_stream_step_warm(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         else launch_stream_step(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipEventRecord(h->ev1, s));
@@ -646,9 +669,12 @@ int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
         return MPCB_OK;
     }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    if (int rc = raise_lds_limit(h, warm != nullptr)) return rc;
+    if (int rc = raise_lds_limit(h, variant)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
-    if (warm)
+    if (variant == 2)
+        launch_step_sens(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
+                         rs, h->pool_doubles);
+    else if (variant == 1)
         launch_step_warm(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
                          rs, h->pool_doubles);
     else

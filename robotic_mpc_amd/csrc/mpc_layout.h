@@ -143,7 +143,7 @@ struct Outputs {
 // Device pointers of one controller step (mpcb_step_io, then the task reference of mpcb_step_ref): the caller's feedback states in,
 // solver.get(0,'u') and the step's statistics out, batch-major.  x_pred / u_pred may be null (not written).  The members past
 // u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged", one that stops
-// at ref_changed "every simulation carries its solver memory".
+// at ref_changed "every simulation carries its solver memory", one that stops at warm "no sensitivities".
 struct StepIO {
     const double *xhat;  // [batch][12]
     double *u0;          // [batch][6]
@@ -158,6 +158,10 @@ struct StepIO {
     const double *yref = nullptr;   // [batch][N][NTASK] targets of g1..g5 at stages 0..N-1, or null: each instance's packed g_ref
     int ref_changed = 0;            // != 0: the reference differs from the previous step's (the carried linearisation is stale)
     const int *warm = nullptr;      // [batch] WARM_* of each simulation (mpcb_step_warm), or null: WARM_CARRY for all
+    // mpcb_step_sens (mpcb_step_sens_out): the feedback gain and reference sensitivity of u0, read by the sens kernels only
+    double *du0_dx = nullptr;       // [batch][6][12] d u0 / d xhat
+    double *du0_dyref = nullptr;    // [batch][N][NTASK][6] (d u0 / d yref_k)', or null (not written)
+    int *sens_valid = nullptr;      // [batch] 1: exact sensitivities written, 0: NaN
 };
 
 // How a simulation's solver memory enters a controller step (MPCB_WARM_*); any other value is WARM_CARRY.

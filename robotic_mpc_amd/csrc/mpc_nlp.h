@@ -156,5 +156,33 @@ MPC_HD void put_prediction(const StepIO &io, int inst, int lane, int nt, G g1, s
     }
 }
 
+// ---- sensitivities of u0 on a step whose QP the bound-inactive fast path solved (mpcb_step_sens) -----------------------------------
+// u0 is then affine in the feedback state and in the task reference: d u0 / d xhat = -K_0, and with M_1 = -B R~_0^-1 (12x6),
+// M_{k+1} = (A - B K_k) M_k the reference row of stage k is (d u0 / d yref_k)' = -dt W G_k M_k (5x6), G_k = [GQ_k | e_5 GV_k'] the
+// task Jacobian the QP was built from.  One stage of that recursion for lane (j, c), j < 6 joints x c < 6 inputs: Mt holds M_k
+// TRANSPOSED (column c at Mt[12 c .. 12 c + 12)), K the gain rows K[12 j + i], G the [GQ 30 | GV 6] columns of the G2 record.
+// A and B are diagonal blocks (shift_tail): row j of M is q_j, row 6 + j is qdot_j.
+template <class KK, class MM>
+MPC_HD void sens_advance(const InstParams &P, int j, int c, const KK &K, const MM &Mt, double &mq, double &mv)
+{
+    double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int i = 0; i < NX; i += 2) { t0 += K[j * 12 + i] * Mt[c * 12 + i]; t1 += K[j * 12 + i + 1] * Mt[c * 12 + i + 1]; }
+    const double t = t0 + t1, q = Mt[c * 12 + j], v = Mt[c * 12 + 6 + j];
+    mq = q + P.a12[j] * v - P.b1[j] * t;
+    mv = P.a22[j] * v - P.b2[j] * t;
+}
+// entry (i, c), i < NTASK, of (d u0 / d yref_k)'
+template <class GG, class MM>
+MPC_HD double sens_project(const InstParams &P, int i, int c, const GG &G, const MM &Mt)
+{
+    double s = 0.0, sv = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; j++) { s += G[i * 6 + j] * Mt[c * 12 + j]; sv += G[30 + j] * Mt[c * 12 + 6 + j]; }
+    return -P.dt * P.w_task[i] * (i == 4 ? s + sv : s);
+}
+// M_1 = -B R~_0^-1: rows j and 6 + j of column c from ri = R~_0^-1 (j, c)
+MPC_HD void sens_start(const InstParams &P, int j, double ri, double &mq, double &mv) { mq = -P.b1[j] * ri; mv = -P.b2[j] * ri; }
+
 }  // namespace nlp
 }  // namespace mpcb

@@ -1662,8 +1662,11 @@ SE_PASS void fast_commit(bool embed_x0)
 // runs in fp64 only -- ONE fp32 Riccati solve is not a solution to qp_tol (the fp32 leg refines through the fp64 residuals of the loop).
 // `cur` (SQP_RTI; null = full SQP): which slot of the stage records holds the QP iterate -- 0: G1 [QW..QT], 1: G3 [DW..DT] (fast_commit
 // comment).  An accepted fast-path candidate becomes the iterate by flipping it; the interior-point loop wants the iterate in G1.
-template <class FT>
-SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_prev = nullptr, int *cur = nullptr)
+// `fast_accepted` (out, optional): whether this QP is the accepted fast-path candidate (mpc_step's hook asks).
+// FULLFACT (the kernel of mpcb_step_sens): the fast path's factor records go out whole, tail [w | R~^-1] included -- sens_pass reads
+// R~_0^-1; the same factorisation, 48 more scalars stored per stage.
+template <class FT, bool FULLFACT = false>
+SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_prev = nullptr, int *cur = nullptr, bool *fast_accepted = nullptr)
 {
     SSmem &sm = g_ssm;
     const double tol = sm.P.qp_tol;
@@ -1678,7 +1681,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
             SPROF_ADD(10, t_r);
             nlp_prev = nullptr;                                    // the previous step's residuals are done, whatever happens next
             SPROF_T0(t_f);
-            fact_pass<FT, true>();
+            fact_pass<FT, !FULLFACT>();
             SPROF_ADD(11, t_f);
             SPROF_T0(t_w);
             const double ok = unid(forward_pass<FT, false, true>(slot ^ 1).alpha);     // the candidate goes to the slot that is NOT the iterate
@@ -1692,6 +1695,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
                 if (threadIdx.x == 0) g_ssm.w.state[ST_PROF + 15] += 1.0;
 #endif
                 fast[1] = 0;
+                if (fast_accepted) *fast_accepted = true;
                 *iters_out = 1;
                 return 0;
             }
@@ -2067,9 +2071,13 @@ struct StepStats {
 // and, SQP_RTI, in who forms a step's cost and residual norms: a trailing rti_items here, or, with `defer`, the next step's first pass,
 // which streams the same records (the stats then hold the cost carried in and zeros; that next call gets `nlp_prev` and fills it with
 // [cost, stat, eq, ineq, comp] of this step).
-template <class FT, class Lin, class Search>
-SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer)
+// `after_qp(exact)` (SQP_RTI; only the kernel of mpcb_step_sens brings one): called between the QP solve and the closing linearisation,
+// while G2 still holds the linearisation the QP was built from; `exact`: the QP was solved by an accepted fast-path attempt.
+struct NoHook {};
+template <class FT, class Lin, class Search, class AfterQp = NoHook>
+SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer, AfterQp &&after_qp = AfterQp{})
 {
+    constexpr bool HOOK = !std::is_same<typename std::decay<AfterQp>::type, NoHook>::value;
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
     const int lane = threadIdx.x;
@@ -2083,10 +2091,12 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
             rti_items<true, false>(0, o5, c.cur);
             c.lin_cost = unid(o5[0]);
         }
-        const int qs = ipm_solve<FT>(pb.qp_iter_max, &s.qp_iter, c.fast, nlp_prev, &c.cur);
+        bool fast_accepted = false;
+        const int qs = ipm_solve<FT, HOOK>(pb.qp_iter_max, &s.qp_iter, c.fast, nlp_prev, &c.cur, HOOK ? &fast_accepted : nullptr);
         SPROF_ADD(5, tq);
         const bool ok = qs == 0 || qs == 1;
         if (!ok) s.status = 4;                                         // ACADOS_QP_FAILURE, iterate untouched
+        if constexpr (HOOK) after_qp(fast_accepted && qs == 0);
         __builtin_amdgcn_s_waitcnt(0);
         SPROF_T0(tl);
         lin(1.0, ok, false, c.cur);
@@ -2268,13 +2278,93 @@ SE_PASS void shift_pass(int N)
     fence();
 }
 
+// The feedback gain and the reference sensitivity of u0 (mpcb_step_sens; formulas and lane roles: mpc_nlp.h sens_*) of the QP just
+// solved -- `exact`: by an accepted fast-path attempt; otherwise everything is NaN and valid = 0.  Runs between the QP solve and the
+// closing linearisation: the factor records (K_k in the SK columns, R~_0^-1 -- this kernel's fast path stores the records whole,
+// ipm_solve FULLFACT) and the Jacobians of G2 are those of the QP.  fp64 factor
+// only (the fast path runs in fp64 only).  The stage recursion is sequential and the ring is idle: blocks of SENS_CH stages are staged
+// into it ([GQ | GV] and K, every load of a block in flight before the first use), the block runs from LDS with M (transposed,
+// double-buffered) in LDS too, and its rows leave as one contiguous run.  dx [6][12], dy [NMAX][NTASK][6] or null, valid: this
+// simulation's; rows of dy past its own horizon N are zero (those reference rows are never read).
+constexpr int SENS_WG = 36, SENS_WO = NTASK * NU, SENS_CH = (RING_DOUBLES - 2 * 72) / (SENS_WG + 72 + SENS_WO);
+static_assert(SENS_CH >= 1 && O_GV == O_GQ + 30, "sens_pass staging");
+SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, bool exact)
+{
+    SSmem &sm = g_ssm;
+    const InstParams &P = sm.P;
+    const SWs w = sm.w;
+    const int lane = threadIdx.x;
+    MPC_GLOBAL double *const dx = (MPC_GLOBAL double *)dx_, *const dy = (MPC_GLOBAL double *)dy_;
+    MPC_GLOBAL int *const valid = (MPC_GLOBAL int *)valid_;
+    __builtin_amdgcn_s_waitcnt(0);                                // nothing of the forward sweep is still on its way into the ring
+    fence();
+    if (!uni(exact ? 1 : 0)) {
+        const double nan = __builtin_nan("");
+        for (int e = lane; e < NU * NX; e += WAVE) dx[e] = nan;
+        if (dy) for (int e = lane; e < NMAX * SENS_WO; e += WAVE) dy[e] = nan;
+        if (lane == 0) *valid = 0;
+        return;
+    }
+    const int ldd = w.ld / 8;
+    const MPC_GLOBAL double *const g2 = (const MPC_GLOBAL double *)w.G2, *const g4 = (const MPC_GLOBAL double *)w.G4;
+    double *const Mt = sm.ring, *const gb = Mt + 2 * 72, *const kb = gb + SENS_CH * SENS_WG, *const ob = kb + SENS_CH * 72;
+    {
+        const double ka = g4[SK + lane], kc = g4[SK + imin(WAVE + lane, NU * NX - 1)], ri = g4[SRI + imin(lane, 35)];
+        dx[lane] = -ka;
+        if (WAVE + lane < NU * NX) dx[WAVE + lane] = -kc;
+        if (lane < 36) {
+            const int j = lane / 6, cc = lane - j * 6;
+            double mq, mv;
+            nlp::sens_start(P, j, ri, mq, mv);
+            Mt[cc * 12 + j] = mq; Mt[cc * 12 + 6 + j] = mv;
+        }
+        // stage 0's reference row does not reach u0 (x_0 is pinned to x_hat); nor do rows past this simulation's horizon
+        if (dy) {
+            if (lane < SENS_WO) dy[lane] = 0.0;
+            for (int e = N * SENS_WO + lane; e < NMAX * SENS_WO; e += WAVE) dy[e] = 0.0;
+        }
+        if (lane == 0) *valid = 1;
+    }
+    fence();
+    if (!dy) return;
+    int cur = 0;
+    for (int k0 = 1; k0 < N; k0 += SENS_CH) {
+        const int n = imin(SENS_CH, N - k0);
+        for (int e = lane; e < n * SENS_WG; e += WAVE) {
+            const int r = e / SENS_WG;
+            gb[e] = g2[(size_t)(k0 + r) * ldd + O_GQ + (e - r * SENS_WG)];
+        }
+        for (int e = lane; e < n * 72; e += WAVE) {
+            const int r = e / 72;
+            kb[e] = g4[(size_t)(k0 + r) * ldd + SK + (e - r * 72)];
+        }
+        fence();
+        for (int r = 0; r < n; r++) {
+            const double *kk = kb + r * 72, *m = Mt + cur * 72, *g = gb + r * SENS_WG;
+            double *mn = Mt + (cur ^ 1) * 72, *o = ob + r * SENS_WO;
+            if (lane < 36) {
+                const int j = lane / 6, cc = lane - j * 6;
+                if (j < NTASK) o[j * 6 + cc] = nlp::sens_project(P, j, cc, g, m);
+                double mq, mv;
+                nlp::sens_advance(P, j, cc, kk, m, mq, mv);
+                mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+            }
+            fence();
+            cur ^= 1;
+        }
+        for (int e = lane; e < n * SENS_WO; e += WAVE) dy[(size_t)k0 * SENS_WO + e] = ob[e];
+        fence();
+    }
+}
+
 // Controller step (mpcb_step, mpc_stream_step.hip): ONE step of rollout<FT>'s loop for simulation `inst`, from the caller's state
 // io.xhat, with no plant and no logs.  The solver memory carries over in the workspace as between two rollout launches (Carry); `reset`
 // starts from the acados initial guess instead (the rollout's step 0).  Every step is the last of its launch: its cost and residual
 // norms are never deferred to the next step's first pass, since the caller reads them when the launch returns.
 // WARM (the kernel of mpcb_step_warm): io.warm gives this simulation's own mode -- WARM_RESET is `reset` for it alone, WARM_SHIFT moves
 // its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
-template <class FT, bool WARM = false>
+// SENS (the kernel of mpcb_step_sens, SQP_RTI): the sensitivities of u0 leave through io.du0_dx / du0_dyref / sens_valid (sens_pass).
+template <class FT, bool WARM = false, bool SENS = false>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
@@ -2310,7 +2400,15 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
     if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
     fence();
     const double t0 = wclock();
-    const StepStats s = mpc_step<FT>(pb, c, lin, search, nullptr, false);
+    StepStats s;
+    if constexpr (SENS) {
+        s = mpc_step<FT>(pb, c, lin, search, nullptr, false, [&](bool exact) {
+            sens_pass(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * NMAX * NTASK * NU : nullptr,
+                      io.sens_valid + inst, N, NMAX, exact);
+        });
+    } else {
+        s = mpc_step<FT>(pb, c, lin, search, nullptr, false);
+    }
     const double t1 = wclock();
     // solver.get(0,'u') and the step's statistics.  The NLP iterate lives in G1 [X | U] whichever slot `cur` names (that is the QP
     // iterate's: the step lin_pass has just applied).

@@ -78,11 +78,16 @@ class EngineError(RuntimeError):
     pass
 
 
+class MpcbStepSensOut(C.Structure):
+    """mpcb_step_sens_out (include/mpcbatch.h): device pointers."""
+    _fields_ = [("du0_dx", C.POINTER(C.c_double)), ("du0_dyref", C.POINTER(C.c_double)), ("valid", C.POINTER(C.c_int))]
+
+
 _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", "mpcb_last_error",
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
-            "mpcb_step_ref", "mpcb_step_warm")
+            "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -129,6 +134,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_controller_engine_for.argtypes = [C.POINTER(MpcbProblem), C.c_int]
     lib.mpcb_step_ref.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, C.c_int, C.c_void_p]
     lib.mpcb_step_warm.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.c_void_p]
+    lib.mpcb_step_sens.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.POINTER(MpcbStepSensOut), C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -330,6 +336,28 @@ class MpcBatchEngine:
         wp = C.cast(C.c_void_p(warm.data_ptr()), _ip) if warm is not None else None
         self._check(self.lib.mpcb_step_warm(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), C.c_void_p(stream)),
                     "mpcb_step_warm")
+
+    def step_sens(self, io, yref=None, ref_changed: bool = False, warm=None, reset: bool = False, sens=None,
+                  stream: Optional[int] = None):
+        """mpcb_step_sens: step_warm() that also writes the sensitivities of u0 -- `sens` a dict of contiguous device tensors
+        du0_dx [batch, 6, 12] float64, valid [batch] int32 and optionally du0_dyref [batch, N, 5, 6] float64, or None: step_warm()
+        exactly."""
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._step_struct(io)
+        yp = C.cast(C.c_void_p(yref.data_ptr()), _dp) if yref is not None else None
+        wp = C.cast(C.c_void_p(warm.data_ptr()), _ip) if warm is not None else None
+        sp = None
+        if sens is not None:
+            dy = sens.get("du0_dyref")
+            so = MpcbStepSensOut(C.cast(C.c_void_p(sens["du0_dx"].data_ptr()), _dp),
+                                 C.cast(C.c_void_p(dy.data_ptr()), _dp) if dy is not None else None,
+                                 C.cast(C.c_void_p(sens["valid"].data_ptr()), _ip))
+            sp = C.byref(so)
+        self._check(self.lib.mpcb_step_sens(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
+                                            C.c_void_p(stream)), "mpcb_step_sens")
 
     def debug_task_lin(self, cfgs: Sequence[Dict], chain, x: np.ndarray) -> np.ndarray:
         """Diagnostic: the device linearisation at points x[i] = [q; qdot] with the parameters of cfgs[i];

@@ -15,9 +15,11 @@ per-stage tracking reference set before the loop) and every (a new one every ste
 iterate moved one stage, BatchController.step(shift=True): the shift pass and one more linearisation per step).  When it is given,
 each line also reports the closed-loop effect on a schedule that slides one stage per step (row j of step k is stage k + j of one
 ramp): the medians over steps 100.. of the stationarity residual and of max |u_pred - the previous step's u_pred|.
+`--sens` asks every step for the sensitivities of u0 (BatchController.step(sens=True): the sensitivity pass in the step kernel) and
+reports the fraction of steps that had them.
 
     python scripts/controller_rate.py [--batch 256 ...] [--engine latency|stream ...] [--N 100] [--steps 600] [--solver SQP_RTI]
-                                      [--skip-rollout] [--ref none|once|every ...] [--warm carry|shift ...]
+                                      [--skip-rollout] [--ref none|once|every ...] [--warm carry|shift ...] [--sens]
 """
 import argparse
 import json
@@ -68,6 +70,8 @@ def main():
     ap.add_argument("--ref", nargs="+", choices=("none", "once", "every"), default=["none"])
     # warm start of every step: the previous iterate as it is, or moved one stage (the shift pass + one more linearisation per step)
     ap.add_argument("--warm", nargs="+", choices=("carry", "shift"), default=None)
+    # every step also returns du0_dx / du0_dyref / sens_valid (the sensitivity pass)
+    ap.add_argument("--sens", action="store_true")
     args = ap.parse_args()
     for B in args.batch:
         for eng in args.engine:
@@ -126,6 +130,8 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
     if ref == "once":
         ctl.set_reference(sched[0])
 
+    nvalid = []
+
     def closed_loop(events=None):
         ctl.reset()
         x = x0
@@ -133,12 +139,15 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
             if events is not None:
                 events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
                 events[-1][0].record()
+            kw = dict(sens=True) if args.sens else {}
             if warm == "shift":
-                u = ctl.step(x, yref=sched[k % 2] if ref == "every" else None, shift=True)["u0"]
-            else:
-                u = ctl.step(x, yref=sched[k % 2] if ref == "every" else None)["u0"]
+                kw.update(shift=True)
+            o = ctl.step(x, yref=sched[k % 2] if ref == "every" else None, **kw)
+            u = o["u0"]
             if events is not None:
                 events[-1][1].record()
+                if args.sens:
+                    nvalid.append(o["sens_valid"].sum())   # (outside the timed span; the timed loop above has no such launch)
             x = plant(x, u)
         return x
 
@@ -154,10 +163,12 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
     closed_loop(ev)
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
-    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, step_loop_ms=round(loop_ms, 3),
+    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, sens=bool(args.sens), step_loop_ms=round(loop_ms, 3),
                step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
                step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
                launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
+    if args.sens:
+        out.update(sens_valid_fraction=round(float(torch.stack(nvalid).sum()) / (B * S), 5))
     if sliding and S > 110:
         out.update(sliding_schedule=sliding_medians(ctl, plant, x0, S, warm == "shift"))
     if not args.skip_rollout:
