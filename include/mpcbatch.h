@@ -284,6 +284,29 @@ typedef struct {
 int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                    const mpcb_step_sens_out *sens, void *stream);
 
+/* ---- run-time cost weights, and the sensitivity of u0 to them ---- */
+#define MPCB_NWEIGHT 7   /* w_u, w_qddot, task weights of g1..g5: parameters [3], [4], [56..60], in this order */
+/* Overwrites the seven cost weights of every simulation's device parameter record with `weights`, a DEVICE array
+ * [batch][MPCB_NWEIGHT].  Asynchronous on `stream` (a small kernel); the array is read during that launch only.  Ordering against
+ * the steps is the caller's: set the weights on the stream of the steps, or order the streams with an event, so that no step is
+ * running while the weights change and the next one starts after they have.  Nothing else of the record depends on the weights.
+ * The handle remembers that the carried linearisation is stale: the next mpcb_step* linearises again at its start for every
+ * simulation, exactly as after ref_changed != 0.  Everything else carries (the iterate, the multipliers, the QP memory, the merit
+ * weights, the fast-path suspension).  The weights stay in force across steps and resets until they are set again or
+ * mpcb_setup_controller* packs the configuration's own.  They are not validated: keep every weight >= 0 and
+ * w_u + w_qddot + levenberg_marquardt > 0, or the input Hessian is singular.
+ * MPCB_ESTATE on a handle not set up as a controller, MPCB_EINVAL on NULL. */
+int mpcb_set_weights(mpcb_handle *h, const double *weights /* DEVICE [batch][MPCB_NWEIGHT] */, void *stream);
+
+/* mpcb_step_sens that also writes du0_dw[i][p] = d u0 / d weight_p, 6 doubles each: DEVICE [batch][MPCB_NWEIGHT][6].
+ * du0_dw == NULL is mpcb_step_sens exactly.  sens (with du0_dx and valid) is required; sens->du0_dyref may be NULL.
+ * Where valid[i] == 0 every entry of du0_dw[i] is NaN.
+ * Like du0_dx, this is the exact derivative of this step's QP with its linearisation point held fixed (the QP's matrices are affine
+ * in the weights): of one real-time iteration, not of a converged solve, and without the dependence of the carried iterate on
+ * the weights of earlier steps.  A weight of 0 has its derivative.  With a horizon of 1 the five task rows are exactly zero. */
+int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                     const mpcb_step_sens_out *sens, double *du0_dw, void *stream);
+
 /* ---- the controller step on either kernel family ---- */
 #define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
 #define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */

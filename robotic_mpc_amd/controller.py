@@ -24,6 +24,10 @@ failed) while the others keep their warm start.
 ``step(..., sens=True)`` also returns the local law behind ``u0``: the feedback gain ``du0_dx`` and the sensitivity to the task
 reference ``du0_dyref`` of the step's QP, exact wherever the bound-inactive fast path solved it (``sens_valid``);
 ``robotic_mpc_amd.autograd.differentiable_step`` wraps them into a torch autograd function.
+
+``set_weights(w)`` changes the seven cost weights (w_u, w_qddot and the task weights of g1..g5) between steps without building
+another controller -- the warm start carries -- and ``step(..., sens_w=True)`` also returns ``du0_dw``, the sensitivity of ``u0``
+to them: what a gradient-based tuning of a batch of controllers needs (``differentiable_step(..., weights=w)``).
 """
 from __future__ import annotations
 
@@ -35,6 +39,7 @@ from . import config as cfgmod, packing
 from .engine import CONTROLLER_ENGINES, STEP_FIELDS, WARM_RESET, WARM_SHIFT, MpcBatchEngine
 
 NREF = 5    # task outputs with a reference (MPCB_NREF, include/mpcbatch.h)
+NWEIGHT = 7  # cost weights that can change at run time (MPCB_NWEIGHT): w_u, w_qddot, the task weights of g1..g5
 
 
 class BatchController:
@@ -59,6 +64,12 @@ class BatchController:
     rows beyond a configuration's own horizon are NaN.  Anything the chosen engine cannot run raises ``ValueError`` before
     the device is touched; without a GPU, construction raises ``EngineError``.
     """
+
+    # run-time cost weights (set_weights): the controller's own [B, 7] device buffer (None: the packed weights are in force) and
+    # the stream that last wrote the device records; the du0_dw buffer of step(sens_w=True), from the first use
+    _weights = None
+    _weights_stream = None
+    _sensw = None
 
     def __init__(self, configs: Sequence[Mapping], device: int = 0, engine: str = "latency"):
         if engine not in CONTROLLER_ENGINES:
@@ -216,7 +227,76 @@ class BatchController:
         self._ref_stream = cur
         self._ref_on, self._ref_changed = True, True
 
-    def step(self, xhat, predict: bool = False, yref=None, shift=False, sens: bool = False) -> Dict:
+    def packed_weights(self) -> np.ndarray:
+        """The cost weights of the configurations the controller was built from: [B, 7] float64 (w_u, w_qddot, the task weights
+        of g1..g5), a new numpy array."""
+        return np.array([[c["w_u"], c["w_qddot"], *np.asarray(c["w_task"], dtype=np.float64)] for c in self.configs], dtype=np.float64)
+
+    def _check_weights(self, w):
+        """Validates cost weights ([B, 7] or [7], float64, a numpy array or a tensor on the controller's device) without touching
+        the device; returns them as a [B, 7] or [1, 7] array / tensor."""
+        import torch
+
+        B = self.batch
+        if isinstance(w, np.ndarray):
+            shape, dtype_ok = tuple(w.shape), w.dtype == np.float64
+        elif isinstance(w, torch.Tensor):
+            shape, dtype_ok = tuple(w.shape), w.dtype == torch.float64
+            if w.device.type != "cuda" or w.device.index != self.device:
+                raise ValueError(f"weights must live on cuda:{self.device}, got {w.device}")
+        else:
+            raise ValueError(f"weights must be a torch tensor, a numpy array or None, got {type(w).__name__}")
+        if shape not in ((B, NWEIGHT), (NWEIGHT,)):
+            raise ValueError(f"weights must have shape ({B}, {NWEIGHT}) or ({NWEIGHT},), got {shape}")
+        if not dtype_ok:
+            raise ValueError(f"weights must be float64, got {w.dtype}")
+        w = w[None, :] if len(shape) == 1 else w
+        if isinstance(w, np.ndarray):
+            if not np.isfinite(w).all():
+                raise ValueError("weights has non-finite entries")
+            if (w < 0.0).any():
+                raise ValueError("weights must be >= 0")
+            lm = np.array([c.get("levenberg_marquardt", 0.0) for c in self.configs], dtype=np.float64)
+            if not (w[:, 0] + w[:, 1] + lm > 0.0).all():
+                raise ValueError("w_u + w_qddot + levenberg_marquardt must be > 0 for every simulation: the input Hessian is singular otherwise")
+        return w
+
+    def set_weights(self, w):
+        """Sets the cost weights the following steps use: ``w[i]`` = (w_u, w_qddot, the task weights of g1..g5) of simulation i,
+        [B, 7] float64, or [7] for the whole batch; a numpy array or a tensor on the controller's device.  The weights are copied
+        into the controller's own device buffer (later edits of ``w`` have no effect) and from there into the device's parameter
+        records, and stay in force -- across ``reset()`` too -- until they are set again; ``None`` returns to the weights of the
+        configurations.  The next step linearises again first, as after a new reference; the iterate, the multipliers, the QP
+        memory and the fast-path suspension carry.  A numpy array is validated before the device is touched (shape, dtype, finite,
+        every weight >= 0, w_u + w_qddot + levenberg_marquardt > 0); the values of a device tensor are the caller's to keep valid."""
+        import torch
+
+        arr = self.packed_weights() if w is None else self._check_weights(w)
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(self.device)
+        if self._weights is None:
+            self._weights = torch.empty((self.batch, NWEIGHT), dtype=torch.float64, device=dev)
+        # a step still running on another stream finishes first (it reads the records), and so does an earlier update
+        for other in (self._step_stream, self._weights_stream):
+            if other is not None and other != cur:
+                cur.wait_stream(other)
+        src = torch.from_numpy(np.ascontiguousarray(arr)).to(dev) if isinstance(arr, np.ndarray) else arr
+        self._weights.copy_(src.expand(self.batch, NWEIGHT))
+        self.engine.set_weights(self._weights, stream=cur.cuda_stream)
+        self._weights_stream = cur
+
+    def weights(self):
+        """The cost weights in force: a new [B, 7] float64 tensor on the controller's device."""
+        import torch
+
+        if self._weights is None:
+            return torch.from_numpy(self.packed_weights()).to(torch.device("cuda", self.device))
+        cur = torch.cuda.current_stream(self.device)
+        if self._weights_stream is not None and self._weights_stream != cur:
+            cur.wait_stream(self._weights_stream)
+        return self._weights.clone()
+
+    def step(self, xhat, predict: bool = False, yref=None, shift=False, sens: bool = False, sens_w: bool = False) -> Dict:
         """One MPC step of every controller from the feedback states ``xhat`` ([B, 12] q; qdot, float64: a tensor on the
         controller's device, or a numpy array that is copied there).
 
@@ -244,9 +324,19 @@ class BatchController:
         sensitivities through active bounds are not provided, nor those of ``x_pred`` / ``u_pred``.  The step itself is
         unchanged by ``sens``.  The extra pass costs 12-20 % of the step rate at N = 100 (latency engine 13 / 15 / 20 % at batch 256 /
         1024 / 4096, throughput engine 12-14 %; ``profiles/controller_step_rate_sens.txt``); a step without ``sens`` costs what
-        it did."""
+        it did.
+
+        ``sens_w=True`` implies ``sens`` and adds ``du0_dw`` [B, 7, 6] with ``du0_dw[i, p]`` = d u0 / d weight_p (the weights in
+        the order of ``set_weights``; the controller's own buffer), NaN where ``sens_valid`` is 0.  It is the exact derivative of
+        this step's QP, whose matrices are affine in the weights, with the linearisation point held fixed: the derivative of one
+        real-time iteration.  Over several closed-loop steps the dependence of the carried iterate on the weights of earlier steps
+        is not included.  A weight of 0 has its derivative; with a horizon of 1 the five task rows are exactly zero.
+        Over a ``sens=True`` step it costs another 5-11 % of the step rate at N = 100 (latency engine 7 / 9 / 11 % at batch 256 / 1024 /
+        4096, throughput engine 5-6 %; 18-28 % against a plain step; ``profiles/controller_step_rate_sensw.txt``); steps that do
+        not ask cost what they did."""
         import torch
 
+        sens = sens or sens_w
         if sens and self.configs[0]["solver_type"] != packing.SOLVER_RTI:
             raise ValueError("step(sens=True) needs an SQP_RTI controller: the sensitivities of u0 are those of one RTI step's QP")
         if yref is not None:
@@ -264,6 +354,8 @@ class BatchController:
             warm = self._compose_warm(shift, shift_all, stream)
         if self._ref_on and self._ref_stream is not None and self._ref_stream != stream:
             stream.wait_stream(self._ref_stream)      # the copy of the reference lands before the step reads it
+        if self._weights_stream is not None and self._weights_stream != stream:
+            stream.wait_stream(self._weights_stream)  # the new weights are in the records before the step reads them
         if sens:
             if self._sens is None:
                 dev = torch.device("cuda", self.device)
@@ -272,9 +364,12 @@ class BatchController:
                                   sens_valid=torch.zeros((self.batch,), dtype=torch.int32, device=dev))
             if self._step_stream is not None and self._step_stream != stream:
                 stream.wait_stream(self._step_stream)     # a step still writing the buffers on another stream finishes first
+            if sens_w and self._sensw is None:
+                self._sensw = torch.zeros((self.batch, NWEIGHT, 6), dtype=torch.float64, device=torch.device("cuda", self.device))
             self.engine.step_sens(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm,
                                   reset=self._reset, stream=stream.cuda_stream,
-                                  sens=dict(du0_dx=self._sens["du0_dx"], du0_dyref=self._sens["du0_dyref"], valid=self._sens["sens_valid"]))
+                                  sens=dict(du0_dx=self._sens["du0_dx"], du0_dyref=self._sens["du0_dyref"], valid=self._sens["sens_valid"]),
+                                  **(dict(du0_dw=self._sensw) if sens_w else {}))
         elif warm is not None:
             self.engine.step_warm(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm,
                                   reset=self._reset, stream=stream.cuda_stream)
@@ -290,6 +385,8 @@ class BatchController:
         out = {k: v for k, v in io.items() if k != "xhat"}
         if sens:
             out.update(self._sens)
+        if sens_w:
+            out["du0_dw"] = self._sensw
         return out
 
     def _compose_warm(self, shift, shift_all, stream):

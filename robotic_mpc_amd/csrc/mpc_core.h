@@ -3177,16 +3177,30 @@ struct Engine {
     // The stage recursion is sequential: blocks of stages are staged HBM -> LDS by every lane (all loads of a block in flight together,
     // no store between them), wavefront 0 runs the block from LDS with M (transposed, double-buffered) in LDS too, and the rows of
     // the block leave as one contiguous run.  dx [6][12], dy [N][NTASK][6] or null, valid: this simulation's.
-    MPC_PASS void sens_pass(double *dx, double *dy, int *valid, bool exact)
+    // SW (the kernels of mpcb_step_sens_w): also dw [NWEIGHT][6] = d u0 / d weight (mpc_nlp.h sensw_*).  A block then brings in, per
+    // stage, the QP's step [du | dq | dv] (still in the Newton-step slots of G3 when the commit is deferred to the closing NLP pass,
+    // else the QP iterate of G1), the [qdot | U] run of G1 and the unweighted task residual r of G2: SWX doubles.  Lane (j, c) of the
+    // recursion keeps three partial sums in registers over all blocks -- the j-th addends of rows 0 (w_u) and 1 (w_qddot) of column c
+    // and, j < NTASK, task row j -- and after the last stage one pass through LDS adds the six addends and the 42 values leave as
+    // one run.  Stage 0 enters through Nu_0 = -R~_0^-1 alone (M_0 = 0): rows 0 and 1, nothing for the task rows.
+    struct NoDw {};
+    static constexpr int SWX = 36, SWR = 3 * 36;                       // [du 6 | dq 6 | dv 6 | qdot 6 | U 6 | r 5 | pad]; the partial sums
+    template <bool SW = false>
+    MPC_PASS void sens_pass(double *dx, double *dy, int *valid, bool exact, typename std::conditional<SW, double *, NoDw>::type dw_ = {})
     {
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
         const int Nl = ex.uni(sm.n_hor), NM = ex.uni(N);
+        double *dw = nullptr;
+        if constexpr (SW) dw = dw_;
         if (!exact) {
             ex.par([&](int lane) {
                 const double nan = __builtin_nan("");
                 for (int e = lane; e < NU * NX; e += NT) gst(dx + e, nan);
                 if (dy) for (int e = lane; e < NM * NTASK * NU; e += NT) gst(dy + e, nan);
+                if constexpr (SW) {
+                    if (dw) for (int e = lane; e < NWEIGHT * NU; e += NT) gst(dw + e, nan);
+                }
                 if (lane == 0) *(MPC_GLOBAL int *)valid = 0;
             });
             return;
@@ -3196,19 +3210,28 @@ struct Engine {
         double *const G2 = sm.w.G2, *const G4 = sm.w.G4;
         constexpr int WG = 36, WO = NTASK * NU;                       // [GQ | GV] of a G2 record; a row of dy
         static_assert(O_GV == O_GQ + 30, "GQ and GV are one run of the G2 record");
-        double *const Mt = ex.pool(), *const gb = Mt + 2 * 72;
-        const int per = WG + WO + (res ? 0 : 72);
-        const int CH = ex.uni(imax(1, imin(((res ? rm.scr_n : ex.uni(sm.pool_n)) - 2 * 72) / per, Nl)));
+        static_assert(O_U == O_X + 12 && O_QW + 18 <= W1 && O_DW + 18 <= W3, "the [qdot | U] run of G1; the step slots");
+        double *const Mt = ex.pool(), *const gb = Mt + 2 * 72 + (SW ? SWR : 0);
+        const int per = WG + WO + (res ? 0 : 72) + (SW ? SWX : 0);
+        const int CH = ex.uni(imax(1, imin(((res ? rm.scr_n : ex.uni(sm.pool_n)) - 2 * 72 - (SW ? SWR : 0)) / per, Nl)));
         double *const kb = gb + (size_t)CH * WG, *const ob = kb + (res ? 0 : (size_t)CH * 72);
+        double *const xb = ob + (size_t)CH * WO, *const sb = Mt + 2 * 72;             // (SW) the staged operands; the partial sums
+        // (SW) where the QP's step is: a deferred commit has left it in the Newton-step slots
+        const double *const ST = SW ? (commit_pending ? sm.w.G3 + O_DW : sm.w.G1 + O_QW) : nullptr;
+        const int STW = commit_pending ? W3 : W1;
+        typename Ex::template PerLane<double> a_u, a_a, a_t;
         ex.par([&](int lane) {
             double k0[(NU * NX + NT - 1) / NT];
-            double ri = 0.0;
+            double ri = 0.0, s0 = 0.0, u0 = 0.0;
 #pragma unroll
             for (int r = 0; r < (NU * NX + NT - 1) / NT; r++) {
                 const int e = imin(lane + r * NT, NU * NX - 1);
                 k0[r] = res ? rm.K[e] : gld(G4 + O_K + e);
             }
             if (lane < 36) ri = gld(G4 + O_RI + lane);
+            if constexpr (SW) {
+                if (lane < 36) { s0 = gld(ST + lane / 6); u0 = gld(sm.w.G1 + O_U + lane / 6); }
+            }
 #pragma unroll
             for (int r = 0; r < (NU * NX + NT - 1) / NT; r++) {
                 const int e = lane + r * NT;
@@ -3219,6 +3242,12 @@ struct Engine {
                 double mq, mv;
                 nlp::sens_start(P, j, ri, mq, mv);
                 Mt[cc * 12 + j] = mq; Mt[cc * 12 + 6 + j] = mv;
+                if constexpr (SW) {
+                    // stage 0: Nu_0 = -R~_0^-1, M_0 = 0; x_0 + dx_0 is x_hat
+                    double au, aa;
+                    nlp::sensw_input(P, j, -ri, 0.0, u0 + s0, sm.xhat[6 + j], au, aa);
+                    a_u.at(lane) = au; a_a.at(lane) = aa; a_t.at(lane) = 0.0;
+                }
             }
             // stage 0's reference row does not reach u0 (x_0 is pinned to x_hat); nor do rows past the horizon
             if (dy) {
@@ -3227,7 +3256,7 @@ struct Engine {
             }
             if (lane == 0) *(MPC_GLOBAL int *)valid = 1;
         });
-        if (!dy) return;
+        if (!dy && !(SW && dw)) return;
         int cur = 0;
         for (int k0 = 1; k0 < Nl; k0 += CH) {
             const int n = imin(CH, Nl - k0);
@@ -3240,6 +3269,14 @@ struct Engine {
                     const int r = e / 72;
                     kb[e] = gld(G4 + (size_t)(k0 + r) * W4 + O_K + (e - r * 72));
                 }
+                if constexpr (SW) {
+                    for (int e = lane; e < n * SWX; e += NT) {
+                        const int r = e / SWX, q = e - r * SWX;
+                        const size_t k = (size_t)(k0 + r);
+                        xb[e] = q < 18 ? gld(ST + k * STW + q) : q < 30 ? gld(sm.w.G1 + k * W1 + O_X + 6 + (q - 18))
+                              : gld(G2 + k * W2 + O_R + imin(q - 30, NTASK - 1));
+                    }
+                }
             });
             for (int r = 0; r < n; r++) {
                 const double *kk = res ? rm.K + (size_t)(k0 + r) * 72 : kb + (size_t)r * 72;
@@ -3248,18 +3285,52 @@ struct Engine {
                 ex.seq([&](int lane) {
                     if (lane < 36) {
                         const int j = lane / 6, cc = lane - j * 6;
-                        if (j < NTASK) o[j * 6 + cc] = nlp::sens_project(P, j, cc, g, m);
-                        double mq, mv;
-                        nlp::sens_advance(P, j, cc, kk, m, mq, mv);
-                        mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+                        if constexpr (SW) {
+                            const double *x = xb + (size_t)r * SWX;
+                            if (j < NTASK) {
+                                const double gm = nlp::sensw_gm(j, cc, g, m);
+                                if (dy) o[j * 6 + cc] = -P.dt * P.w_task[j] * gm;
+                                a_t.at(lane) += P.dt * nlp::sensw_rho(j, g, x + 30, x + 6, x + 12) * gm;
+                            }
+                            double mq, mv, nu, au, aa;
+                            nlp::sensw_advance(P, j, cc, kk, m, mq, mv, nu);
+                            nlp::sensw_input(P, j, nu, m[cc * 12 + 6 + j], x[24 + j] + x[j], x[18 + j] + x[12 + j], au, aa);
+                            a_u.at(lane) += au; a_a.at(lane) += aa;
+                            mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+                        } else {
+                            if (j < NTASK) o[j * 6 + cc] = nlp::sens_project(P, j, cc, g, m);
+                            double mq, mv;
+                            nlp::sens_advance(P, j, cc, kk, m, mq, mv);
+                            mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+                        }
                     }
                 });
                 cur ^= 1;
             }
             ex.barrier();
-            ex.par([&](int lane) {
+            if (!SW || dy) ex.par([&](int lane) {
                 for (int e = lane; e < n * WO; e += NT) gst(dy + (size_t)k0 * WO + e, ob[e]);
             });
+        }
+        if constexpr (SW) {
+            // the six addends of rows 0 and 1 meet through LDS; 42 values, one run
+            ex.seq([&](int lane) {
+                if (lane < 36) { sb[lane] = a_u.at(lane); sb[36 + lane] = a_a.at(lane); sb[72 + lane] = a_t.at(lane); }
+            });
+            ex.seq([&](int lane) {
+                if (lane < NWEIGHT * NU) {
+                    const int p = lane / 6, cc = lane - p * 6;
+                    double v;
+                    if (p < 2) {
+                        const double *a = sb + p * 36 + cc;
+                        v = ((a[0] + a[6]) + (a[12] + a[18])) + (a[24] + a[30]);
+                    } else {
+                        v = sb[72 + (p - 2) * 6 + cc];
+                    }
+                    gst(dw + lane, v);
+                }
+            });
+            ex.barrier();
         }
     }
 
@@ -3270,7 +3341,8 @@ struct Engine {
     // WARM (the kernels of mpcb_step_warm): io.warm gives this simulation's own mode -- WARM_RESET is `reset` for it alone, WARM_SHIFT
     // moves its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
     // SENS (the kernels of mpcb_step_sens, SQP_RTI): the sensitivities of u0 leave through io.du0_dx / du0_dyref / sens_valid (sens_pass).
-    template <bool WARM = false, bool SENS = false>
+    // SENSW (the kernels of mpcb_step_sens_w; with SENS): and its sensitivity to the cost weights through io.du0_dw.
+    template <bool WARM = false, bool SENS = false, bool SENSW = false>
     MPC_HD void control_step(const StepIO &io, int inst, bool reset)
     {
         Smem &sm = ex.smem();
@@ -3303,7 +3375,12 @@ struct Engine {
         const double t0 = ex.clock();
         bool plant_done = false;
         int status;
-        if constexpr (SENS) {
+        if constexpr (SENS && SENSW) {
+            status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search, [&](bool exact) {
+                sens_pass<true>(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * N * NTASK * NU : nullptr,
+                                io.sens_valid + inst, exact, io.du0_dw ? io.du0_dw + (size_t)inst * NWEIGHT * NU : nullptr);
+            });
+        } else if constexpr (SENS) {
             status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search, [&](bool exact) {
                 sens_pass(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * N * NTASK * NU : nullptr,
                           io.sens_valid + inst, exact);

@@ -45,6 +45,12 @@ void launch_step_warm(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStre
                       const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
 void launch_stream_step_warm(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
                              size_t ws_stride, const StepIO &io, int reset);
+// ... those that also write the sensitivity of u0 to the cost weights (mpcb_step_sens_w): mpc_step_sensw.hip, mpc_stream_step_sensw.hip
+const void *step_sensw_kernel(int waves_per_sim, int wpe);
+void launch_step_sensw(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                       const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
+void launch_stream_step_sensw(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                              size_t ws_stride, const StepIO &io, int reset);
 // ... and those that also write the sensitivities of u0 (mpcb_step_sens): mpc_step_sens.hip, mpc_stream_step_sens.hip
 const void *step_sens_kernel(int waves_per_sim, int wpe);
 void launch_step_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
@@ -194,6 +200,18 @@ __global__ __launch_bounds__(WAVE) void mpc_summary_kernel(int batch, int Nsim, 
     }
 }
 
+// Run-time cost weights (mpcb_set_weights): the seven weight fields of every simulation's parameter record <- weights [batch][NWEIGHT]
+// (mpc_layout.h put_weights).  One lane per simulation; plain vector stores.
+__global__ __launch_bounds__(WAVE) void mpc_set_weights_kernel(int batch, InstParams *__restrict__ params, const double *__restrict__ weights)
+{
+    const int i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= batch) return;
+    double w[NWEIGHT];
+#pragma unroll
+    for (int p = 0; p < NWEIGHT; p++) w[p] = weights[(size_t)i * NWEIGHT + p];
+    put_weights(params[i], w);
+}
+
 // Diagnostic entry (tests): the device linearisation task_lin on n points, one lane each.
 __global__ void mpc_debug_task_lin_kernel(int n, Robot rb, const InstParams *__restrict__ params, const double *__restrict__ x,
                                           double *__restrict__ rec)
@@ -234,6 +252,7 @@ struct mpcb_handle {
     bool timed = false;
     bool controller = false;   // set up by mpcb_setup_controller: mpcb_step only (no rollouts)
     bool reset_next = false;   // the next mpcb_step starts from the initial guess whatever its flag says
+    bool weights_changed = false;   // mpcb_set_weights since the last step: the carried linearisation is stale (as after ref_changed)
 };
 
 static int fail(mpcb_handle *h, int code, const char *what, hipError_t e = hipSuccess)
@@ -472,6 +491,7 @@ static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *param
     h->timed = false;
     h->controller = controller;
     h->reset_next = true;
+    h->weights_changed = false;
     return MPCB_OK;
 }
 
@@ -507,11 +527,12 @@ static const void *latency_kernel(const mpcb_handle *h)
 
 // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
 // handle can ask for, right before the launch
-// (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens)
+// (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens, 3 of mpcb_step_sens_w)
 static int raise_lds_limit(mpcb_handle *h, int step = 0)
 {
     static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(step == 2 ? step_sens_kernel(h->waves_per_sim, h->wpe)
+    HIPCHK(h, hipFuncSetAttribute(step == 3 ? step_sensw_kernel(h->waves_per_sim, h->wpe)
+                                  : step == 2 ? step_sens_kernel(h->waves_per_sim, h->wpe)
                                   : step == 1 ? step_warm_kernel(h->waves_per_sim, h->wpe) : latency_kernel(h),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     return MPCB_OK;
@@ -613,6 +634,19 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
     return MPCB_OK;
 }
 
+int mpcb_set_weights(mpcb_handle *h, const double *weights, void *stream)
+{
+    if (!h) return MPCB_EINVAL;
+    if (!h->ready || !h->controller) return fail(h, MPCB_ESTATE, "mpcb_set_weights needs a handle set up by mpcb_setup_controller");
+    if (!weights) return fail(h, MPCB_EINVAL, "weights pointer is NULL");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(mpc_set_weights_kernel, dim3((unsigned)((h->pb.batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, (hipStream_t)stream,
+                       h->pb.batch, h->d_params, weights);
+    HIPCHK(h, hipGetLastError());
+    h->weights_changed = true;
+    return MPCB_OK;
+}
+
 int mpcb_step(mpcb_handle *h, const mpcb_step_io *io, int reset, void *stream)
 {
     return mpcb_step_ref(h, io, nullptr, 0, reset, stream);
@@ -633,6 +667,13 @@ int mpcb_step_warm(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
 int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                    const mpcb_step_sens_out *sens, void *stream)
 {
+    return mpcb_step_sens_w(h, io, yref, ref_changed, warm, reset, sens, nullptr, stream);
+}
+
+// (du0_dw == NULL: all of the above; otherwise the kernels that also form the weight sensitivity, supersets of the sens ones)
+int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                     const mpcb_step_sens_out *sens, double *du0_dw, void *stream)
+{
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
     if (!h->controller) return fail(h, MPCB_ESTATE, "mpcb_step needs a handle set up by mpcb_setup_controller");
@@ -644,20 +685,24 @@ int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
             return fail(h, MPCB_EINVAL, "mpcb_step_sens: the sensitivities of u0 are those of an SQP_RTI step's QP; this controller runs full SQP");
         if (!sens->du0_dx || !sens->valid) return fail(h, MPCB_EINVAL, "mpcb_step_sens: du0_dx and valid must be provided");
     }
-    const int variant = sens ? 2 : warm ? 1 : 0;
+    if (du0_dw && !sens) return fail(h, MPCB_EINVAL, "mpcb_step_sens_w: du0_dw needs sens (du0_dx and valid)");
+    const int variant = du0_dw ? 3 : sens ? 2 : warm ? 1 : 0;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     StepIO sio;
     std::memcpy(&sio, io, sizeof(mpcb_step_io));
     sio.yref = yref;
-    sio.ref_changed = ref_changed != 0 ? 1 : 0;
+    // (new weights make the carried linearisation stale exactly as a new reference does)
+    sio.ref_changed = (ref_changed != 0 || h->weights_changed) ? 1 : 0;
     sio.warm = warm;
+    sio.du0_dw = du0_dw;
     if (sens) { sio.du0_dx = sens->du0_dx; sio.du0_dyref = sens->du0_dyref; sio.sens_valid = sens->valid; }
     const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
     if (h->engine == MPCB_ENGINE_STREAM) {
         // throughput engine: one wavefront per simulation, static LDS only, no work queue
         HIPCHK(h, hipEventRecord(h->ev0, s));
-        if (variant == 2) launch_stream_step_sens(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        if (variant == 3) launch_stream_step_sensw(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        else if (variant == 2) launch_stream_step_sens(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         else if (variant == 1) launch_stream_step_warm(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         else launch_stream_step(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         HIPCHK(h, hipGetLastError());
@@ -666,12 +711,16 @@ int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
         h->timed = true;
         h->queue_used = false;
         h->reset_next = false;
+        h->weights_changed = false;
         return MPCB_OK;
     }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
     if (int rc = raise_lds_limit(h, variant)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
-    if (variant == 2)
+    if (variant == 3)
+        launch_step_sensw(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
+                          rs, h->pool_doubles);
+    else if (variant == 2)
         launch_step_sens(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
                          rs, h->pool_doubles);
     else if (variant == 1)
@@ -686,6 +735,7 @@ int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
     h->timed = true;
     h->queue_used = false;
     h->reset_next = false;
+    h->weights_changed = false;
     return MPCB_OK;
 }
 

@@ -110,6 +110,15 @@ struct InstParams {
     double fast_off;    // 0: the bound-inactive fast path of the QP solve is on (mpc_ipm.h, ipm::FAST_MARGIN); 1: every QP through the interior-point loop
 };
 
+// The cost weights that can change at run time (mpcb_set_weights): w_u, w_qddot, w_task[0..4] -- parameters [3], [4], [56..60] of the
+// packed record, in this order.  Nothing else of InstParams is derived from them (mpc_pack.h pack_inst_params).
+constexpr int NWEIGHT = 7;
+MPC_HD void put_weights(InstParams &P, const double *w)
+{
+    P.w_u = w[0]; P.w_qddot = w[1];
+    for (int i = 0; i < NTASK; i++) P.w_task[i] = w[2 + i];
+}
+
 // Batch-uniform problem description (== mpcb_problem).
 struct Problem {
     int batch;
@@ -143,7 +152,7 @@ struct Outputs {
 // Device pointers of one controller step (mpcb_step_io, then the task reference of mpcb_step_ref): the caller's feedback states in,
 // solver.get(0,'u') and the step's statistics out, batch-major.  x_pred / u_pred may be null (not written).  The members past
 // u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged", one that stops
-// at ref_changed "every simulation carries its solver memory", one that stops at warm "no sensitivities".
+// at ref_changed "every simulation carries its solver memory", one that stops at warm "no sensitivities", one that stops at sens_valid "none to the weights".
 struct StepIO {
     const double *xhat;  // [batch][12]
     double *u0;          // [batch][6]
@@ -162,6 +171,8 @@ struct StepIO {
     double *du0_dx = nullptr;       // [batch][6][12] d u0 / d xhat
     double *du0_dyref = nullptr;    // [batch][N][NTASK][6] (d u0 / d yref_k)', or null (not written)
     int *sens_valid = nullptr;      // [batch] 1: exact sensitivities written, 0: NaN
+    // mpcb_step_sens_w: the sensitivity of u0 to the seven cost weights, read by the sens_w kernels only
+    double *du0_dw = nullptr;       // [batch][NWEIGHT][6] d u0 / d weight_p
 };
 
 // How a simulation's solver memory enters a controller step (MPCB_WARM_*); any other value is WARM_CARRY.

@@ -184,5 +184,50 @@ MPC_HD double sens_project(const InstParams &P, int i, int c, const GG &G, const
 // M_1 = -B R~_0^-1: rows j and 6 + j of column c from ri = R~_0^-1 (j, c)
 MPC_HD void sens_start(const InstParams &P, int j, double ri, double &mq, double &mv) { mq = -P.b1[j] * ri; mv = -P.b2[j] * ri; }
 
+// ---- sensitivity of u0 to the seven cost weights (mpcb_step_sens_w): w_u, w_qddot, the task weights of g1..g5 -----------------------
+// The QP's matrices are affine in the weights, so d u0 / d weight_p = sum_k (d u0 / d g_k) (d/d weight_p of the stage gradient at the
+// QP's solution).  M_k above is (d u0 / d gx_k)'; the input gradient reaches u0 through the feed-forward of its own stage,
+// Nu_k = (d u0 / d gu_k)' = -K_k M_k (6x6; a perturbation of gu_k moves the backward vector p_k by -K_k' of it, and p_k acts as gx_k
+// does), Nu_0 = -R~_0^-1.  With u+ = U_k + du_k, v+ the qdot half of X_k + dx_k and rho = r_k + G_k dx_k (unweighted) the stage
+// gradient's derivatives are 2 dt u+ (u rows, w_u), dt cq^2 (u+ - v+) (u rows) and its negative (qdot rows, w_qddot), and
+// dt G_i' rho_i (x rows, task weight i).  No weight is divided by: a weight of 0 has its derivative.
+// sens_advance that also hands back nu = Nu_k[j][c] (the same arithmetic: M_{k+1} is bit for bit sens_advance's)
+template <class KK, class MM>
+MPC_HD void sensw_advance(const InstParams &P, int j, int c, const KK &K, const MM &Mt, double &mq, double &mv, double &nu)
+{
+    double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int i = 0; i < NX; i += 2) { t0 += K[j * 12 + i] * Mt[c * 12 + i]; t1 += K[j * 12 + i + 1] * Mt[c * 12 + i + 1]; }
+    const double t = t0 + t1, q = Mt[c * 12 + j], v = Mt[c * 12 + 6 + j];
+    mq = q + P.a12[j] * v - P.b1[j] * t;
+    mv = P.a22[j] * v - P.b2[j] * t;
+    nu = -t;
+}
+// lane (j, c)'s addends of one stage to du0_dw[0][c] (w_u) and du0_dw[1][c] (w_qddot): nu = Nu_k[j][c], mv = M_k[6 + j][c] (0 at
+// stage 0), up = u+_kj, vp = v+_kj
+MPC_HD void sensw_input(const InstParams &P, int j, double nu, double mv, double up, double vp, double &a_u, double &a_qddot)
+{
+    a_u = nu * (2.0 * P.dt * up);
+    a_qddot = (nu - mv) * (P.dt * P.cq[j] * P.cq[j] * (up - vp));
+}
+// (G_k M_k)[i][c], i < NTASK: the sum sens_project scales by -dt w_i
+template <class GG, class MM>
+MPC_HD double sensw_gm(int i, int c, const GG &G, const MM &Mt)
+{
+    double s = 0.0, sv = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; j++) { s += G[i * 6 + j] * Mt[c * 12 + j]; sv += G[30 + j] * Mt[c * 12 + 6 + j]; }
+    return i == 4 ? s + sv : s;
+}
+// rho_i = r_i + (G_k dx_k)_i, the linearised task residual at the QP's solution: r [5] unweighted, dq / dv [6] the halves of dx_k
+template <class GG, class RR, class DQ, class DV>
+MPC_HD double sensw_rho(int i, const GG &G, const RR &r, const DQ &dq, const DV &dv)
+{
+    double s = 0.0, sv = 0.0;
+#pragma unroll
+    for (int j = 0; j < 6; j++) { s += G[i * 6 + j] * dq[j]; sv += G[30 + j] * dv[j]; }
+    return r[i] + (i == 4 ? s + sv : s);
+}
+
 }  // namespace nlp
 }  // namespace mpcb

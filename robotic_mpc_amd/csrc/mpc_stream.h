@@ -2286,9 +2286,25 @@ SE_PASS void shift_pass(int N)
 // into it ([GQ | GV] and K, every load of a block in flight before the first use), the block runs from LDS with M (transposed,
 // double-buffered) in LDS too, and its rows leave as one contiguous run.  dx [6][12], dy [NMAX][NTASK][6] or null, valid: this
 // simulation's; rows of dy past its own horizon N are zero (those reference rows are never read).
+// SW (the kernel of mpcb_step_sens_w): also dw [NWEIGHT][6] = d u0 / d weight (mpc_nlp.h sensw_*).  A block then brings in, per stage,
+// the QP's step [du | dq | dv] from the slot that holds the QP iterate (`slot`: the accepted candidate's, fast_commit comment), the
+// [qdot | U] run of G1 and the unweighted task residual r of G2 (SENSW_WX doubles; blocks of SENSW_CH stages).  Lane (j, c) of the
+// recursion keeps three partial sums in registers over all blocks -- the j-th addends of rows 0 (w_u) and 1 (w_qddot) of column c and,
+// j < NTASK, task row j; after the last stage one pass through LDS adds the six addends and the 42 values leave as one run.  Stage 0
+// enters through Nu_0 = -R~_0^-1 alone (M_0 = 0): rows 0 and 1, nothing for the task rows.
 constexpr int SENS_WG = 36, SENS_WO = NTASK * NU, SENS_CH = (RING_DOUBLES - 2 * 72) / (SENS_WG + 72 + SENS_WO);
-static_assert(SENS_CH >= 1 && O_GV == O_GQ + 30, "sens_pass staging");
-SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, bool exact)
+constexpr int SENSW_WX = 36, SENSW_WR = 3 * 36;      // [du 6 | dq 6 | dv 6 | qdot 6 | U 6 | r 5 | pad]; the partial sums
+constexpr int SENSW_CH = (RING_DOUBLES - 2 * 72 - SENSW_WR) / (SENS_WG + 72 + SENS_WO + SENSW_WX);
+static_assert(SENS_CH >= 1 && SENSW_CH >= 1 && O_GV == O_GQ + 30 && O_U == O_X + 12, "sens_pass staging");
+template <bool SW>
+struct SensWArgs {};
+template <>
+struct SensWArgs<true> {
+    double *dw;     // [NWEIGHT][6] of this simulation, or null
+    int slot;       // 0: the QP's step is in G1 [O_QW ..), 1: in G3 [O_DW ..)
+};
+template <bool SW = false>
+SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, bool exact, SensWArgs<SW> wa = {})
 {
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
@@ -2296,20 +2312,33 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
     const int lane = threadIdx.x;
     MPC_GLOBAL double *const dx = (MPC_GLOBAL double *)dx_, *const dy = (MPC_GLOBAL double *)dy_;
     MPC_GLOBAL int *const valid = (MPC_GLOBAL int *)valid_;
+    MPC_GLOBAL double *dw = nullptr;
+    if constexpr (SW) dw = (MPC_GLOBAL double *)wa.dw;
     __builtin_amdgcn_s_waitcnt(0);                                // nothing of the forward sweep is still on its way into the ring
     fence();
     if (!uni(exact ? 1 : 0)) {
         const double nan = __builtin_nan("");
         for (int e = lane; e < NU * NX; e += WAVE) dx[e] = nan;
         if (dy) for (int e = lane; e < NMAX * SENS_WO; e += WAVE) dy[e] = nan;
+        if constexpr (SW) {
+            if (dw && lane < NWEIGHT * NU) dw[lane] = nan;
+        }
         if (lane == 0) *valid = 0;
         return;
     }
+    constexpr int CH = SW ? SENSW_CH : SENS_CH;
     const int ldd = w.ld / 8;
     const MPC_GLOBAL double *const g2 = (const MPC_GLOBAL double *)w.G2, *const g4 = (const MPC_GLOBAL double *)w.G4;
-    double *const Mt = sm.ring, *const gb = Mt + 2 * 72, *const kb = gb + SENS_CH * SENS_WG, *const ob = kb + SENS_CH * 72;
+    double *const Mt = sm.ring, *const gb = Mt + 2 * 72 + (SW ? SENSW_WR : 0), *const kb = gb + CH * SENS_WG, *const ob = kb + CH * 72;
+    double *const xb = ob + CH * SENS_WO, *const sb = Mt + 2 * 72;          // (SW) the staged operands; the partial sums
+    const MPC_GLOBAL double *const g1 = (const MPC_GLOBAL double *)w.G1;
+    const MPC_GLOBAL double *st = nullptr;                                  // (SW) the QP's step of stage 0
+    if constexpr (SW) st = uni(wa.slot) ? (const MPC_GLOBAL double *)w.G3 + O_DW : g1 + O_QW;
+    double a_u = 0.0, a_a = 0.0, a_t = 0.0;
     {
         const double ka = g4[SK + lane], kc = g4[SK + imin(WAVE + lane, NU * NX - 1)], ri = g4[SRI + imin(lane, 35)];
+        double s0 = 0.0, u0 = 0.0;
+        if constexpr (SW) { s0 = st[imin(lane, 35) / 6]; u0 = g1[O_U + imin(lane, 35) / 6]; }
         dx[lane] = -ka;
         if (WAVE + lane < NU * NX) dx[WAVE + lane] = -kc;
         if (lane < 36) {
@@ -2317,6 +2346,8 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
             double mq, mv;
             nlp::sens_start(P, j, ri, mq, mv);
             Mt[cc * 12 + j] = mq; Mt[cc * 12 + 6 + j] = mv;
+            // stage 0: Nu_0 = -R~_0^-1, M_0 = 0; x_0 + dx_0 is x_hat
+            if constexpr (SW) nlp::sensw_input(P, j, -ri, 0.0, u0 + s0, sm.xhat[6 + j], a_u, a_a);
         }
         // stage 0's reference row does not reach u0 (x_0 is pinned to x_hat); nor do rows past this simulation's horizon
         if (dy) {
@@ -2326,10 +2357,10 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
         if (lane == 0) *valid = 1;
     }
     fence();
-    if (!dy) return;
+    if (!dy && !(SW && dw)) return;
     int cur = 0;
-    for (int k0 = 1; k0 < N; k0 += SENS_CH) {
-        const int n = imin(SENS_CH, N - k0);
+    for (int k0 = 1; k0 < N; k0 += CH) {
+        const int n = imin(CH, N - k0);
         for (int e = lane; e < n * SENS_WG; e += WAVE) {
             const int r = e / SENS_WG;
             gb[e] = g2[(size_t)(k0 + r) * ldd + O_GQ + (e - r * SENS_WG)];
@@ -2338,21 +2369,59 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
             const int r = e / 72;
             kb[e] = g4[(size_t)(k0 + r) * ldd + SK + (e - r * 72)];
         }
+        if constexpr (SW) {
+            for (int e = lane; e < n * SENSW_WX; e += WAVE) {
+                const int r = e / SENSW_WX, q = e - r * SENSW_WX;
+                const size_t k = (size_t)(k0 + r) * ldd;
+                xb[e] = q < 18 ? st[k + q] : q < 30 ? g1[k + O_X + 6 + (q - 18)] : g2[k + O_R + imin(q - 30, NTASK - 1)];
+            }
+        }
         fence();
         for (int r = 0; r < n; r++) {
             const double *kk = kb + r * 72, *m = Mt + cur * 72, *g = gb + r * SENS_WG;
             double *mn = Mt + (cur ^ 1) * 72, *o = ob + r * SENS_WO;
             if (lane < 36) {
                 const int j = lane / 6, cc = lane - j * 6;
-                if (j < NTASK) o[j * 6 + cc] = nlp::sens_project(P, j, cc, g, m);
-                double mq, mv;
-                nlp::sens_advance(P, j, cc, kk, m, mq, mv);
-                mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+                if constexpr (SW) {
+                    const double *x = xb + r * SENSW_WX;
+                    if (j < NTASK) {
+                        const double gm = nlp::sensw_gm(j, cc, g, m);
+                        o[j * 6 + cc] = -P.dt * P.w_task[j] * gm;
+                        a_t += P.dt * nlp::sensw_rho(j, g, x + 30, x + 6, x + 12) * gm;
+                    }
+                    double mq, mv, nu, au, aa;
+                    nlp::sensw_advance(P, j, cc, kk, m, mq, mv, nu);
+                    nlp::sensw_input(P, j, nu, m[cc * 12 + 6 + j], x[24 + j] + x[j], x[18 + j] + x[12 + j], au, aa);
+                    a_u += au; a_a += aa;
+                    mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+                } else {
+                    if (j < NTASK) o[j * 6 + cc] = nlp::sens_project(P, j, cc, g, m);
+                    double mq, mv;
+                    nlp::sens_advance(P, j, cc, kk, m, mq, mv);
+                    mn[cc * 12 + j] = mq; mn[cc * 12 + 6 + j] = mv;
+                }
             }
             fence();
             cur ^= 1;
         }
-        for (int e = lane; e < n * SENS_WO; e += WAVE) dy[(size_t)k0 * SENS_WO + e] = ob[e];
+        if (!SW || dy) for (int e = lane; e < n * SENS_WO; e += WAVE) dy[(size_t)k0 * SENS_WO + e] = ob[e];
+        fence();
+    }
+    if constexpr (SW) {
+        // the six addends of rows 0 and 1 meet through LDS; 42 values, one run
+        if (lane < 36) { sb[lane] = a_u; sb[36 + lane] = a_a; sb[72 + lane] = a_t; }
+        fence();
+        if (lane < NWEIGHT * NU) {
+            const int p = lane / 6, cc = lane - p * 6;
+            double v;
+            if (p < 2) {
+                const double *a = sb + p * 36 + cc;
+                v = ((a[0] + a[6]) + (a[12] + a[18])) + (a[24] + a[30]);
+            } else {
+                v = sb[72 + (p - 2) * 6 + cc];
+            }
+            dw[lane] = v;
+        }
         fence();
     }
 }
@@ -2364,7 +2433,8 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
 // WARM (the kernel of mpcb_step_warm): io.warm gives this simulation's own mode -- WARM_RESET is `reset` for it alone, WARM_SHIFT moves
 // its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
 // SENS (the kernel of mpcb_step_sens, SQP_RTI): the sensitivities of u0 leave through io.du0_dx / du0_dyref / sens_valid (sens_pass).
-template <class FT, bool WARM = false, bool SENS = false>
+// SENSW (the kernel of mpcb_step_sens_w; with SENS): and its sensitivity to the cost weights through io.du0_dw.
+template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
@@ -2401,7 +2471,13 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
     fence();
     const double t0 = wclock();
     StepStats s;
-    if constexpr (SENS) {
+    if constexpr (SENS && SENSW) {
+        s = mpc_step<FT>(pb, c, lin, search, nullptr, false, [&](bool exact) {
+            sens_pass<true>(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * NMAX * NTASK * NU : nullptr,
+                            io.sens_valid + inst, N, NMAX, exact,
+                            SensWArgs<true>{io.du0_dw ? io.du0_dw + (size_t)inst * NWEIGHT * NU : nullptr, c.cur});
+        });
+    } else if constexpr (SENS) {
         s = mpc_step<FT>(pb, c, lin, search, nullptr, false, [&](bool exact) {
             sens_pass(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * NMAX * NTASK * NU : nullptr,
                       io.sens_valid + inst, N, NMAX, exact);

@@ -87,7 +87,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
-            "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens")
+            "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -135,6 +135,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_step_ref.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, C.c_int, C.c_void_p]
     lib.mpcb_step_warm.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.c_void_p]
     lib.mpcb_step_sens.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.POINTER(MpcbStepSensOut), C.c_void_p]
+    lib.mpcb_set_weights.argtypes = [C.c_void_p, _dp, C.c_void_p]
+    lib.mpcb_step_sens_w.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.POINTER(MpcbStepSensOut), _dp,
+                                     C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -337,11 +340,23 @@ class MpcBatchEngine:
         self._check(self.lib.mpcb_step_warm(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), C.c_void_p(stream)),
                     "mpcb_step_warm")
 
+    def set_weights(self, weights, stream: Optional[int] = None):
+        """mpcb_set_weights: the seven cost weights of every simulation <- `weights`, a contiguous device tensor [batch, 7] float64
+        (w_u, w_qddot, the task weights of g1..g5), read during the launch only; asynchronous on `stream` (default: the current
+        torch stream).  The next step linearises again at its start."""
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self.lib.mpcb_set_weights(self._h, C.cast(C.c_void_p(weights.data_ptr()), _dp), C.c_void_p(stream)),
+                    "mpcb_set_weights")
+
     def step_sens(self, io, yref=None, ref_changed: bool = False, warm=None, reset: bool = False, sens=None,
-                  stream: Optional[int] = None):
+                  stream: Optional[int] = None, du0_dw=None):
         """mpcb_step_sens: step_warm() that also writes the sensitivities of u0 -- `sens` a dict of contiguous device tensors
         du0_dx [batch, 6, 12] float64, valid [batch] int32 and optionally du0_dyref [batch, N, 5, 6] float64, or None: step_warm()
-        exactly."""
+        exactly.  `du0_dw` (a contiguous device tensor [batch, 7, 6] float64; needs `sens`): mpcb_step_sens_w, which also writes
+        the sensitivity of u0 to the cost weights there."""
         if stream is None:
             import torch
 
@@ -356,6 +371,10 @@ class MpcBatchEngine:
                                  C.cast(C.c_void_p(dy.data_ptr()), _dp) if dy is not None else None,
                                  C.cast(C.c_void_p(sens["valid"].data_ptr()), _ip))
             sp = C.byref(so)
+        if du0_dw is not None:
+            self._check(self.lib.mpcb_step_sens_w(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
+                                                  C.cast(C.c_void_p(du0_dw.data_ptr()), _dp), C.c_void_p(stream)), "mpcb_step_sens_w")
+            return
         self._check(self.lib.mpcb_step_sens(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
                                             C.c_void_p(stream)), "mpcb_step_sens")
 

@@ -16,10 +16,11 @@ iterate moved one stage, BatchController.step(shift=True): the shift pass and on
 each line also reports the closed-loop effect on a schedule that slides one stage per step (row j of step k is stage k + j of one
 ramp): the medians over steps 100.. of the stationarity residual and of max |u_pred - the previous step's u_pred|.
 `--sens` asks every step for the sensitivities of u0 (BatchController.step(sens=True): the sensitivity pass in the step kernel) and
-reports the fraction of steps that had them.
+reports the fraction of steps that had them; `--sens-w` asks for the sensitivity to the cost weights as well
+(BatchController.step(sens_w=True)).
 
     python scripts/controller_rate.py [--batch 256 ...] [--engine latency|stream ...] [--N 100] [--steps 600] [--solver SQP_RTI]
-                                      [--skip-rollout] [--ref none|once|every ...] [--warm carry|shift ...] [--sens]
+                                      [--skip-rollout] [--ref none|once|every ...] [--warm carry|shift ...] [--sens] [--sens-w]
 """
 import argparse
 import json
@@ -72,7 +73,10 @@ def main():
     ap.add_argument("--warm", nargs="+", choices=("carry", "shift"), default=None)
     # every step also returns du0_dx / du0_dyref / sens_valid (the sensitivity pass)
     ap.add_argument("--sens", action="store_true")
+    # ... and du0_dw (the weight sums inside the sensitivity pass); implies --sens
+    ap.add_argument("--sens-w", action="store_true")
     args = ap.parse_args()
+    args.sens = args.sens or args.sens_w
     for B in args.batch:
         for eng in args.engine:
             for ref in args.ref:
@@ -139,7 +143,7 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
             if events is not None:
                 events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
                 events[-1][0].record()
-            kw = dict(sens=True) if args.sens else {}
+            kw = dict(sens_w=True) if args.sens_w else dict(sens=True) if args.sens else {}
             if warm == "shift":
                 kw.update(shift=True)
             o = ctl.step(x, yref=sched[k % 2] if ref == "every" else None, **kw)
@@ -163,7 +167,7 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
     closed_loop(ev)
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
-    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, sens=bool(args.sens), step_loop_ms=round(loop_ms, 3),
+    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, sens=bool(args.sens), sens_w=bool(args.sens_w), step_loop_ms=round(loop_ms, 3),
                step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
                step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
                launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
