@@ -5,6 +5,8 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -26,30 +28,37 @@ def _stale(target: str) -> bool:
     return any(os.path.getmtime(s) > t for s in srcs)
 
 
+def _compile(target: str, flags, verbose: bool = False) -> None:
+    """One hipcc per translation unit, side by side (the units are independent modules and the largest takes most of the time a
+    single command spends on all of them one after the other), then one link.  Objects live in a temporary directory."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    common = [hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", *flags]
+    jobs = max(1, min(len(SOURCES), int(os.environ.get("MAX_JOBS", 0)) or len(os.sched_getaffinity(0))))
+    with tempfile.TemporaryDirectory(prefix="mpcb_build_") as d:
+        cmds = [common + ["-c", os.path.join(CSRC, f), "-o", os.path.join(d, f + ".o")] for f in SOURCES]
+        if verbose:
+            print("\n".join(" ".join(c) for c in cmds), file=sys.stderr)
+        with ThreadPoolExecutor(jobs) as pool:
+            list(pool.map(subprocess.check_call, cmds))
+        subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-fPIC", "-shared", "-o", target + ".tmp", *[c[-1] for c in cmds]])
+        os.replace(target + ".tmp", target)
+
+
 def build(force: bool = False, profile: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 -> robotic_mpc_amd/libmpcbatch.so (cross-compiles without a GPU)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     target = LIB_PROF if profile else LIB
     if not force and not _stale(target):
         return target
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-shared", "-std=c++17", "-o", target,
-           *[os.path.join(CSRC, f) for f in SOURCES]]
-    if profile:
-        cmd.insert(1, "-DMPCB_PROFILE")
-    if verbose:
-        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+    flags = (["-DMPCB_PROFILE"] if profile else []) + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
+    _compile(target, flags, verbose)
     return target
 
 
 def build_variant(name: str, defines) -> str:
     """Diagnostic builds (scripts/): robotic_mpc_amd/libmpcbatch_<name>.so with extra -D switches, rebuilt when stale."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     target = os.path.join(HERE, f"libmpcbatch_{name}.so")
     if _stale(target):
-        subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-shared", "-std=c++17", *[f"-D{d}" for d in defines],
-                               "-o", target, *[os.path.join(CSRC, f) for f in SOURCES]])
+        _compile(target, [f"-D{d}" for d in defines])
     return target
 
 

@@ -58,6 +58,12 @@ constexpr int L2W = 114;
 #ifndef MPCB_FUSE
 #define MPCB_FUSE 1
 #endif
+// 1 (default): the factorisation sweep's recursion wavefront eliminates the right-hand sides inside the LDL' loop and stores K / R~^-1
+// under one exec mask; 0: the solve behind the loop and two store branches, as written before (A/B builds).  The same operations on
+// the same values either way: the two builds agree bit for bit.
+#ifndef MPCB_FACT_PIPE
+#define MPCB_FACT_PIPE 1
+#endif
 #ifdef MPCB_PROFILE
 #define PROF_T0(v) const double v = ex.clock()
 #define PROF_ADD(i, v) prof[i] += ex.clock() - v
@@ -1118,7 +1124,11 @@ struct Engine {
         const ResMap rm = res_map();
         const int CH = RES ? chunk_len_in(rm.scr_n, 2 * (WR + WF), 2 * WR) : chunk_len(2 * (WR + W4), 2 * WR);
         typename Ex::template PerLane<FactLane> fl;
+        // MPCB_FACT_PIPE: where the lane stores its column of K / R~^-1: offset of the chunk, doubles per stage, doubles per row
+        typename Ex::template PerLane<int> scb, sks, sst;
         ex.seq([&](int lane) {
+            sks.at(lane) = RES && lane < 12 ? 72 : WF;
+            sst.at(lane) = lane < 12 ? 12 : 6;
             FactLane &f = fl.at(lane);
             const int a = lane < 36 ? lane / 6 : 0, b = lane < 36 ? lane % 6 : 0;
             f.a = a; f.b = b;
@@ -1294,7 +1304,64 @@ struct Engine {
                     continue;
                 }
                 // ---- B: LDL' (right-looking) + one right-hand side per lane
-#ifndef MPCB_DIAG_NO_B
+#if !defined(MPCB_DIAG_NO_B) && MPCB_FACT_PIPE
+                // The right-hand side is loaded with R~ and eliminated column by column as L appears (the same products in the same
+                // order per x[i] as a forward solve behind the loop); every lane does it, only lanes < 18 store, through one
+                // per-lane address: no exec-mask branches around the solve or between the K and the R~^-1 columns.
+                ex.seq([&](int lane) {
+                    const double *St = sm.St2[sb];
+                    double A_[6][6];
+#pragma unroll
+                    for (int i = 0; i < 6; i++)
+#pragma unroll
+                        for (int j = 0; j <= i; j++) A_[i][j] = sm.Rt[i * 6 + j];
+                    double x[6];
+                    const int col = lane < 12 ? lane : 0;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) x[i] = St[i * 12 + col];   // unconditional loads, then select
+#pragma unroll
+                    for (int i = 0; i < 6; i++) x[i] = lane < 12 ? x[i] : (i == lane - 12 ? 1.0 : 0.0);
+                    if (ex.uni(k == imin(k1, Nl - 1))) {
+                        // where the lane's column goes, as an offset into the pool: K (the resident array, or the chunk record) for
+                        // lanes < 12, R~^-1 (the chunk record) for the others; per stage it moves by `sks` doubles
+                        const int rec = (int)(vf - ex.pool()) - k0 * WF - FO;
+                        const int kcol = RES ? (int)(rm.K - ex.pool()) + lane : rec + O_K + lane;
+                        scb.at(lane) = lane < 12 ? kcol : rec + O_RI + (lane - 12);
+                    }
+                    double dinv[6];
+#pragma unroll
+                    for (int j = 0; j < 6; j++) {
+#ifdef MPCB_DIAG_NO_LDL
+                        dinv[j] = A_[j][j]; continue;
+#endif
+                        dinv[j] = fast_rcp(A_[j][j]);
+                        double lj[6];
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++) lj[i] = A_[i][j] * dinv[j];
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++)
+#pragma unroll
+                            for (int r = j + 1; r <= i; r++) A_[i][r] -= lj[i] * A_[r][j];
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++) A_[i][j] = lj[i];   // L(i,j)
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++) x[i] -= lj[i] * x[j];   // L y = rhs: column j, as soon as it exists
+                    }
+#pragma unroll
+                    for (int i = 0; i < 6; i++) x[i] *= dinv[i];
+#pragma unroll
+                    for (int j = 5; j >= 0; j--) {         // L' x = y, column oriented
+#pragma unroll
+                        for (int i = 0; i < j; i++) x[i] -= A_[j][i] * x[j];
+                    }
+                    if (lane < 18) {
+                        double *xp = ex.pool() + (scb.at(lane) + k * sks.at(lane));
+                        const int st = sst.at(lane);
+#pragma unroll
+                        for (int i = 0; i < 6; i++) xp[i * st] = x[i];
+                    }
+                });
+#elif !defined(MPCB_DIAG_NO_B)
                 ex.seq([&](int lane) {
                     const double *St = sm.St2[sb];
                     double A_[6][6];
