@@ -307,6 +307,32 @@ int mpcb_set_weights(mpcb_handle *h, const double *weights /* DEVICE [batch][MPC
 int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                      const mpcb_step_sens_out *sens, double *du0_dw, void *stream);
 
+/* ---- joint-wise terminal cost with a terminal reference ---- */
+#define MPCB_NTERM 30   /* pqq[6] pqv[6] pvv[6] x_e[12] */
+/* mpcb_step_sens with a terminal cost on the last stage of each simulation's horizon (SQP_RTI controllers):
+ *   l_N(x) = 1/2 sum_j [q_j - q_e,j, v_j - v_e,j] [[pqq_j, pqv_j], [pqv_j, pvv_j]] [.]',   x = [q; qdot], x_e = [q_e; qdot_e],
+ * one symmetric 2x2 block per joint -- the shape of the discrete LQR cost-to-go of this prediction model, six decoupled two-state
+ * joints, for diagonal state and input weights.  It is NOT scaled by dt.  term[i] = pqq[6] | pqv[6] | pvv[6] | x_e[12] of simulation i,
+ * a DEVICE array [batch][MPCB_NTERM] read during the launch only, like yref; all-zero blocks are exactly no terminal cost.  Keep every
+ * block positive semidefinite (pqq, pvv >= 0, pqq pvv >= pqv^2); nothing is validated.
+ * In the Gauss-Newton QP of the step at the iterate (X, U), with P the 12x12 matrix of the blocks:
+ *   H_N = levenberg_marquardt I + P,   g_N = P (X_N - x_e);
+ * the cost output adds l_N at the returned iterate and the stage-N rows of the stationarity residual include P (X_N - x_e); the
+ * bound-inactive fast path and the interior-point loop both solve this QP.  On a ragged batch stage N is each simulation's own
+ * horizon end.  MPCB_WARM_SHIFT is unchanged (x_N is propagated by the model as before).
+ * term_changed != 0 (the blocks or x_e differ from the previous step's, or the terminal cost was switched on or off) makes every
+ * simulation linearise again at the start of the step, exactly as ref_changed does.
+ * With sens, du0_dx and du0_dyref are the exact Jacobians of this QP as before (the gain recursion starts from P_N), and
+ * du0_dxe[i] = d u0 / d x_e, DEVICE [batch][6][12] or NULL, is written next to them: NaN where valid[i] == 0.  With a horizon of 1 it
+ * is not zero.
+ * term == NULL && term_changed == 0 && du0_dxe == NULL is mpcb_step_sens exactly (same kernels, same bits); term == NULL with
+ * term_changed != 0 is mpcb_step_sens from a fresh linearisation.  MPCB_EINVAL: term != NULL on a full-SQP controller; du0_dxe
+ * without sens or without term.  MPCB_ESTATE on a handle not set up as a controller.  The weight sensitivity (mpcb_step_sens_w) is
+ * not offered together with a terminal cost. */
+int mpcb_step_term(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const mpcb_step_sens_out *sens, const double *term /* DEVICE [batch][MPCB_NTERM] or NULL */, int term_changed,
+                   double *du0_dxe /* DEVICE [batch][6][12] or NULL */, void *stream);
+
 /* ---- the controller step on either kernel family ---- */
 #define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
 #define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */

@@ -28,6 +28,10 @@ reference ``du0_dyref`` of the step's QP, exact wherever the bound-inactive fast
 ``set_weights(w)`` changes the seven cost weights (w_u, w_qddot and the task weights of g1..g5) between steps without building
 another controller -- the warm start carries -- and ``step(..., sens_w=True)`` also returns ``du0_dw``, the sensitivity of ``u0``
 to them: what a gradient-based tuning of a batch of controllers needs (``differentiable_step(..., weights=w)``).
+
+``set_terminal_cost(P, x_ref)`` closes the horizon with a joint-wise quadratic terminal cost around a terminal reference (SQP_RTI
+controllers): one 2x2 block per joint, the shape of the discrete LQR cost-to-go of the prediction model
+(``robotic_mpc_amd.terminal.lqr_terminal`` designs one).  While it is in force ``step(..., sens=True)`` also returns ``du0_dxe``.
 """
 from __future__ import annotations
 
@@ -40,6 +44,7 @@ from .engine import CONTROLLER_ENGINES, STEP_FIELDS, WARM_RESET, WARM_SHIFT, Mpc
 
 NREF = 5    # task outputs with a reference (MPCB_NREF, include/mpcbatch.h)
 NWEIGHT = 7  # cost weights that can change at run time (MPCB_NWEIGHT): w_u, w_qddot, the task weights of g1..g5
+NTERM = 30   # doubles of a simulation's terminal cost (MPCB_NTERM): pqq[6] pqv[6] pvv[6] x_e[12]
 
 
 class BatchController:
@@ -70,6 +75,13 @@ class BatchController:
     _weights = None
     _weights_stream = None
     _sensw = None
+    # terminal cost (set_terminal_cost): the controller's own [B, 30] device buffer, whether it is in force, whether the next step
+    # must tell the device that it changed, the stream that last wrote it; the du0_dxe buffer of step(sens=True), from the first use
+    _term = None
+    _term_on = False
+    _term_changed = False
+    _term_stream = None
+    _sensxe = None
 
     def __init__(self, configs: Sequence[Mapping], device: int = 0, engine: str = "latency"):
         if engine not in CONTROLLER_ENGINES:
@@ -296,6 +308,106 @@ class BatchController:
             cur.wait_stream(self._weights_stream)
         return self._weights.clone()
 
+    def _check_terminal(self, P, x_ref):
+        """Validates a terminal cost without touching the device -- ``P`` as blocks [B, 6, 3] / [6, 3] (pqq, pqv, pvv per joint) or
+        as a symmetric matrix [B, 12, 12] / [12, 12] over [q; qdot], ``x_ref`` [B, 12] / [12]; float64, numpy arrays or tensors on the
+        controller's device -- and returns (blocks [B or 1, 6, 3], x_ref [B or 1, 12]) of the same kind."""
+        import torch
+
+        B = self.batch
+        if self.configs[0]["solver_type"] != packing.SOLVER_RTI:
+            raise ValueError("set_terminal_cost needs an SQP_RTI controller: the terminal cost is not offered with full SQP")
+        out = []
+        for name, a, shapes in (("P", P, ((B, 6, 3), (6, 3), (B, 12, 12), (12, 12))), ("x_ref", x_ref, ((B, 12), (12,)))):
+            if isinstance(a, np.ndarray):
+                shape, dtype_ok = tuple(a.shape), a.dtype == np.float64
+            elif isinstance(a, torch.Tensor):
+                shape, dtype_ok = tuple(a.shape), a.dtype == torch.float64
+                if a.device.type != "cuda" or a.device.index != self.device:
+                    raise ValueError(f"{name} must live on cuda:{self.device}, got {a.device}")
+            else:
+                raise ValueError(f"{name} must be a torch tensor or a numpy array, got {type(a).__name__}")
+            if shape not in shapes:
+                raise ValueError(f"{name} must have one of the shapes {shapes}, got {shape}")
+            if not dtype_ok:
+                raise ValueError(f"{name} must be float64, got {a.dtype}")
+            if isinstance(a, np.ndarray) and not np.isfinite(a).all():
+                raise ValueError(f"{name} has non-finite entries")
+            out.append(a if len(shape) == len(shapes[0]) else a[None])
+        Pm, xe = out
+        if Pm.shape[-1] == 12:
+            j = np.arange(6)
+            if isinstance(Pm, np.ndarray):
+                # the joint-block pattern exactly: nothing outside the (q_j, qdot_j) blocks, and the two off-diagonal entries of a
+                # block equal up to rounding (the upper one is taken)
+                rest = Pm.copy()
+                rest[:, j, j] = 0.0; rest[:, 6 + j, 6 + j] = 0.0; rest[:, j, 6 + j] = 0.0; rest[:, 6 + j, j] = 0.0
+                if (rest != 0.0).any():
+                    b, r, c = (int(v[0]) for v in np.nonzero(rest))
+                    raise ValueError(f"P[{r}, {c}] = {rest[b, r, c]!r} (simulation {b}) lies outside the joint blocks (q_j, qdot_j): the "
+                                     "terminal cost is joint-wise; full 12x12 weights are not offered")
+                asym = np.abs(Pm[:, j, 6 + j] - Pm[:, 6 + j, j])
+                if (asym > 1e-12 * max(float(np.abs(Pm).max()), 1e-300)).any():
+                    b, jj = (int(v[0]) for v in np.nonzero(asym > 1e-12 * np.abs(Pm).max()))
+                    raise ValueError(f"P is not symmetric: P[{jj}, {6 + jj}] != P[{6 + jj}, {jj}] (simulation {b})")
+                blocks = np.stack([Pm[:, j, j], Pm[:, j, 6 + j], Pm[:, 6 + j, 6 + j]], axis=2)
+            else:
+                blocks = torch.stack([Pm[:, j, j], Pm[:, j, 6 + j], Pm[:, 6 + j, 6 + j]], dim=2)
+        else:
+            blocks = Pm
+        if isinstance(blocks, np.ndarray):
+            pqq, pqv, pvv = blocks[..., 0], blocks[..., 1], blocks[..., 2]
+            if (pqq < 0.0).any() or (pvv < 0.0).any() or (pqq * pvv < pqv * pqv).any():
+                raise ValueError("every joint block of P must be positive semidefinite: pqq >= 0, pvv >= 0, pqq pvv >= pqv^2")
+        return blocks, xe
+
+    def set_terminal_cost(self, P, x_ref=None):
+        """Puts a joint-wise terminal cost in force (SQP_RTI controllers; ``ValueError`` on a full-SQP one): the following steps
+        minimise, besides the stage costs, ``1/2 (x_N - x_ref)' P (x_N - x_ref)`` at the last stage of each simulation's own horizon,
+        not scaled by dt.  ``P`` is given as blocks [B, 6, 3] or [6, 3] -- (pqq, pqv, pvv) of the symmetric 2x2 block of joint j over
+        (q_j, qdot_j) -- or as a symmetric matrix [B, 12, 12] or [12, 12] over [q; qdot] that has exactly that pattern (any other
+        non-zero entry raises ``ValueError`` naming it); ``x_ref`` is [B, 12] or [12].  float64 numpy arrays or tensors on the
+        controller's device; they are copied into the controller's own buffer (later edits have no effect).  The setting stays in
+        force across steps and ``reset()`` until it is set again; ``set_terminal_cost(None)`` switches the terminal cost off.  The
+        next step linearises again first, as after a new reference; everything else carries.  A numpy input is validated before the
+        device is touched (shape, dtype, finite, every block positive semidefinite: pqq, pvv >= 0, pqq pvv >= pqv^2); the values of a
+        device tensor are the caller's to keep valid.  All-zero blocks are exactly no terminal cost.
+        ``robotic_mpc_amd.terminal.lqr_terminal`` designs the blocks of an LQR terminal weight."""
+        import torch
+
+        if P is None:
+            if self._term_on:
+                self._term_on, self._term_changed = False, True
+            return
+        if x_ref is None:
+            raise ValueError("set_terminal_cost needs the terminal reference x_ref with P")
+        blocks, xe = self._check_terminal(P, x_ref)
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(self.device)
+        if self._term is None:
+            self._term = torch.empty((self.batch, NTERM), dtype=torch.float64, device=dev)
+        if self._step_stream is not None and self._step_stream != cur:
+            cur.wait_stream(self._step_stream)        # a step still reading the buffer on another stream finishes first
+        on_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
+        b = on_dev(blocks).expand(self.batch, 6, 3)
+        self._term[:, 0:6].copy_(b[:, :, 0]); self._term[:, 6:12].copy_(b[:, :, 1]); self._term[:, 12:18].copy_(b[:, :, 2])
+        self._term[:, 18:30].copy_(on_dev(xe).expand(self.batch, 12))
+        self._term_stream = cur
+        self._term_on, self._term_changed = True, True
+
+    def terminal_cost(self):
+        """The terminal cost in force: ``None``, or dict(blocks [B, 6, 3], x_ref [B, 12]) of new float64 tensors on the controller's
+        device."""
+        import torch
+
+        if not self._term_on:
+            return None
+        cur = torch.cuda.current_stream(self.device)
+        if self._term_stream is not None and self._term_stream != cur:
+            cur.wait_stream(self._term_stream)
+        t = self._term
+        return dict(blocks=torch.stack([t[:, 0:6], t[:, 6:12], t[:, 12:18]], dim=2).clone(), x_ref=t[:, 18:30].clone())
+
     def step(self, xhat, predict: bool = False, yref=None, shift=False, sens: bool = False, sens_w: bool = False) -> Dict:
         """One MPC step of every controller from the feedback states ``xhat`` ([B, 12] q; qdot, float64: a tensor on the
         controller's device, or a numpy array that is copied there).
@@ -333,9 +445,16 @@ class BatchController:
         is not included.  A weight of 0 has its derivative; with a horizon of 1 the five task rows are exactly zero.
         Over a ``sens=True`` step it costs another 5-11 % of the step rate at N = 100 (latency engine 7 / 9 / 11 % at batch 256 / 1024 /
         4096, throughput engine 5-6 %; 18-28 % against a plain step; ``profiles/controller_step_rate_sensw.txt``); steps that do
-        not ask cost what they did."""
+        not ask cost what they did.
+
+        While a terminal cost is in force (``set_terminal_cost``) the step's QP, ``cost`` and ``residuals`` include it,
+        ``du0_dx`` / ``du0_dyref`` are the exact Jacobians of that QP, and ``sens=True`` adds ``du0_dxe`` [B, 6, 12] = d u0 / d x_ref
+        of the terminal reference (NaN where ``sens_valid`` is 0; not zero with a horizon of 1).  ``sens_w=True`` then raises
+        ``ValueError``: the weight sensitivity is not offered together with a terminal cost."""
         import torch
 
+        if sens_w and self._term_on:
+            raise ValueError("step(sens_w=True) is not offered while a terminal cost is in force (set_terminal_cost(None) switches it off)")
         sens = sens or sens_w
         if sens and self.configs[0]["solver_type"] != packing.SOLVER_RTI:
             raise ValueError("step(sens=True) needs an SQP_RTI controller: the sensitivities of u0 are those of one RTI step's QP")
@@ -356,6 +475,11 @@ class BatchController:
             stream.wait_stream(self._ref_stream)      # the copy of the reference lands before the step reads it
         if self._weights_stream is not None and self._weights_stream != stream:
             stream.wait_stream(self._weights_stream)  # the new weights are in the records before the step reads them
+        if self._term_on and self._term_stream is not None and self._term_stream != stream:
+            stream.wait_stream(self._term_stream)     # the copy of the terminal cost lands before the step reads it
+        # (a terminal cost that was switched off leaves a stale linearisation behind, exactly as a changed reference does)
+        ref_changed = self._ref_changed or (self._term_changed and not self._term_on)
+        term = dict(term=self._term, term_changed=self._term_changed) if self._term_on else {}
         if sens:
             if self._sens is None:
                 dev = torch.device("cuda", self.device)
@@ -366,25 +490,34 @@ class BatchController:
                 stream.wait_stream(self._step_stream)     # a step still writing the buffers on another stream finishes first
             if sens_w and self._sensw is None:
                 self._sensw = torch.zeros((self.batch, NWEIGHT, 6), dtype=torch.float64, device=torch.device("cuda", self.device))
-            self.engine.step_sens(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm,
+            if self._term_on and self._sensxe is None:
+                self._sensxe = torch.zeros((self.batch, 6, 12), dtype=torch.float64, device=torch.device("cuda", self.device))
+            self.engine.step_sens(io, self._yref if self._ref_on else None, ref_changed=ref_changed, warm=warm,
                                   reset=self._reset, stream=stream.cuda_stream,
                                   sens=dict(du0_dx=self._sens["du0_dx"], du0_dyref=self._sens["du0_dyref"], valid=self._sens["sens_valid"]),
-                                  **(dict(du0_dw=self._sensw) if sens_w else {}))
+                                  **(dict(du0_dw=self._sensw) if sens_w else {}),
+                                  **(dict(term, du0_dxe=self._sensxe) if self._term_on else {}))
+        elif self._term_on:
+            self.engine.step_sens(io, self._yref if self._ref_on else None, ref_changed=ref_changed, warm=warm, reset=self._reset,
+                                  stream=stream.cuda_stream, **term)
         elif warm is not None:
-            self.engine.step_warm(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm,
+            self.engine.step_warm(io, self._yref if self._ref_on else None, ref_changed=ref_changed, warm=warm,
                                   reset=self._reset, stream=stream.cuda_stream)
-        elif self._ref_on or self._ref_changed:
-            self.engine.step_ref(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, reset=self._reset,
+        elif self._ref_on or ref_changed:
+            self.engine.step_ref(io, self._yref if self._ref_on else None, ref_changed=ref_changed, reset=self._reset,
                                  stream=stream.cuda_stream)
         else:
             self.engine.step(io, reset=self._reset, stream=stream.cuda_stream)
         self._step_stream = stream
         self._reset = False
         self._ref_changed = False
+        self._term_changed = False
         self._reset_mask = None
         out = {k: v for k, v in io.items() if k != "xhat"}
         if sens:
             out.update(self._sens)
+            if self._term_on:
+                out["du0_dxe"] = self._sensxe
         if sens_w:
             out["du0_dw"] = self._sensw
         return out

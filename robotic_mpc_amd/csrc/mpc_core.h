@@ -145,7 +145,9 @@ MPC_HD void load_constants(Ex &ex, const InstParams *P, const Robot *rb)
     });
 }
 
-template <class Ex>
+// TERM (the kernels of mpcb_step_term only): the controller step with the joint-wise terminal cost of mpc_nlp.h term_* -- a compile-time
+// flag of the engine, so that every pass control_step reaches sees it and the engines of all other kernels are the code they were.
+template <class Ex, bool TERM = false>
 struct Engine {
     static constexpr int NT = Ex::NT;  // lanes per simulation
     Ex &ex;
@@ -157,11 +159,15 @@ struct Engine {
     //   commit_pending  the accepted candidate has not been written to the QP iterate yet: the next NLP pass does it with its update
     //   rhs_valid       G2 already holds the fast path's right-hand side (gt, Gamma = 0, rb) for the current linearisation and x_hat
     bool commit_pending, rhs_valid;
+    // TERM: this simulation's terminal-cost record [pqq 6 | pqv 6 | pvv 6 | x_e 12] in the step's device buffer (control_step sets it).
+    // Wavefront-uniform and needed at stage N only: the passes read it from there where they use it (TermRec), never through LDS.
+    struct NoTerm {};
+    typename std::conditional<TERM, const double *, NoTerm>::type term;
 #ifdef MPCB_PROFILE
     double prof[NPROF];
 #endif
 
-    MPC_HD Engine(Ex &e, const Ctx &cc) : ex(e), c(cc), N(cc.N), lin_cost(0.0), fast_skip(0), fast_back(0), commit_pending(false), rhs_valid(false)
+    MPC_HD Engine(Ex &e, const Ctx &cc) : ex(e), c(cc), N(cc.N), lin_cost(0.0), fast_skip(0), fast_back(0), commit_pending(false), rhs_valid(false), term()
     {
         ex.par([&](int lane) {
             if (lane == 0) { Smem &sm = ex.smem(); sm.w = cc.w; sm.n_hor = cc.N; sm.pool_n = cc.pool_n; }
@@ -401,6 +407,16 @@ struct Engine {
     }
     MPC_HD static double gld(const double *p) { return *(MPC_GLOBAL const double *)p; }
     MPC_HD static void gst(double *p, double v) { *(MPC_GLOBAL double *)p = v; }
+    // the terminal-cost record as the accessor mpc_nlp.h term_* take: uniform global loads
+    struct TermRec {
+        const double *p;
+        MPC_HD double operator[](int i) const { return gld(p + i); }
+    };
+    MPC_HD TermRec term_rec() const
+    {
+        if constexpr (TERM) return TermRec{ex.uni(term)};
+        else return TermRec{nullptr};
+    }
 
     // The fast path's right-hand side of joint j at one stage (Gamma = 0): condensed gradient gt = g at (dw, pi, lam) = 0 with the
     // feedback step dx_0 = x_hat - x_0 embedded, and rb = b + A dx_0.  ONE function with explicit fused multiply-adds for its two
@@ -637,6 +653,13 @@ struct Engine {
                     } else {
 #pragma unroll
                         for (int i = 0; i < W2_LIN; i++) rec[i] = 0.0;
+                        if constexpr (TERM) {
+                            // l_N at the terminal state: this lane's stage has no residual of its own
+                            const TermRec tm = term_rec();
+                            const double *g1 = G1 + (size_t)k * W1;
+#pragma unroll
+                            for (int j = 0; j < 6; j++) csum += nlp::term_cost(tm, j, gld(g1 + O_X + j), gld(g1 + O_X + 6 + j));
+                        }
                     }
                 }
                 if (do_plant && k0 == 0 && lane == NT - WAVE) {
@@ -708,6 +731,10 @@ struct Engine {
                                     ru += P.b1[j] * v[r][3] + P.b2[j] * v[r][4];
                                 }
                                 bound(j, uj, v[r][7], v[r][8], v[r][9], v[r][10], ru);
+                                double tgq = 0.0, tgv = 0.0;      // TERM, stage N: rows q_j, v_j of P (X_N - x_e)
+                                if constexpr (TERM) {
+                                    if (k == Nl) nlp::term_grad(term_rec(), j, qj, vj, tgq, tgv);
+                                }
                                 // q_j (stat_cls<1>)
                                 double rq = 0.0;
                                 if (k >= 1) {
@@ -718,6 +745,7 @@ struct Engine {
                                         rq = P.dt * s_ + v[r][3];
                                     }
                                     rq -= v[r][5];
+                                    if constexpr (TERM) rq += tgq;
                                 }
                                 bound(6 + j, qj, v[r][11], v[r][12], v[r][13], v[r][14], rq);
                                 // v_j (stat_cls<2>)
@@ -728,6 +756,7 @@ struct Engine {
                                         rv += P.a12[j] * v[r][3] + P.a22[j] * v[r][4];
                                     }
                                     rv -= v[r][6];
+                                    if constexpr (TERM) rv += tgv;
                                 }
                                 if (k == 0) { rq = 0.0; rv = 0.0; }    // x_0 is eliminated (lbx_0 = ubx_0)
                                 as_ = fmax(as_, fmax(fabs(ru), fmax(fabs(rq), fabs(rv))));
@@ -738,10 +767,13 @@ struct Engine {
                                     // the fast path's right-hand side of the NEXT QP (fast_rhs): the new plant state is in sm.logv[24..35]
                                     // (the plant lane of the linearisation phase above)
                                     const double dxq = k == 0 ? sm.logv[24 + j] - qj : 0.0, dxv = k == 0 ? sm.logv[30 + j] - vj : 0.0;
-                                    const RhsItem o = rhs_item(P, j, k < Nl, k >= 1, uj, vj, dxq, dxv, rec[O_GQ + j], rec[O_GQ + 6 + j],
-                                                               rec[O_GQ + 12 + j], rec[O_GQ + 18 + j], rec[O_GQ + 24 + j], rec[O_Y], rec[O_Y + 1],
-                                                               rec[O_Y + 2], rec[O_Y + 3], rec[O_Y + 4], rec[O_GV + j], rec[O_BD + j],
-                                                               rec[O_BD + 6 + j]);
+                                    RhsItem o = rhs_item(P, j, k < Nl, k >= 1, uj, vj, dxq, dxv, rec[O_GQ + j], rec[O_GQ + 6 + j],
+                                                         rec[O_GQ + 12 + j], rec[O_GQ + 18 + j], rec[O_GQ + 24 + j], rec[O_Y], rec[O_Y + 1],
+                                                         rec[O_Y + 2], rec[O_Y + 3], rec[O_Y + 4], rec[O_GV + j], rec[O_BD + j],
+                                                         rec[O_BD + 6 + j]);
+                                    if constexpr (TERM) {
+                                        if (k == Nl) { o.gtq = tgq; o.gtv = tgv; }
+                                    }
                                     if (wide) {
                                         rec[O_GT + j] = o.gtu; rec[O_GT + 6 + j] = o.gtq; rec[O_GT + 12 + j] = o.gtv;
                                         rec[O_GAM + j] = 0.0; rec[O_GAM + 6 + j] = 0.0;
@@ -1029,6 +1061,15 @@ struct Engine {
                                 rgv += (k < Nl ? dt : 1.0) * lm * dvv;
                                 rgv -= v[r][6];
                             }
+                            double tgq = 0.0;
+                            if constexpr (TERM) {
+                                // stage N: rows q_j, v_j of g_N + P dx_N = P (X_N + dx_N - x_e)
+                                if (k == Nl) {
+                                    double tgv;
+                                    nlp::term_grad(term_rec(), j, q[r][0] + q[r][1], vj, tgq, tgv);
+                                    rgv += tgv;
+                                }
+                            }
                             gst(g3 + O_RG + 12 + j, rgv); gst(g2 + O_GT + 12 + j, rgv);
                             // q_j (stat_cls<1>); pi_k[j] is v[r][4]
                             const double dq = q[r][1];
@@ -1042,6 +1083,7 @@ struct Engine {
                                 }
                                 rg += (k < Nl ? dt : 1.0) * lm * dq;
                                 rg -= q[r][8];
+                                if constexpr (TERM) rg += tgq;
                             }
                             const double gt = bounds(lane, k, 6 + j, q[r][0], dq, q[r][9], q[r][10], q[r][11], q[r][12], rg);
                             gst(g3 + O_RG + 6 + j, rg); gst(g2 + O_GT + 6 + j, gt);
@@ -1142,6 +1184,32 @@ struct Engine {
             f.mqq = f.mqv = f.mvq = f.mvv = 0.0;
             f.qqq = f.qqv = f.qvq = f.qvv = 0.0;
         });
+        // TERM: what the terminal stage takes of the terminal weight waits in registers from here on (the loads run under the first
+        // chunk's fetch, not at the head of the recursion): the lane's diagonal block (pqq, pqv, pvv of joint a = b, 0 off the
+        // diagonal) and its entries e = lane, lane + WAVE of the packed P_N record
+        typename Ex::template PerLane<double> tqq, tqv, tvv, tpm[(NPM + WAVE - 1) / WAVE];
+        if constexpr (TERM) {
+            const TermRec tm = term_rec();
+            ex.seq([&](int lane) {
+                const int a = lane < 36 ? lane / 6 : 0, b = lane < 36 ? lane % 6 : 0;
+                const bool dg = lane < 36 && a == b;
+                tqq.at(lane) = dg ? tm[nlp::TM_QQ + a] : 0.0;
+                tqv.at(lane) = dg ? tm[nlp::TM_QV + a] : 0.0;
+                tvv.at(lane) = dg ? tm[nlp::TM_VV + a] : 0.0;
+#pragma unroll
+                for (int r = 0; r < (NPM + WAVE - 1) / WAVE; r++) {
+                    const int e = lane + r * WAVE;
+                    double v = 0.0;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) {
+                        v = e == tri(i, i) ? nlp::term_hess(tm, i, i) : v;
+                        v = e == tri(i, 6 + i) ? nlp::term_hess(tm, i, 6 + i) : v;
+                        v = e == tri(6 + i, 6 + i) ? nlp::term_hess(tm, 6 + i, 6 + i) : v;
+                    }
+                    tpm[r].at(lane) = v;
+                }
+            });
+        }
         const double dw0 = P.dt * P.w_task[0], dw1 = P.dt * P.w_task[1], dw2 = P.dt * P.w_task[2], dw3 = P.dt * P.w_task[3],
                      dw4 = P.dt * P.w_task[4];
         // R~, S~ of stage `kd` from the lane's block of P_{kd+1}; also the A'MA block for stage kd
@@ -1283,20 +1351,36 @@ struct Engine {
                 const double *gam = ric + 36;
                 if (k == Nl) {
                     // terminal stage: no cost, no bounds -> P_N = lm I (0 without levenberg_marquardt) ; R~, S~ of stage N-1
+                    // (TERM: P_N = lm I + P, the joint blocks of the terminal weight: the recursion starts from them)
                     ex.seq([&](int lane) {
                         const double lmN = ex.smem().P.lm;
                         // every entry written once, by one lane: a diagonal write after a zero fill by OTHER lanes holds only while
                         // the wavefront runs in lockstep (the host emulation runs the lanes one after the other and lost the diagonal)
+                        if constexpr (TERM) {
+#pragma unroll
+                            for (int r = 0; r < (NPM + WAVE - 1) / WAVE; r++) {
+                                const int e = lane + r * WAVE;
+                                double v = 0.0;
+#pragma unroll
+                                for (int i = 0; i < NX; i++) v = e == tri(i, i) ? lmN : v;
+                                if (e < NPM) fac[O_PM + e] = v + tpm[r].at(lane);
+                            }
+                        } else {
                         for (int e = lane; e < NPM; e += WAVE) {
                             double v = 0.0;
 #pragma unroll
                             for (int i = 0; i < NX; i++) v = e == tri(i, i) ? lmN : v;
                             fac[O_PM + e] = v;
                         }
+                        }
                         if (lane < 36) {
                             FactLane &f = fl.at(lane);
                             f.mqv = f.mvq = 0.0;
                             f.mqq = f.mvv = f.a == f.b ? lmN : 0.0;
+                            if constexpr (TERM) {
+                                f.mqv = f.mvq = tqv.at(lane);
+                                f.mqq += tqq.at(lane); f.mvv += tvv.at(lane);
+                            }
                             next_stage(lane, f, ricd[36 + f.a], sb);
                         }
                         if (lane == 0) ex.post(&sm.prog, 0);
@@ -2656,8 +2740,12 @@ struct Engine {
                     if (e < items) {
                         const int k = e / 6, j = e - k * 6;
                         const double dxq = k == 0 ? sm.xhat[j] - v[r][2] : 0.0, dxv = k == 0 ? sm.xhat[6 + j] - v[r][1] : 0.0;
-                        const RhsItem o = rhs_item(P, j, k < Nl, k >= 1, v[r][0], v[r][1], dxq, dxv, v[r][4], v[r][5], v[r][6], v[r][7], v[r][8],
-                                                   v[r][9], v[r][10], v[r][11], v[r][12], v[r][13], v[r][3], v[r][14], v[r][15]);
+                        RhsItem o = rhs_item(P, j, k < Nl, k >= 1, v[r][0], v[r][1], dxq, dxv, v[r][4], v[r][5], v[r][6], v[r][7], v[r][8],
+                                             v[r][9], v[r][10], v[r][11], v[r][12], v[r][13], v[r][3], v[r][14], v[r][15]);
+                        if constexpr (TERM) {
+                            // stage N (>= 1: no feedback step there): g_N = P (X_N - x_e)
+                            if (k == Nl) nlp::term_grad(term_rec(), j, v[r][2], v[r][1], o.gtq, o.gtv);
+                        }
                         double *g2 = G2 + (size_t)k * W2;
                         gst(g2 + O_GT + j, o.gtu); gst(g2 + O_GT + 6 + j, o.gtq); gst(g2 + O_GT + 12 + j, o.gtv);
                         gst(g2 + O_GAM + j, 0.0); gst(g2 + O_GAM + 6 + j, 0.0);
@@ -3252,14 +3340,18 @@ struct Engine {
     // one run.  Stage 0 enters through Nu_0 = -R~_0^-1 alone (M_0 = 0): rows 0 and 1, nothing for the task rows.
     struct NoDw {};
     static constexpr int SWX = 36, SWR = 3 * 36;                       // [du 6 | dq 6 | dv 6 | qdot 6 | U 6 | r 5 | pad]; the partial sums
+    // TERM: also dxe [6][12] = d u0 / d x_e (or null), the terminal reference: the recursion's last advance leaves M_N, and stage N's
+    // gradient falls by P e_i when x_e,i grows (mpc_nlp.h term_sens) -- two products per entry, by the lanes that hold M_N.
     template <bool SW = false>
-    MPC_PASS void sens_pass(double *dx, double *dy, int *valid, bool exact, typename std::conditional<SW, double *, NoDw>::type dw_ = {})
+    MPC_PASS void sens_pass(double *dx, double *dy, int *valid, bool exact, typename std::conditional<SW, double *, NoDw>::type dw_ = {},
+                            typename std::conditional<TERM, double *, NoDw>::type dxe_ = {})
     {
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
         const int Nl = ex.uni(sm.n_hor), NM = ex.uni(N);
-        double *dw = nullptr;
+        double *dw = nullptr, *dxe = nullptr;
         if constexpr (SW) dw = dw_;
+        if constexpr (TERM) dxe = dxe_;
         if (!exact) {
             ex.par([&](int lane) {
                 const double nan = __builtin_nan("");
@@ -3267,6 +3359,9 @@ struct Engine {
                 if (dy) for (int e = lane; e < NM * NTASK * NU; e += NT) gst(dy + e, nan);
                 if constexpr (SW) {
                     if (dw) for (int e = lane; e < NWEIGHT * NU; e += NT) gst(dw + e, nan);
+                }
+                if constexpr (TERM) {
+                    if (dxe) for (int e = lane; e < NU * NX; e += NT) gst(dxe + e, nan);
                 }
                 if (lane == 0) *(MPC_GLOBAL int *)valid = 0;
             });
@@ -3323,7 +3418,7 @@ struct Engine {
             }
             if (lane == 0) *(MPC_GLOBAL int *)valid = 1;
         });
-        if (!dy && !(SW && dw)) return;
+        if (!dy && !(SW && dw) && !(TERM && dxe)) return;
         int cur = 0;
         for (int k0 = 1; k0 < Nl; k0 += CH) {
             const int n = imin(CH, Nl - k0);
@@ -3375,9 +3470,24 @@ struct Engine {
                 cur ^= 1;
             }
             ex.barrier();
-            if (!SW || dy) ex.par([&](int lane) {
+            if ((!SW && !TERM) || dy) ex.par([&](int lane) {
                 for (int e = lane; e < n * WO; e += NT) gst(dy + (size_t)k0 * WO + e, ob[e]);
             });
+        }
+        if constexpr (TERM) {
+            // M_N is where the last advance (or, with a horizon of 1, the start) left it: lane (j, c) reads back its own two entries
+            if (dxe) {
+                const TermRec tm = term_rec();
+                const double *m = Mt + cur * 72;
+                ex.seq([&](int lane) {
+                    if (lane < 36) {
+                        const int j = lane / 6, cc = lane - j * 6;
+                        double dq, dv;
+                        nlp::term_sens(tm, j, m[cc * 12 + j], m[cc * 12 + 6 + j], dq, dv);
+                        gst(dxe + cc * 12 + j, dq); gst(dxe + cc * 12 + 6 + j, dv);
+                    }
+                });
+            }
         }
         if constexpr (SW) {
             // the six addends of rows 0 and 1 meet through LDS; 42 values, one run
@@ -3409,11 +3519,15 @@ struct Engine {
     // moves its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
     // SENS (the kernels of mpcb_step_sens, SQP_RTI): the sensitivities of u0 leave through io.du0_dx / du0_dyref / sens_valid (sens_pass).
     // SENSW (the kernels of mpcb_step_sens_w; with SENS): and its sensitivity to the cost weights through io.du0_dw.
+    // TERM (the engine's flag; the kernels of mpcb_step_term): io.term holds this simulation's terminal cost, and with SENS the
+    // sensitivity of u0 to its reference leaves through io.du0_dxe.  Not combined with SENSW.
     template <bool WARM = false, bool SENS = false, bool SENSW = false>
     MPC_HD void control_step(const StepIO &io, int inst, bool reset)
     {
+        static_assert(!(TERM && SENSW), "the weight sensitivity is not offered with a terminal cost");
         Smem &sm = ex.smem();
         Ws &w = c.w;
+        if constexpr (TERM) term = io.term + (size_t)inst * NTERM;
         bool lin_valid = false;
         int mode = WARM_CARRY;
         if constexpr (WARM) {
@@ -3446,6 +3560,11 @@ struct Engine {
             status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search, [&](bool exact) {
                 sens_pass<true>(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * N * NTASK * NU : nullptr,
                                 io.sens_valid + inst, exact, io.du0_dw ? io.du0_dw + (size_t)inst * NWEIGHT * NU : nullptr);
+            });
+        } else if constexpr (SENS && TERM) {
+            status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search, [&](bool exact) {
+                sens_pass<false>(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * N * NTASK * NU : nullptr,
+                                 io.sens_valid + inst, exact, {}, io.du0_dxe ? io.du0_dxe + (size_t)inst * NU * NX : nullptr);
             });
         } else if constexpr (SENS) {
             status = nlp_step<false>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search, [&](bool exact) {

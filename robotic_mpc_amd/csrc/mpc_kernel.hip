@@ -51,6 +51,18 @@ void launch_step_sensw(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStr
                        const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
 void launch_stream_step_sensw(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
                               size_t ws_stride, const StepIO &io, int reset);
+// ... those of the step with a joint-wise terminal cost (mpcb_step_term), without and with the sensitivity pass: mpc_step_term.hip,
+// mpc_step_term_sens.hip, mpc_stream_step_term.hip, mpc_stream_step_term_sens.hip
+const void *step_term_kernel(int waves_per_sim, int wpe);
+void launch_step_term(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                      const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
+const void *step_term_sens_kernel(int waves_per_sim, int wpe);
+void launch_step_term_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                           const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
+void launch_stream_step_term(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                             size_t ws_stride, const StepIO &io, int reset);
+void launch_stream_step_term_sens(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                                  size_t ws_stride, const StepIO &io, int reset);
 // ... and those that also write the sensitivities of u0 (mpcb_step_sens): mpc_step_sens.hip, mpc_stream_step_sens.hip
 const void *step_sens_kernel(int waves_per_sim, int wpe);
 void launch_step_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
@@ -527,11 +539,14 @@ static const void *latency_kernel(const mpcb_handle *h)
 
 // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
 // handle can ask for, right before the launch
-// (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens, 3 of mpcb_step_sens_w)
+// (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens, 3 of mpcb_step_sens_w, 4 / 5 of
+// mpcb_step_term without / with sens)
 static int raise_lds_limit(mpcb_handle *h, int step = 0)
 {
     static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(step == 3 ? step_sensw_kernel(h->waves_per_sim, h->wpe)
+    HIPCHK(h, hipFuncSetAttribute(step == 5 ? step_term_sens_kernel(h->waves_per_sim, h->wpe)
+                                  : step == 4 ? step_term_kernel(h->waves_per_sim, h->wpe)
+                                  : step == 3 ? step_sensw_kernel(h->waves_per_sim, h->wpe)
                                   : step == 2 ? step_sens_kernel(h->waves_per_sim, h->wpe)
                                   : step == 1 ? step_warm_kernel(h->waves_per_sim, h->wpe) : latency_kernel(h),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
@@ -670,9 +685,26 @@ int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
     return mpcb_step_sens_w(h, io, yref, ref_changed, warm, reset, sens, nullptr, stream);
 }
 
+static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                     const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream);
+
 // (du0_dw == NULL: all of the above; otherwise the kernels that also form the weight sensitivity, supersets of the sens ones)
 int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                      const mpcb_step_sens_out *sens, double *du0_dw, void *stream)
+{
+    return step_impl(h, io, yref, ref_changed, warm, reset, sens, du0_dw, nullptr, 0, nullptr, stream);
+}
+
+// (term == NULL: mpcb_step_sens, after term_changed from a fresh linearisation; otherwise the kernels built with the terminal cost --
+// supersets of the warm-start ones, and with sens of the sens ones)
+int mpcb_step_term(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const mpcb_step_sens_out *sens, const double *term, int term_changed, double *du0_dxe, void *stream)
+{
+    return step_impl(h, io, yref, ref_changed, warm, reset, sens, nullptr, term, term_changed, du0_dxe, stream);
+}
+
+static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                     const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
@@ -686,22 +718,29 @@ int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref,
         if (!sens->du0_dx || !sens->valid) return fail(h, MPCB_EINVAL, "mpcb_step_sens: du0_dx and valid must be provided");
     }
     if (du0_dw && !sens) return fail(h, MPCB_EINVAL, "mpcb_step_sens_w: du0_dw needs sens (du0_dx and valid)");
-    const int variant = du0_dw ? 3 : sens ? 2 : warm ? 1 : 0;
+    if (term && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_step_term: the terminal cost is offered with SQP_RTI; this controller runs full SQP");
+    if (du0_dxe && (!sens || !term)) return fail(h, MPCB_EINVAL, "mpcb_step_term: du0_dxe needs sens (du0_dx and valid) and term");
+    const int variant = term ? (sens ? 5 : 4) : du0_dw ? 3 : sens ? 2 : warm ? 1 : 0;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     StepIO sio;
     std::memcpy(&sio, io, sizeof(mpcb_step_io));
     sio.yref = yref;
-    // (new weights make the carried linearisation stale exactly as a new reference does)
-    sio.ref_changed = (ref_changed != 0 || h->weights_changed) ? 1 : 0;
+    // (new weights, or a new terminal cost, make the carried linearisation stale exactly as a new reference does)
+    sio.ref_changed = (ref_changed != 0 || term_changed != 0 || h->weights_changed) ? 1 : 0;
     sio.warm = warm;
     sio.du0_dw = du0_dw;
+    sio.term = term;
+    sio.du0_dxe = du0_dxe;
     if (sens) { sio.du0_dx = sens->du0_dx; sio.du0_dyref = sens->du0_dyref; sio.sens_valid = sens->valid; }
     const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
     if (h->engine == MPCB_ENGINE_STREAM) {
         // throughput engine: one wavefront per simulation, static LDS only, no work queue
         HIPCHK(h, hipEventRecord(h->ev0, s));
-        if (variant == 3) launch_stream_step_sensw(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        if (variant == 5) launch_stream_step_term_sens(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        else if (variant == 4) launch_stream_step_term(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
+        else if (variant == 3) launch_stream_step_sensw(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         else if (variant == 2) launch_stream_step_sens(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         else if (variant == 1) launch_stream_step_warm(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
         else launch_stream_step(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
@@ -717,7 +756,13 @@ int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref,
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
     if (int rc = raise_lds_limit(h, variant)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
-    if (variant == 3)
+    if (variant == 5)
+        launch_step_term_sens(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride,
+                              sio, rs, h->pool_doubles);
+    else if (variant == 4)
+        launch_step_term(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
+                         rs, h->pool_doubles);
+    else if (variant == 3)
         launch_step_sensw(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
                           rs, h->pool_doubles);
     else if (variant == 2)

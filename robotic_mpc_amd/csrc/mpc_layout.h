@@ -119,6 +119,10 @@ MPC_HD void put_weights(InstParams &P, const double *w)
     for (int i = 0; i < NTASK; i++) P.w_task[i] = w[2 + i];
 }
 
+// The joint-wise terminal cost of a controller step (mpcb_step_term): per simulation the 2x2 blocks (pqq_j, pqv_j, pvv_j) of the six
+// joints and the terminal reference x_e = [q_e; qdot_e] -- NTERM doubles, in this order (formulas: mpc_nlp.h term_*).
+constexpr int NTERM = 30;
+
 // Batch-uniform problem description (== mpcb_problem).
 struct Problem {
     int batch;
@@ -152,7 +156,8 @@ struct Outputs {
 // Device pointers of one controller step (mpcb_step_io, then the task reference of mpcb_step_ref): the caller's feedback states in,
 // solver.get(0,'u') and the step's statistics out, batch-major.  x_pred / u_pred may be null (not written).  The members past
 // u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged", one that stops
-// at ref_changed "every simulation carries its solver memory", one that stops at warm "no sensitivities", one that stops at sens_valid "none to the weights".
+// at ref_changed "every simulation carries its solver memory", one that stops at warm "no sensitivities", one that stops at sens_valid "none to the weights",
+// one that stops at du0_dw "no terminal cost".
 struct StepIO {
     const double *xhat;  // [batch][12]
     double *u0;          // [batch][6]
@@ -173,6 +178,9 @@ struct StepIO {
     int *sens_valid = nullptr;      // [batch] 1: exact sensitivities written, 0: NaN
     // mpcb_step_sens_w: the sensitivity of u0 to the seven cost weights, read by the sens_w kernels only
     double *du0_dw = nullptr;       // [batch][NWEIGHT][6] d u0 / d weight_p
+    // mpcb_step_term: the joint-wise terminal cost and the sensitivity of u0 to its reference, read by the term kernels only
+    const double *term = nullptr;   // [batch][NTERM] pqq 6 | pqv 6 | pvv 6 | x_e 12 (mpc_nlp.h term_*)
+    double *du0_dxe = nullptr;      // [batch][6][12] d u0 / d x_e, or null (not written)
 };
 
 // How a simulation's solver memory enters a controller step (MPCB_WARM_*); any other value is WARM_CARRY.

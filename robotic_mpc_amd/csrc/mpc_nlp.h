@@ -229,5 +229,40 @@ MPC_HD double sensw_rho(int i, const GG &G, const RR &r, const DQ &dq, const DV 
     return r[i] + (i == 4 ? s + sv : s);
 }
 
+// ---- joint-wise terminal cost (mpcb_step_term) -------------------------------------------------------------------------------------
+// l_N(x) = 1/2 sum_j [q_j - q_e,j, v_j - v_e,j] [[pqq_j, pqv_j], [pqv_j, pvv_j]] [.]', not scaled by dt.  T: the simulation's record
+// [pqq 6 | pqv 6 | pvv 6 | x_e 12] (mpc_layout.h NTERM), wavefront-uniform and read where it is used.  In the Gauss-Newton QP at the
+// iterate: H_N = lm I + P, g_N = P (X_N - x_e); the cost and the stationarity rows of stage N take the same two functions.
+constexpr int TM_QQ = 0, TM_QV = 6, TM_VV = 12, TM_XE = 18;
+// rows q_j and qdot_j of P (x - x_e) at the terminal state's (q, v) of joint j
+template <class T>
+MPC_HD void term_grad(const T &t, int j, double q, double v, double &gq, double &gv)
+{
+    const double eq = q - t[TM_XE + j], ev = v - t[TM_XE + 6 + j];
+    gq = t[TM_QQ + j] * eq + t[TM_QV + j] * ev;
+    gv = t[TM_QV + j] * eq + t[TM_VV + j] * ev;
+}
+// joint j's term of l_N
+template <class T>
+MPC_HD double term_cost(const T &t, int j, double q, double v)
+{
+    const double eq = q - t[TM_XE + j], ev = v - t[TM_XE + 6 + j];
+    return 0.5 * (eq * (t[TM_QQ + j] * eq + t[TM_QV + j] * ev) + ev * (t[TM_QV + j] * eq + t[TM_VV + j] * ev));
+}
+// entry (i, j), i <= j, of the 12x12 terminal weight P (states ordered [q; qdot]): six 2x2 blocks, zero elsewhere
+template <class T>
+MPC_HD double term_hess(const T &t, int i, int j)
+{
+    if (i == j) return i < 6 ? t[TM_QQ + i] : t[TM_VV + i - 6];
+    return (i < 6 && j == i + 6) ? t[TM_QV + i] : 0.0;
+}
+// (d u0 / d x_e)(c, j) and (c, 6 + j) = -(M_N' P) there: g_N falls by P e_i when x_e,i grows.  mq = M_N[j][c], mv = M_N[6 + j][c]
+template <class T>
+MPC_HD void term_sens(const T &t, int j, double mq, double mv, double &dq, double &dv)
+{
+    dq = -(mq * t[TM_QQ + j] + mv * t[TM_QV + j]);
+    dv = -(mq * t[TM_QV + j] + mv * t[TM_VV + j]);
+}
+
 }  // namespace nlp
 }  // namespace mpcb

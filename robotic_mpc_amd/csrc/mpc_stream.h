@@ -330,6 +330,27 @@ SE_DEV void sweep(Bundle<NI, BI> &bin, int N, int lane, F &&body)
     }
 }
 
+// TERM (the kernels of mpcb_step_term only): the controller step with the joint-wise terminal cost of mpc_nlp.h term_*.  A compile-time
+// flag of control_step and of every pass it reaches that sees stage N's cost; this simulation's record [pqq 6 | pqv 6 | pvv 6 | x_e 12]
+// travels with it as an argument -- an empty struct, no register, in every other kernel.  The record is wavefront-uniform and needed
+// at stage N only: the passes read it from the step's device buffer where they use it (TermRec), never through LDS.
+template <bool TERM>
+struct TermArg {};
+template <>
+struct TermArg<true> {
+    const double *p;
+};
+struct TermRec {
+    const MPC_GLOBAL double *p;
+    SE_DEV double operator[](int i) const { return p[i]; }
+};
+template <bool TERM>
+SE_DEV TermRec term_rec(TermArg<TERM> t)
+{
+    if constexpr (TERM) return TermRec{(const MPC_GLOBAL double *)uni_ref(TaskRef{t.p}).y};
+    else return TermRec{nullptr};
+}
+
 // Stationarity element of class CLS (0: u_j, 1: q_j, 2: v_j) -- mpc_core.h Engine::stat_cls with the records in LDS.
 // r1: G1 row of stage k, r2: [R..GV] of stage k, pk / pm: pi_k / pi_{k-1}.
 template <int CLS>
@@ -381,8 +402,8 @@ struct IpmNorms {
 // multiplier step stored with stage k+1; pi_{k-1} travels in LDS from the previous iteration.
 //   in  : G1 row | G3 [DW..DT] | G2 [R..GV]            (234 doubles)
 //   out : G1 [QW..QT] | G2 [R,Y] | G2 [GAM|GT|RB] | G3 [RG|RD|RM]   (196 doubles)
-template <int MODE>
-SE_PASS IpmNorms residual_pass(double a)
+template <int MODE, bool TERM = false>
+SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {})
 {
     static_assert(MODE == 0 || MODE == 1, "warm start or Newton step");
     SSmem &sm = g_ssm;
@@ -545,6 +566,14 @@ SE_PASS IpmNorms residual_pass(double a)
             pin(l_lo); pin(t_lo); pin(l_hi); pin(t_hi);
             pin(g0); pin(g1); pin(g2); pin(g3); pin(g4); pin(gv); pin(y0); pin(y1); pin(y2); pin(y3); pin(y4);
             pin(q_h); pin(q_n); pin(c1); pin(c2);
+            double t_add = 0.0;      // TERM, stage N: the row of g_N + P dx_N = P (X_N + dx_N - x_e) this lane's stationarity row takes
+            if constexpr (TERM) {
+                if (k == N && lane < NW && cls >= 1) {
+                    double tgq, tgv;
+                    nlp::term_grad(term_rec(tm), cj, cur[O_X + cj] + cur[O_QW + 6 + cj], cur[O_X + 6 + cj] + cur[O_QW + 12 + cj], tgq, tgv);
+                    t_add = cls == 1 ? tgq : tgv;
+                }
+            }
             if (lane < NW) {
                 // stationarity of the QP at w + dw (mpc_core.h stat_cls with `with_delta`), same operation order
                 double rg = 0.0;
@@ -564,6 +593,7 @@ SE_PASS IpmNorms residual_pass(double a)
                         }
                         rg += (k < N ? k_dt : 1.0) * k_lm * q_g;
                         rg -= q_h;
+                        if constexpr (TERM) rg += t_add;
                     }
                 } else {
                     if (k > 0) {
@@ -574,6 +604,7 @@ SE_PASS IpmNorms residual_pass(double a)
                         }
                         rg += (k < N ? k_dt : 1.0) * k_lm * q_d;
                         rg -= q_h;
+                        if constexpr (TERM) rg += t_add;
                     }
                 }
                 double gt = rg;
@@ -640,7 +671,8 @@ SE_PASS IpmNorms residual_pass(double a)
 // three phases U | Y | S,D and the same arithmetic per element).  ~17 batches of loads per pass instead of 101 stages of chain;
 // while a batch is in flight the SIMD's other simulation runs.  y of every stage waits in the (idle) ring between Y and S.
 // (residual_items_ok: beside RING_DOUBLES above)
-SE_PASS IpmNorms residual_items(double a)
+template <bool TERM = false>
+SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {})
 {
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
@@ -846,6 +878,15 @@ SE_PASS IpmNorms residual_items(double a)
                         rgv += (k < N ? dt : 1.0) * lm * dvv;
                         rgv -= v[r][6];
                     }
+                    double tgq = 0.0;
+                    if constexpr (TERM) {
+                        // stage N: rows q_j, v_j of g_N + P dx_N = P (X_N + dx_N - x_e)
+                        if (k == N) {
+                            double tgv;
+                            nlp::term_grad(term_rec(tm), j, q[r][0] + q[r][1], vj, tgq, tgv);
+                            rgv += tgv;
+                        }
+                    }
                     gst(g3 + O_RG + 12, rgv); gst(g2 + O_GT + 12, rgv);
                     // q_j; pi_k[j] is v[r][4]
                     const double dq = q[r][1];
@@ -859,6 +900,7 @@ SE_PASS IpmNorms residual_items(double a)
                         }
                         rg += (k < N ? dt : 1.0) * lm * dq;
                         rg -= q[r][8];
+                        if constexpr (TERM) rg += tgq;
                     }
                     const double gt = bounds(k, 6 + j, q[r][0], dq, q[r][9], q[r][10], q[r][11], q[r][12], rg);
                     gst(g3 + O_RG + 6, rg); gst(g2 + O_GT + 6, gt);
@@ -904,8 +946,10 @@ SE_PASS IpmNorms residual_items(double a)
 // SQPM (full SQP): the norms use the blended NLP multipliers of G5 (NPI | NLAM | NT: the same relative layout as QPI | QLAM | QT of G1).
 // `slot` (SQP_RTI): where the QP iterate, hence its multipliers, sits in the stage record -- 0: G1 [QPI | QLAM | QT], 1: G3 [DPI | DLAM | DT]
 // (an accepted fast-path candidate that has become the iterate by a flip of the index, fast_commit / ipm_solve).
-template <bool NORMS, bool RHS, bool SQPM = false>
-SE_PASS void rti_items(int xsel, double *out5, int slot = 0)
+// TERM: stage N's joint items take the terminal cost -- its term of the cost, P (X_N - x_e) in the stationarity rows and in the
+// right-hand side's gt (mpc_nlp.h term_*).
+template <bool NORMS, bool RHS, bool SQPM = false, bool TERM = false>
+SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = {})
 {
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
@@ -963,6 +1007,14 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0)
                 double s_ = 0.0;
 #pragma unroll
                 for (int i = 0; i < NTASK; i++) s_ += g[r][1 + i] * g[r][6 + i];
+                double tgq = 0.0, tgv = 0.0;
+                if constexpr (TERM) {
+                    if (k == N) {
+                        const TermRec tr = term_rec(tm);
+                        nlp::term_grad(tr, j, qj, vj, tgq, tgv);
+                        if (NORMS) csum += nlp::term_cost(tr, j, qj, vj);
+                    }
+                }
                 double bdq, bdv;
                 MPC_GLOBAL double *g2 = rec(k, j) + C2;
                 if (NORMS) {
@@ -1002,6 +1054,7 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0)
                     if (k > 0) {
                         if (st) rq = dt * s_ + m[r][0];
                         rq -= m[r][2];
+                        if constexpr (TERM) rq += tgq;
                     }
                     bound(6 + j, k >= 1 && st, qj, m[r][8], m[r][9], m[r][10], m[r][11], rq);
                     double rv = 0.0;
@@ -1011,6 +1064,7 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0)
                             rv += P.a12[j] * m[r][0] + P.a22[j] * m[r][1];
                         }
                         rv -= m[r][3];
+                        if constexpr (TERM) rv += tgv;
                     }
                     if (k == 0) {
                         rq = 0.0; rv = 0.0;                                               // x_0 is eliminated (lbx_0 = ubx_0)
@@ -1024,8 +1078,11 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0)
                     const double dxq = k == 0 ? xh_q - qj : 0.0, dxv = k == 0 ? xh_v - vj : 0.0;
                     const double vjn = vj + dxv;
                     const double gtu = st ? dt * (2.0 * P.w_u * uj + c2 * (uj - vjn)) : 0.0;
-                    const double gtq = st && k >= 1 ? dt * s_ : 0.0;
-                    const double gtv = st && k >= 1 ? dt * (g[r][0] * g[r][10] + c2 * (vjn - uj)) : 0.0;
+                    double gtq = st && k >= 1 ? dt * s_ : 0.0;
+                    double gtv = st && k >= 1 ? dt * (g[r][0] * g[r][10] + c2 * (vjn - uj)) : 0.0;
+                    if constexpr (TERM) {
+                        if (k == N) { gtq = tgq; gtv = tgv; }       // stage N (>= 1: no feedback step there): g_N = P (X_N - x_e)
+                    }
                     const double rbq = st ? (dxq + P.a12[j] * dxv) + bdq : 0.0;
                     const double rbv = st ? P.a22[j] * dxv + bdv : 0.0;
                     gst(g2 + O_GT, gtu); gst(g2 + O_GT + 6, gtq); gst(g2 + O_GT + 12, gtv);
@@ -1079,8 +1136,9 @@ struct FactLane {
 };
 
 // FASTF (fast path): the record goes out without its tail [w | R~^-1] -- only the corrector reads that (48 of 232 scalars).
-template <class FT, bool FASTF = false>
-SE_PASS void fact_pass()
+// TERM: the recursion starts from P_N = lm I + P, the joint blocks of the terminal weight (mpc_nlp.h term_hess).
+template <class FT, bool FASTF = false, bool TERM = false>
+SE_PASS void fact_pass(TermArg<TERM> tm = {})
 {
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
@@ -1151,12 +1209,43 @@ SE_PASS void fact_pass()
         const double *gam = ric + 36, *gt = ric + 48, *rbv = ric + 66;
         if (k == N) {
             // terminal stage: no cost, no bounds -> P_N = lm I ; p_N = gt_x ; R~, S~ of stage N-1
+            if constexpr (TERM) {
+                // every entry of the P_N record written once, by one lane, with its value; the rest of the row zero
+                const TermRec tr = term_rec(tm);
+                double hqq[6], hqv[6], hvv[6];
+#pragma unroll
+                for (int i = 0; i < 6; i++) { hqq[i] = nlp::term_hess(tr, i, i); hqv[i] = nlp::term_hess(tr, i, 6 + i); hvv[i] = nlp::term_hess(tr, 6 + i, 6 + i); }
+                for (int e = lane; e < SW4; e += WAVE) {
+                    const int q = e - SPM;
+                    FT v = (FT)0;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) {
+                        v = q == tri(i, i) ? lmN + (FT)hqq[i] : v;
+                        v = q == tri(i, 6 + i) ? (FT)hqv[i] : v;
+                        v = q == tri(6 + i, 6 + i) ? lmN + (FT)hvv[i] : v;
+                    }
+                    fac[e] = v;
+                }
+                fence();
+                if (lane < 36) {
+                    FT bqq = (FT)0, bqv = (FT)0, bvv = (FT)0;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) {
+                        const bool on = f.a == i && f.b == i;
+                        bqq = on ? lmN + (FT)hqq[i] : bqq; bqv = on ? (FT)hqv[i] : bqv; bvv = on ? lmN + (FT)hvv[i] : bvv;
+                    }
+                    f.mqq = bqq; f.mqv = f.mvq = bqv; f.mvv = bvv;
+                }
+            } else {
             for (int e = lane; e < SW4; e += WAVE) fac[e] = (FT)0;
             fence();
             if (lane < NX) fac[SPM + tri(lane, lane)] = lmN;
+            }
             if (lane < 36) {
+                if constexpr (!TERM) {
                 f.mqv = f.mvq = (FT)0;
                 f.mqq = f.mvv = f.a == f.b ? lmN : (FT)0;
+                }
                 if (k >= 1) next_stage((FT)ricd[36 + f.a], sb);
             } else if (lane >= 40 && lane < 52) {
                 pr = (FT)gt[6 + jv];
@@ -1665,8 +1754,9 @@ SE_PASS void fast_commit(bool embed_x0)
 // `fast_accepted` (out, optional): whether this QP is the accepted fast-path candidate (mpc_step's hook asks).
 // FULLFACT (the kernel of mpcb_step_sens): the fast path's factor records go out whole, tail [w | R~^-1] included -- sens_pass reads
 // R~_0^-1; the same factorisation, 48 more scalars stored per stage.
-template <class FT, bool FULLFACT = false>
-SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_prev = nullptr, int *cur = nullptr, bool *fast_accepted = nullptr)
+template <class FT, bool FULLFACT = false, bool TERM = false>
+SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_prev = nullptr, int *cur = nullptr, bool *fast_accepted = nullptr,
+                     TermArg<TERM> tm = {})
 {
     SSmem &sm = g_ssm;
     const double tol = sm.P.qp_tol;
@@ -1677,11 +1767,11 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         else {
             tried = 1;
             SPROF_T0(t_r);
-            if (nlp_prev) rti_items<true, true>(1, nlp_prev, slot); else rti_items<false, true>(0, nullptr);
+            if (nlp_prev) rti_items<true, true, false, TERM>(1, nlp_prev, slot, tm); else rti_items<false, true, false, TERM>(0, nullptr, 0, tm);
             SPROF_ADD(10, t_r);
             nlp_prev = nullptr;                                    // the previous step's residuals are done, whatever happens next
             SPROF_T0(t_f);
-            fact_pass<FT, !FULLFACT>();
+            fact_pass<FT, !FULLFACT, TERM>(tm);
             SPROF_ADD(11, t_f);
             SPROF_T0(t_w);
             const double ok = unid(forward_pass<FT, false, true>(slot ^ 1).alpha);     // the candidate goes to the slot that is NOT the iterate
@@ -1704,9 +1794,9 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         }
     }
     // nlp_prev: the NLP residual / cost of the previous step's iterate is still to be evaluated -- by this QP's first pass
-    if (nlp_prev) rti_items<true, false>(1, nlp_prev, slot);     // (the same items as everywhere else: see rti_items)
+    if (nlp_prev) rti_items<true, false, false, TERM>(1, nlp_prev, slot, tm);     // (the same items as everywhere else: see rti_items)
     if (cur && slot == 1) { fast_commit(false); *cur = 0; }      // the interior-point passes expect the iterate in G1 (this also overwrites a rejected candidate there)
-    IpmNorms r = residual_pass<0>(0.0);
+    IpmNorms r = residual_pass<0, TERM>(0.0, tm);
     const double nc = unid(r.nc);
     double mu = nc > 0 ? unid(r.smu) / nc : 0.0;
     int it = 0, status = 1;
@@ -1718,7 +1808,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
 #endif
         if (stop >= 0) { status = stop; break; }
         SPROF_T0(tf);
-        fact_pass<FT>();
+        fact_pass<FT, false, TERM>(tm);
         SPROF_ADD(0, tf);
         const bool has_bounds = nc > 0;
         if (has_bounds) {
@@ -1739,7 +1829,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         }
         const double a = ipm::step_scale(alpha);
         SPROF_T0(tr);
-        r = residual_items_ok(uni(sm.n_hor)) ? residual_items(a) : residual_pass<1>(a);
+        r = residual_items_ok(uni(sm.n_hor)) ? residual_items<TERM>(a, tm) : residual_pass<1, TERM>(a, tm);
         SPROF_ADD(4, tr);
         mu = nc > 0 ? unid(r.smu) / nc : 0.0;
     }
@@ -2074,8 +2164,10 @@ struct StepStats {
 // `after_qp(exact)` (SQP_RTI; only the kernel of mpcb_step_sens brings one): called between the QP solve and the closing linearisation,
 // while G2 still holds the linearisation the QP was built from; `exact`: the QP was solved by an accepted fast-path attempt.
 struct NoHook {};
-template <class FT, class Lin, class Search, class AfterQp = NoHook>
-SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer, AfterQp &&after_qp = AfterQp{})
+// TERM (SQP_RTI): `tm` is the terminal cost of the QP, the cost and the stationarity rows (TermArg).
+template <class FT, class Lin, class Search, class AfterQp = NoHook, bool TERM = false>
+SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer, AfterQp &&after_qp = AfterQp{},
+                          TermArg<TERM> tm = {})
 {
     constexpr bool HOOK = !std::is_same<typename std::decay<AfterQp>::type, NoHook>::value;
     SSmem &sm = g_ssm;
@@ -2088,11 +2180,11 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
         if (!c.lin_valid) {
             lin(0.0, false, false, -1); __builtin_amdgcn_s_waitcnt(0); fence();
             double o5[5];
-            rti_items<true, false>(0, o5, c.cur);
+            rti_items<true, false, false, TERM>(0, o5, c.cur, tm);
             c.lin_cost = unid(o5[0]);
         }
         bool fast_accepted = false;
-        const int qs = ipm_solve<FT, HOOK>(pb.qp_iter_max, &s.qp_iter, c.fast, nlp_prev, &c.cur, HOOK ? &fast_accepted : nullptr);
+        const int qs = ipm_solve<FT, HOOK, TERM>(pb.qp_iter_max, &s.qp_iter, c.fast, nlp_prev, &c.cur, HOOK ? &fast_accepted : nullptr, tm);
         SPROF_ADD(5, tq);
         const bool ok = qs == 0 || qs == 1;
         if (!ok) s.status = 4;                                         // ACADOS_QP_FAILURE, iterate untouched
@@ -2108,7 +2200,7 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
             if (lane < NX) sm.vec[3][lane] = sm.xhat[lane];            // the x_hat this QP was solved for
         } else {
             double o5[5];
-            rti_items<true, false>(0, o5, c.cur);
+            rti_items<true, false, false, TERM>(0, o5, c.cur, tm);
             s.cost = unid(o5[0]); s.res4[0] = o5[1]; s.res4[1] = o5[2]; s.res4[2] = o5[3]; s.res4[3] = o5[4];
         }
         SPROF_ADD(9, tn);
@@ -2303,8 +2395,17 @@ struct SensWArgs<true> {
     double *dw;     // [NWEIGHT][6] of this simulation, or null
     int slot;       // 0: the QP's step is in G1 [O_QW ..), 1: in G3 [O_DW ..)
 };
-template <bool SW = false>
-SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, bool exact, SensWArgs<SW> wa = {})
+// TERM: also dxe [6][12] = d u0 / d x_e (or null), the terminal reference: the recursion's last advance leaves M_N, and stage N's
+// gradient falls by P e_i when x_e,i grows (mpc_nlp.h term_sens) -- two products per entry, by the lanes that hold M_N.
+template <bool TERM>
+struct TermSensArgs {};
+template <>
+struct TermSensArgs<true> {
+    const double *p;   // the terminal-cost record of this simulation
+    double *dxe;       // [6][12] of this simulation, or null
+};
+template <bool SW = false, bool TERM = false>
+SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, bool exact, SensWArgs<SW> wa = {}, TermSensArgs<TERM> ta = {})
 {
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
@@ -2312,8 +2413,9 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
     const int lane = threadIdx.x;
     MPC_GLOBAL double *const dx = (MPC_GLOBAL double *)dx_, *const dy = (MPC_GLOBAL double *)dy_;
     MPC_GLOBAL int *const valid = (MPC_GLOBAL int *)valid_;
-    MPC_GLOBAL double *dw = nullptr;
+    MPC_GLOBAL double *dw = nullptr, *dxe = nullptr;
     if constexpr (SW) dw = (MPC_GLOBAL double *)wa.dw;
+    if constexpr (TERM) dxe = (MPC_GLOBAL double *)ta.dxe;
     __builtin_amdgcn_s_waitcnt(0);                                // nothing of the forward sweep is still on its way into the ring
     fence();
     if (!uni(exact ? 1 : 0)) {
@@ -2322,6 +2424,9 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
         if (dy) for (int e = lane; e < NMAX * SENS_WO; e += WAVE) dy[e] = nan;
         if constexpr (SW) {
             if (dw && lane < NWEIGHT * NU) dw[lane] = nan;
+        }
+        if constexpr (TERM) {
+            if (dxe) for (int e = lane; e < NU * NX; e += WAVE) dxe[e] = nan;
         }
         if (lane == 0) *valid = 0;
         return;
@@ -2357,7 +2462,7 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
         if (lane == 0) *valid = 1;
     }
     fence();
-    if (!dy && !(SW && dw)) return;
+    if (!dy && !(SW && dw) && !(TERM && dxe)) return;
     int cur = 0;
     for (int k0 = 1; k0 < N; k0 += CH) {
         const int n = imin(CH, N - k0);
@@ -2404,8 +2509,18 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
             fence();
             cur ^= 1;
         }
-        if (!SW || dy) for (int e = lane; e < n * SENS_WO; e += WAVE) dy[(size_t)k0 * SENS_WO + e] = ob[e];
+        if ((!SW && !TERM) || dy) for (int e = lane; e < n * SENS_WO; e += WAVE) dy[(size_t)k0 * SENS_WO + e] = ob[e];
         fence();
+    }
+    if constexpr (TERM) {
+        // M_N is where the last advance (or, with a horizon of 1, the start) left it
+        if (dxe && lane < 36) {
+            const int j = lane / 6, cc = lane - j * 6;
+            const double *m = Mt + cur * 72;
+            double dq, dv;
+            nlp::term_sens(term_rec(TermArg<true>{ta.p}), j, m[cc * 12 + j], m[cc * 12 + 6 + j], dq, dv);
+            dxe[cc * 12 + j] = dq; dxe[cc * 12 + 6 + j] = dv;
+        }
     }
     if constexpr (SW) {
         // the six addends of rows 0 and 1 meet through LDS; 42 values, one run
@@ -2434,10 +2549,13 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
 // its carried memory one stage first (shift_pass); the plain instantiation is the step as it was.
 // SENS (the kernel of mpcb_step_sens, SQP_RTI): the sensitivities of u0 leave through io.du0_dx / du0_dyref / sens_valid (sens_pass).
 // SENSW (the kernel of mpcb_step_sens_w; with SENS): and its sensitivity to the cost weights through io.du0_dw.
-template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false>
+// TERM (the kernels of mpcb_step_term, SQP_RTI): io.term holds this simulation's terminal cost -- on a ragged batch it acts at the
+// simulation's own horizon end -- and with SENS the sensitivity of u0 to its reference leaves through io.du0_dxe.  Not with SENSW.
+template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false, bool TERM = false>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
+    static_assert(!(TERM && SENSW), "the weight sensitivity is not offered with a terminal cost");
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
     const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), NMAX = pb.N;
@@ -2477,6 +2595,15 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
                             io.sens_valid + inst, N, NMAX, exact,
                             SensWArgs<true>{io.du0_dw ? io.du0_dw + (size_t)inst * NWEIGHT * NU : nullptr, c.cur});
         });
+    } else if constexpr (SENS && TERM) {
+        const double *const tp = io.term + (size_t)inst * NTERM;
+        s = mpc_step<FT>(pb, c, lin, search, nullptr, false, [&](bool exact) {
+            sens_pass<false, true>(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * NMAX * NTASK * NU : nullptr,
+                                   io.sens_valid + inst, N, NMAX, exact, {},
+                                   TermSensArgs<true>{tp, io.du0_dxe ? io.du0_dxe + (size_t)inst * NU * NX : nullptr});
+        }, TermArg<true>{tp});
+    } else if constexpr (TERM) {
+        s = mpc_step<FT>(pb, c, lin, search, nullptr, false, NoHook{}, TermArg<true>{io.term + (size_t)inst * NTERM});
     } else if constexpr (SENS) {
         s = mpc_step<FT>(pb, c, lin, search, nullptr, false, [&](bool exact) {
             sens_pass(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * NMAX * NTASK * NU : nullptr,

@@ -87,7 +87,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
-            "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w")
+            "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -138,6 +138,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_set_weights.argtypes = [C.c_void_p, _dp, C.c_void_p]
     lib.mpcb_step_sens_w.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.POINTER(MpcbStepSensOut), _dp,
                                      C.c_void_p]
+    lib.mpcb_step_term.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.POINTER(MpcbStepSensOut), _dp, C.c_int,
+                                   _dp, C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -352,11 +354,14 @@ class MpcBatchEngine:
                     "mpcb_set_weights")
 
     def step_sens(self, io, yref=None, ref_changed: bool = False, warm=None, reset: bool = False, sens=None,
-                  stream: Optional[int] = None, du0_dw=None):
+                  stream: Optional[int] = None, du0_dw=None, term=None, term_changed: bool = False, du0_dxe=None):
         """mpcb_step_sens: step_warm() that also writes the sensitivities of u0 -- `sens` a dict of contiguous device tensors
         du0_dx [batch, 6, 12] float64, valid [batch] int32 and optionally du0_dyref [batch, N, 5, 6] float64, or None: step_warm()
         exactly.  `du0_dw` (a contiguous device tensor [batch, 7, 6] float64; needs `sens`): mpcb_step_sens_w, which also writes
-        the sensitivity of u0 to the cost weights there."""
+        the sensitivity of u0 to the cost weights there.  `term` (a contiguous device tensor [batch, 30] float64: pqq 6 | pqv 6 |
+        pvv 6 | x_e 12 per simulation) or `term_changed`: mpcb_step_term, the step with that joint-wise terminal cost in force,
+        which linearises again first when `term_changed`; `du0_dxe` (a contiguous device tensor [batch, 6, 12] float64; needs
+        `sens` and `term`) takes d u0 / d x_e.  Not together with `du0_dw`."""
         if stream is None:
             import torch
 
@@ -371,6 +376,15 @@ class MpcBatchEngine:
                                  C.cast(C.c_void_p(dy.data_ptr()), _dp) if dy is not None else None,
                                  C.cast(C.c_void_p(sens["valid"].data_ptr()), _ip))
             sp = C.byref(so)
+        if term is not None or term_changed or du0_dxe is not None:
+            if du0_dw is not None:
+                raise EngineError("the weight sensitivity (du0_dw) is not offered together with a terminal cost")
+            self._check(self.lib.mpcb_step_term(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
+                                                C.cast(C.c_void_p(term.data_ptr()), _dp) if term is not None else None,
+                                                int(bool(term_changed)),
+                                                C.cast(C.c_void_p(du0_dxe.data_ptr()), _dp) if du0_dxe is not None else None,
+                                                C.c_void_p(stream)), "mpcb_step_term")
+            return
         if du0_dw is not None:
             self._check(self.lib.mpcb_step_sens_w(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
                                                   C.cast(C.c_void_p(du0_dw.data_ptr()), _dp), C.c_void_p(stream)), "mpcb_step_sens_w")

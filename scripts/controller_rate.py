@@ -17,10 +17,15 @@ each line also reports the closed-loop effect on a schedule that slides one stag
 ramp): the medians over steps 100.. of the stationarity residual and of max |u_pred - the previous step's u_pred|.
 `--sens` asks every step for the sensitivities of u0 (BatchController.step(sens=True): the sensitivity pass in the step kernel) and
 reports the fraction of steps that had them; `--sens-w` asks for the sensitivity to the cost weights as well
-(BatchController.step(sens_w=True)).
+(BatchController.step(sens_w=True)).  `--terminal` puts a joint-wise LQR terminal cost in force before the loop
+(BatchController.set_terminal_cost with robotic_mpc_amd.terminal.lqr_terminal's blocks around each simulation's start posture at
+rest): the kernels of mpcb_step_term; with --sens every step also returns du0_dxe.  Not with --sens-w.  `--terminal zero` puts all-zero
+blocks in force instead: the same kernels on exactly the plain step's trajectory and solver work (a zero terminal cost is none), which
+isolates what the kernels themselves cost; the LQR cost changes the closed loop and with it the QP iterations per step (qp_iter_mean).
 
     python scripts/controller_rate.py [--batch 256 ...] [--engine latency|stream ...] [--N 100] [--steps 600] [--solver SQP_RTI]
                                       [--skip-rollout] [--ref none|once|every ...] [--warm carry|shift ...] [--sens] [--sens-w]
+                                      [--terminal [lqr|zero]]
 """
 import argparse
 import json
@@ -75,8 +80,12 @@ def main():
     ap.add_argument("--sens", action="store_true")
     # ... and du0_dw (the weight sums inside the sensitivity pass); implies --sens
     ap.add_argument("--sens-w", action="store_true")
+    # a joint-wise LQR terminal cost in force (the kernels of mpcb_step_term)
+    ap.add_argument("--terminal", nargs="?", const="lqr", default=None, choices=("lqr", "zero"))
     args = ap.parse_args()
     args.sens = args.sens or args.sens_w
+    if args.terminal and args.sens_w:
+        ap.error("--sens-w is not offered together with --terminal")
     for B in args.batch:
         for eng in args.engine:
             for ref in args.ref:
@@ -133,8 +142,15 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
         y[:, :, 4] += 0.01 * torch.sin(0.3 * ramp + j)
     if ref == "once":
         ctl.set_reference(sched[0])
+    if args.terminal:
+        from robotic_mpc_amd import terminal
 
-    nvalid = []
+        x_e = x0.clone()
+        x_e[:, 6:] = 0.0
+        blocks = terminal.lqr_terminal(raw[0])["blocks"] if args.terminal == "lqr" else np.zeros((6, 3))
+        ctl.set_terminal_cost(np.stack([blocks] * B), x_e)
+
+    nvalid, nqp = [], []
 
     def closed_loop(events=None):
         ctl.reset()
@@ -150,6 +166,7 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
             u = o["u0"]
             if events is not None:
                 events[-1][1].record()
+                nqp.append(o["qp_iter"].sum())                  # (outside the timed span, like the count below)
                 if args.sens:
                     nvalid.append(o["sens_valid"].sum())   # (outside the timed span; the timed loop above has no such launch)
             x = plant(x, u)
@@ -167,10 +184,11 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
     closed_loop(ev)
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
-    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, sens=bool(args.sens), sens_w=bool(args.sens_w), step_loop_ms=round(loop_ms, 3),
+    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, sens=bool(args.sens), sens_w=bool(args.sens_w), terminal=args.terminal or False, step_loop_ms=round(loop_ms, 3),
                step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
                step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
                launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
+    out.update(qp_iter_mean=round(float(torch.stack(nqp).sum()) / (B * S), 4))
     if args.sens:
         out.update(sens_valid_fraction=round(float(torch.stack(nvalid).sum()) / (B * S), 5))
     if sliding and S > 110:
