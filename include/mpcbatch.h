@@ -360,6 +360,34 @@ int mpcb_setup_controller_on(mpcb_handle *h, const mpcb_problem *p, const double
  * engine at every size.  Nsim is ignored: a controller has no run length. */
 int mpcb_controller_engine_for(const mpcb_problem *p, int ragged);
 
+/* ---- rollouts that track a time-varying task reference schedule ---- */
+/* mpcb_rollout whose closed loop tracks a schedule of the five task targets instead of the two constants packed at setup
+ * (parameters [5] and [6]).  `yref_sched` is a DEVICE pointer [batch][Nsim + N][MPCB_NREF], N = mpcb_problem.N (the longest horizon
+ * of the batch); row r of a simulation is the target at time r * dt.  Closed-loop step t (0 <= t < Nsim) of simulation i, of own
+ * horizon N_i, uses yref_sched[i][t + k] as the target of g1..g5 at stage k = 0 .. N_i - 1; row t, t = 0 .. Nsim, is also what
+ * column t of the `errors` log is measured against (hence Nsim + N rows, which keeps N = 1 legal):
+ *   e1 = g1 - y0, e2 = y1 - n . z_task, e3 = y_task.x - y2, e4 = y3 - X, e5 = y4 - v_task.y   (rows 5 and 6 unchanged)
+ * -- with the packed row [0, 1, 0, px_ref, vy_ref] the formula of mpcb_rollout term by term; mpcb_summary reduces the logged rows.
+ * The array is read during the launch only; pass the same array to every launch of one run.
+ *
+ * Step t is mpcb_step_ref(window t, ref_changed = 1) followed by the built-in plant step and log: it linearises at its start
+ * against its own window, and its cost and residuals are those of the returned iterate against window t.  The iterate, the
+ * multipliers, the QP memory, the merit weights and the fast-path suspension carry as in mpcb_rollout; the warm start is not
+ * shifted.  An SQP_RTI step therefore runs one NLP pass more than mpcb_rollout's.  Measured at N = 100, 600 steps
+ * (profiles/rollout_ref_rate.txt, device time): 1.09x mpcb_rollout's time at 256 simulations on the latency engine, 1.24x at 4096 on
+ * the throughput engine (queued; the deferred norms are lost too) -- and 1 / 1.20 and 1 / 1.17 of the 600 mpcb_step_ref launches it
+ * replaces.
+ *
+ * yref_sched == NULL is mpcb_rollout exactly (the same kernels).  Whichever engine mpcb_setup chose runs the scheduled rollout, work
+ * queue and ragged horizons included.  MPCB_ESTATE on a controller handle or before mpcb_setup; MPCB_EINVAL with
+ * MPCB_PRECISION_FP32_RICCATI; the step-range rules of mpcb_rollout. */
+int mpcb_rollout_ref(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
+                     const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] or NULL */, void *stream);
+
+/* 1: the last mpcb_rollout / mpcb_rollout_ref launch of this handle went through the throughput engine's work queue, 0: it did
+ * not (< 0: error).  Host state only. */
+int mpcb_queue_used(mpcb_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

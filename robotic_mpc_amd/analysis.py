@@ -30,8 +30,12 @@ def surface_normal(coeffs, x, y):
     return np.stack([nx / nn, ny / nn, nz / nn])
 
 
-def compute_errors(ee_pose: np.ndarray, ee_vel: np.ndarray, coeffs, t_ee, px_ref: float, vy_ref: float) -> Dict[str, np.ndarray]:
-    """simulator.py:265-344.  ee_pose (12,T) = [p; R row-major], ee_vel (6,T) = J_world qdot."""
+def compute_errors(ee_pose: np.ndarray, ee_vel: np.ndarray, coeffs, t_ee, px_ref: float, vy_ref: float, yref=None) -> Dict[str, np.ndarray]:
+    """simulator.py:265-344.  ee_pose (12,T) = [p; R row-major], ee_vel (6,T) = J_world qdot.
+
+    `yref` (T,5): the rows of a task reference schedule (reference.py) the columns are measured against, instead of the constant
+    row [0, 1, 0, px_ref, vy_ref] -- e1 = g1 - y0, e2 = y1 - g2, e3 = g3 - y2, e4 = y3 - g4, e5 = y4 - g5; with that constant row,
+    the same numbers."""
     p = ee_pose[:3]                              # :271
     R = ee_pose[3:12].T.reshape(-1, 3, 3)        # :303, one 3x3 per step
     t = np.asarray(t_ee, dtype=np.float64).reshape(3)
@@ -51,6 +55,14 @@ def compute_errors(ee_pose: np.ndarray, ee_vel: np.ndarray, coeffs, t_ee, px_ref
     g3 = R_task_y[:, 0]                          # :333
     g4 = px                                      # :334
     g5 = v_task[:, 1]                            # :335
+    if yref is not None:
+        y = np.asarray(yref, dtype=np.float64)
+        if y.shape != (g1.shape[0], 5):
+            raise ValueError(f"yref must be [{g1.shape[0]}, 5] (one row per logged column), got {y.shape}")
+        return {
+            "e1": g1 - y[:, 0], "e2": y[:, 1] - g2, "e3": g3 - y[:, 2], "e4": y[:, 3] - g4, "e5": y[:, 4] - g5,
+            "p_task_z": pz, "p_ee_y": p[1].copy(),
+        }
     return {
         "e1": g1, "e2": 1.0 - g2, "e3": g3, "e4": px_ref - g4, "e5": vy_ref - g5,  # :337-341
         "p_task_z": pz, "p_ee_y": p[1].copy(),                                     # :342,344

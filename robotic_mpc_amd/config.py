@@ -36,7 +36,10 @@ EXTENSION_DEFAULTS = {"translation_ee_t": (0.0, 0.0, 0.1), "urdf_path": None, "e
                       # inside every bound is solved by ONE Riccati factorisation instead of the interior-point loop (same solution to
                       # well below qp_tol).  False: every QP goes through the HPIPM-style loop, as in the reference's solver.solve()
                       # (simulator.py:212)
-                      "qp_fast_path": True}
+                      "qp_fast_path": True,
+                      # time-varying task reference of the rollout (reference.py): None -- regulate to px_ref / vy_ref -- or a
+                      # JSON-serialisable spec {"kind": "table" | "serpentine", ...}; fp64 only
+                      "reference_schedule": None}
 # codes of the parameter record (include/mpcbatch.h [7]); RK4 = 0 keeps default records unchanged
 PLANT_INTEGRATORS = {"RK4": 0, "Euler": 1, "RK2": 2, "RK3": 3}
 
@@ -248,7 +251,19 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
     t_ee = np.asarray(cfg["translation_ee_t"], dtype=np.float64).reshape(-1)
     if t_ee.shape != (3,):
         raise ValueError("translation_ee_t must have 3 entries")
+    schedule = cfg["reference_schedule"]
+    if schedule is not None:
+        from . import reference
+
+        if cfg["riccati_precision"] == "fp32":
+            raise ValueError("a reference_schedule is offered with riccati_precision='fp64' only")
+        reference.validate(schedule)
+        schedule = copy.deepcopy(dict(schedule))
+        # (the number of rows of a table, and everything else, against this run's Nsim + N)
+        reference.sample({"reference_schedule": schedule, "Nsim": Nsim, "N": N, "dt": dt, "px_ref": float(cfg["px_ref"]),
+                          "vy_ref": float(cfg["vy_ref"])})
     return {
+        "reference_schedule": schedule,
         "robot_name": cfg["robot_name"], "urdf_path": cfg["urdf_path"], "ee_frame": cfg["ee_frame"],
         "N": N, "Nsim": Nsim, "dt": dt,
         "solver_type": SOLVER_RTI if so["nlp_solver_type"] == "SQP_RTI" else SOLVER_SQP,

@@ -460,9 +460,11 @@ struct Engine {
     // path's right-hand side for the NEW plant state (gt = g, Gamma = 0, rb = b + A dx_0: the same products the stationarity rows are
     // made of), so fast_rhs needs no pass of its own; with room for whole G2 records in LDS (stride L2W) it leaves with the
     // linearisation in one coalesced store, otherwise by 8-byte stores from the items.
-    // REF (the controller step's instantiation only): the task residuals are formed against the task reference `ref` (non-null,
-    // task_targets).
-    template <bool REF = false>
+    // REF (the controller step's and the scheduled rollout's instantiations): the task residuals are formed against the task reference
+    // `ref` (non-null, task_targets).  RLOG (with REF; the scheduled rollout's, rollout<true>): `ref` is the window of a reference
+    // schedule, and the plant lane measures the task errors of the new plant state against its row 1 -- the schedule row of the log
+    // column that state goes to.
+    template <bool REF = false, bool RLOG = false>
     MPC_PASS double nlp_direct(double alpha, bool do_update, bool sqp_mult, double *res4, bool do_plant = false, bool fuse_commit = false,
                                bool want_rhs = false, TaskRef ref = TaskRef{nullptr})
     {
@@ -672,7 +674,8 @@ struct Engine {
                         sm.logv[24 + j] = zn[j]; sm.logv[30 + j] = zn[6 + j];
                     }
                     plant_log(rb, zn, sm.logv);
-                    task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
+                    if constexpr (REF && RLOG) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, ref.y + NTASK);
+                    else task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
                     sm.ret[6] = ex.clock() - tp0;
                 }
                 ex.put_sum(sm.red[4], lane, csum);
@@ -3174,7 +3177,15 @@ struct Engine {
 
     // ======================================================================= closed loop
     // Simulator.run (simulator.py:199-241) for steps [step0, step1) of one instance.
-    MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1)
+    // REF (the kernels of mpcb_rollout_ref, mpc_rollout_ref.hip): the task reference is a schedule, `sched` [Nsim + N][NTASK] rows of
+    // this simulation.  Step i is control_step against the window sched + i * NTASK with ref_changed set, followed by the plant step:
+    // it linearises at its start against its own window (the carried linearisation was formed against the previous one, and so was
+    // the fast path's right-hand side, which the closing pass therefore does not form), its cost and residual norms are those of the
+    // new iterate against that window, and log column t measures the task errors against schedule row t.  Everything else carries as
+    // without a schedule; there is no shift.
+    struct NoSched {};
+    template <bool REF = false>
+    MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {})
     {
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
@@ -3185,22 +3196,32 @@ struct Engine {
         int log_lo = step0 == 0 ? 0 : step0 + 1;   // first log column this launch produces
         if (step0 == 0) {
             initial_guess();
-            log_lo = ex.uni(log_state(out, inst, 0, log_lo, false));
+            if constexpr (REF) log_lo = ex.uni(log_state<true>(out, inst, 0, log_lo, false, sched));
+            else log_lo = ex.uni(log_state(out, inst, 0, log_lo, false));
         } else {
             ex.par([&](int lane) {
                 if (lane < NX) sm.xhat[lane] = w.state[ST_Z + lane];
             });
             load_carry(lin_valid);
         }
+        TaskRef ref{nullptr};                       // (REF) the window of step i
         const auto lin = [&](double alpha, bool do_update, bool sqp_mult, double *r4, bool do_plant, bool fuse_commit, bool want_rhs) {
-            return nlp_direct(alpha, do_update, sqp_mult, r4, do_plant, fuse_commit, want_rhs);
+            if constexpr (REF) return nlp_direct<true, true>(alpha, do_update, sqp_mult, r4, do_plant, fuse_commit, false, ref);
+            else return nlp_direct(alpha, do_update, sqp_mult, r4, do_plant, fuse_commit, want_rhs);
         };
-        const auto search = [&](int sqp_iter) { return line_search(sqp_iter); };
+        const auto search = [&](int sqp_iter) {
+            if constexpr (REF) return line_search<true>(sqp_iter, ref);
+            else return line_search(sqp_iter);
+        };
         for (int i = step0; i < step1; i++) {
             int sqp_iter = 0, qp_iter = 0;
             double res4[4] = {0, 0, 0, 0}, cost = 0.0;
             const double t0 = ex.clock();
             bool plant_done = false;
+            if constexpr (REF) {
+                ref = TaskRef{sched + (size_t)i * NTASK};
+                lin_valid = false;
+            }
             const int status = nlp_step<true>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
             const double t1 = ex.clock();
             PROF_T0(tp);
@@ -3224,7 +3245,8 @@ struct Engine {
             ex.par([&](int lane) {
                 if (lane < NX) sm.xhat[lane] = sm.logv[24 + lane];
             });
-            log_lo = ex.uni(log_state(out, inst, i + 1, log_lo, plant_done));
+            if constexpr (REF) log_lo = ex.uni(log_state<true>(out, inst, i + 1, log_lo, plant_done, sched + (size_t)(i + 1) * NTASK));
+            else log_lo = ex.uni(log_state(out, inst, i + 1, log_lo, plant_done));
             const double t2 = ex.clock();
             // plant_time: what is left of it here + the plant lane's own time inside the NLP pass
             ex.par([&](int lane) { if (lane == 0) out.plant_time[sb + i] = (t2 - t1) + (plant_done ? sm.ret[6] : 0.0); });
@@ -3588,7 +3610,10 @@ struct Engine {
     // Simulator.errors (simulator.py:265-344) of that column.  Columns collect in LDS (sm.logbuf) and leave as
     // contiguous runs of up to LOGB columns per row: `log_lo` = first column of the current block still in LDS.
     // `computed`: sm.logv already holds the pose / rpy / J qdot / task errors of sm.xhat (done inside the last NLP pass)
-    MPC_PASS int log_state(const Outputs &out, int inst, int col, int log_lo, bool computed)
+    // REF (rollout<true>): the task errors are measured against `yrow`, the reference schedule's row of this column
+    template <bool REF = false>
+    MPC_PASS int log_state(const Outputs &out, int inst, int col, int log_lo, bool computed,
+                           typename std::conditional<REF, const double *, NoSched>::type yrow = {})
     {
         Smem &sm = ex.smem();
         const Robot &rb = sm.rb;
@@ -3598,7 +3623,8 @@ struct Engine {
 #pragma unroll
                 for (int i = 0; i < 12; i++) z[i] = sm.xhat[i];
                 plant_log(rb, z, sm.logv);
-                task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
+                if constexpr (REF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow);
+                else task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
             }
         });
         ex.par([&](int lane) {

@@ -69,6 +69,15 @@ void launch_step_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStre
                       const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
 void launch_stream_step_sens(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
                              size_t ws_stride, const StepIO &io, int reset);
+// ... and the rollout kernels of both engines that track a task reference schedule (mpcb_rollout_ref): mpc_rollout_ref.hip,
+// mpc_stream_rollout_ref.hip
+const void *rollout_ref_kernel(int waves_per_sim, int wpe);
+void launch_rollout_ref(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                        const InstParams *params, double *ws_base, size_t ws_stride, const Outputs &out, int step0, int step1,
+                        int pool_doubles, const double *yref_sched);
+void launch_stream_rollout_ref(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                               size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
+                               long long timeout_ticks, const double *yref_sched);
 }  // namespace mpcb
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
@@ -107,6 +116,8 @@ __global__ __launch_bounds__(WAVE *NWV, WPE) void mpc_rollout_kernel(Problem pb,
 // The bound is a bug guard, not a schedule: a waiting item's predecessor is always running, so it is sized from the WORK LIMIT of
 // one chunk (queue_timeout_ticks below), never from typical times -- a legitimately slow chunk (full SQP at a long horizon, every
 // QP running to qp_solver_iter_max) must not trip it and take the whole bucket down.
+// (The kernel of the scheduled rollout, mpc_stream_rollout_ref.hip, repeats this loop: moved into a shared function template over
+// the body, it compiled this kernel to other code than it has here.)
 template <class FT>
 __global__ __launch_bounds__(WAVE, MPCB_STREAM_WPE) void mpc_stream_kernel(Problem pb, const Robot *__restrict__ rbd, const InstParams *__restrict__ params,
                                                                            double *ws_base, size_t ws_stride, Outputs out, int step0, int step1,
@@ -540,11 +551,12 @@ static const void *latency_kernel(const mpcb_handle *h)
 // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
 // handle can ask for, right before the launch
 // (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens, 3 of mpcb_step_sens_w, 4 / 5 of
-// mpcb_step_term without / with sens)
+// mpcb_step_term without / with sens, 6 of mpcb_rollout_ref)
 static int raise_lds_limit(mpcb_handle *h, int step = 0)
 {
     static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(step == 5 ? step_term_sens_kernel(h->waves_per_sim, h->wpe)
+    HIPCHK(h, hipFuncSetAttribute(step == 6 ? rollout_ref_kernel(h->waves_per_sim, h->wpe)
+                                  : step == 5 ? step_term_sens_kernel(h->waves_per_sim, h->wpe)
                                   : step == 4 ? step_term_kernel(h->waves_per_sim, h->wpe)
                                   : step == 3 ? step_sensw_kernel(h->waves_per_sim, h->wpe)
                                   : step == 2 ? step_sens_kernel(h->waves_per_sim, h->wpe)
@@ -567,9 +579,19 @@ static long long queue_timeout_ticks(const Problem &pb, int chunk_steps)
 
 int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, void *stream)
 {
+    return mpcb_rollout_ref(h, step0, step1, o, nullptr, stream);
+}
+
+// (yref_sched == NULL: the kernels of mpcb_rollout; otherwise those of the scheduled rollout, mpc_rollout_ref.hip /
+// mpc_stream_rollout_ref.hip -- one launch path: queue sizing, timeout, events and next_step are the same, only the kernel and one
+// argument differ)
+int mpcb_rollout_ref(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, void *stream)
+{
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
     if (h->controller) return fail(h, MPCB_ESTATE, "mpcb_rollout on a controller handle (mpcb_setup_controller): use mpcb_step");
+    if (yref_sched && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_ref: a reference schedule is offered in fp64 only (no fp32 Riccati leg)");
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -609,7 +631,10 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
         const long long qticks = queue_timeout_ticks(h->pb, chunk);
         HIPCHK(h, hipEventRecord(h->ev0, s));
         const dim3 sgrid((unsigned)(queued ? nslots : h->pb.batch));
-        if (h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        if (yref_sched)
+            launch_stream_rollout_ref(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
+                                      yref_sched);
+        else if (h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
             hipLaunchKernelGGL(mpc_stream_kernel<float>, sgrid, dim3(WAVE), 0, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out,
                                step0, step1, queue, chunk, qticks);
         else
@@ -623,10 +648,13 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
         return MPCB_OK;
     }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    if (int rc = raise_lds_limit(h)) return rc;
+    if (int rc = raise_lds_limit(h, yref_sched ? 6 : 0)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
     const dim3 grid((unsigned)h->pb.batch);
-    if (h->waves_per_sim == 8)
+    if (yref_sched)
+        launch_rollout_ref(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
+                           h->pool_doubles, yref_sched);
+    else if (h->waves_per_sim == 8)
         hipLaunchKernelGGL(mpc_rollout_kernel<8>, grid, dim3(WAVE * 8), lds, s, h->pb, h->rb, h->d_params, h->d_ws,
                            h->ws_stride, out, step0, step1, h->pool_doubles);
     else if (h->waves_per_sim == 4 && h->wpe == 2)
@@ -828,6 +856,12 @@ int mpcb_engine(mpcb_handle *h)
 {
     if (!h || !h->ready) return MPCB_EINVAL;
     return h->engine;
+}
+
+int mpcb_queue_used(mpcb_handle *h)
+{
+    if (!h || !h->ready) return MPCB_EINVAL;
+    return h->queue_used ? 1 : 0;
 }
 
 int mpcb_engine_for(const mpcb_problem *p)

@@ -255,4 +255,29 @@ MPC_HD void task_errors(const InstParams &P, const Robot &rb, const double *pose
     out7[6] = pose12[1];                                               // p_ee_y             :344
 }
 
+// The same against a row y[NTASK] of a task reference schedule (mpcb_rollout_ref) instead of the packed [0, 1, 0, px_ref, vy_ref]:
+// e1 = g1 - y0, e2 = y1 - n . z_task, e3 = y_task[0] - y2, e4 = y3 - X, e5 = y4 - v_task,y -- with the packed row, the formula
+// above term by term.  Rows 5 and 6 do not depend on the reference.
+MPC_HD void task_errors(const InstParams &P, const Robot &rb, const double *pose12, const double *vel6, double *out7, const double *y)
+{
+    const double r00 = pose12[3], r01 = pose12[4], r02 = pose12[5], r10 = pose12[6], r11 = pose12[7], r12 = pose12[8],
+                 r20 = pose12[9], r21 = pose12[10], r22 = pose12[11];
+    const double tx = rb.t_ee[0], ty = rb.t_ee[1], tz = rb.t_ee[2];
+    const double twx = r00 * tx + r01 * ty + r02 * tz, twy = r10 * tx + r11 * ty + r12 * tz, twz = r20 * tx + r21 * ty + r22 * tz;
+    const double X = pose12[0] + twx, Y = pose12[1] + twy, Z = pose12[2] + twz;
+    const double dotw = vel6[3] * twx + vel6[4] * twy + vel6[5] * twz;
+    const double vty = r10 * (vel6[0] + dotw) + r11 * (vel6[1] + dotw) + r12 * (vel6[2] + dotw);
+    const double a = P.coeffs[0], b = P.coeffs[1], c = P.coeffs[2], d = P.coeffs[3], e = P.coeffs[4], f = P.coeffs[5];
+    const double nx = 2 * a * X + c * Y + d, ny = 2 * b * Y + c * X + e;
+    const double nn = sqrt(nx * nx + ny * ny + 1.0);
+    const double S = a * X * X + b * Y * Y + c * X * Y + d * X + e * Y + f;
+    out7[0] = (S - Z) - y[0];
+    out7[1] = y[1] - (nx / nn * r02 + ny / nn * r12 + (-1.0 / nn) * r22);
+    out7[2] = r01 - y[2];
+    out7[3] = y[3] - X;
+    out7[4] = y[4] - vty;
+    out7[5] = Z;
+    out7[6] = pose12[1];
+}
+
 }  // namespace mpcb

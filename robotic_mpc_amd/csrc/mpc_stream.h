@@ -2065,7 +2065,10 @@ SE_DEV void log_flush(const Outputs &out, int inst, int T1, int c_lo, int c_hi)
     fence();
 }
 
-SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo)
+// REF (rollout<FT, true>): the task errors are measured against `yrow`, the reference schedule's row of this column
+struct NoSched {};
+template <bool REF = false>
+SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo, typename std::conditional<REF, const double *, NoSched>::type yrow = {})
 {
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
@@ -2075,7 +2078,8 @@ SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo)
 #pragma unroll
         for (int i = 0; i < 12; i++) z[i] = sm.xhat[i];
         plant_log(rb, z, sm.logv);
-        task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
+        if constexpr (REF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow);
+        else task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
     }
     fence();
     if (lane < LOG_ROWS) sm.logbuf[lane][col & (SLOGB - 1)] = nlp::log_value(lane, sm.xhat, sm.u0, sm.logv);
@@ -2254,10 +2258,17 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 
 // =============================================================================================== rollout and controller step
 // Simulator.run (simulator.py:199-241) for steps [step0, step1) of one simulation.
-template <class FT>
+// REF (the kernel of mpcb_rollout_ref, mpc_stream_rollout_ref.hip): the task reference is a schedule, `sched` [Nsim + NMAX][NTASK] rows of
+// this simulation (NMAX the longest horizon of the batch; this simulation reads rows [t, t + N) at step t, and row t for log column
+// t).  Step i is control_step against the window sched + i * NTASK with ref_changed set, followed by the plant step: it linearises at
+// its start against its own window, and forms its own cost and residual norms against it -- the next step's first pass runs against
+// the next window, so nothing is deferred.  Everything else carries as without a schedule; there is no shift.
+template <class FT, bool REF = false>
 SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
-                    const Outputs &out, int inst, int step0, int step1)
+                    const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched_ = {})
 {
+    const double *sched = nullptr;
+    if constexpr (REF) sched = uni_ref(TaskRef{sched_}).y;
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
     const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), Nsim = pb.Nsim, T1 = Nsim + 1;
@@ -2271,7 +2282,8 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if (lane < NX) sm.xhat[lane] = lane < 6 ? P.q0[lane] : P.qdot0[lane - 6];
         if (lane < NU) sm.u0[lane] = P.qdot0[lane];                   // u[:,0] = qdot_0 (simulator.py:81)
         initial_guess<FT>(pb, N);
-        log_lo = uni(log_state(out, inst, T1, 0, log_lo));
+        if constexpr (REF) log_lo = uni(log_state<true>(out, inst, T1, 0, log_lo, sched));
+        else log_lo = uni(log_state(out, inst, T1, 0, log_lo));
     } else {
         if (lane < NX) sm.xhat[lane] = w.state[ST_Z + lane];
         c.load(w.state);
@@ -2282,9 +2294,18 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
     for (int i = step0; i < step1; i++) {
         const double t0 = wclock();
         // the last step of this launch / work item forms its own norms; the others leave them to the next step's first pass
-        const bool defer = pb.solver_type == 1 && i + 1 < step1;
+        // (REF: every step forms its own -- the next step's first pass runs against the next window)
+        const bool defer = !REF && pb.solver_type == 1 && i + 1 < step1;
         double nlp_prev[5];
-        const StepStats s = mpc_step<FT>(pb, c, lin, search, res_pending ? nlp_prev : nullptr, defer);
+        StepStats s;
+        if constexpr (REF) {
+            const TaskRef ref{sched + (size_t)i * NTASK};
+            c.lin_valid = false;
+            s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
+                             [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false);
+        } else {
+            s = mpc_step<FT>(pb, c, lin, search, res_pending ? nlp_prev : nullptr, defer);
+        }
         // cost and residual norms of step i-1, evaluated by this step's first pass
         if (res_pending) nlp::put_nlp(out, sbase + i - 1, lane, nlp_prev[0], nlp_prev[1], nlp_prev[2], nlp_prev[3], nlp_prev[4]);
         res_pending = defer;
@@ -2307,7 +2328,8 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         fence();
         if (lane < NX) sm.xhat[lane] = sm.logv[24 + lane];
         fence();
-        log_lo = uni(log_state(out, inst, T1, i + 1, log_lo));
+        if constexpr (REF) log_lo = uni(log_state<true>(out, inst, T1, i + 1, log_lo, sched + (size_t)(i + 1) * NTASK));
+        else log_lo = uni(log_state(out, inst, T1, i + 1, log_lo));
         const double t2 = wclock();
         if (lane == 0) out.plant_time[sbase + i] = t2 - t1;
 #ifdef MPCB_SPROF

@@ -87,7 +87,8 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
-            "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term")
+            "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
+            "mpcb_rollout_ref", "mpcb_queue_used")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -121,6 +122,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_result_bytes_per_sim.restype = C.c_size_t
     lib.mpcb_setup.argtypes = [C.c_void_p, C.POINTER(MpcbProblem), _dp, _dp]
     lib.mpcb_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), C.c_void_p]
+    lib.mpcb_rollout_ref.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.c_void_p]
+    lib.mpcb_queue_used.argtypes = [C.c_void_p]
     lib.mpcb_sync.argtypes = [C.c_void_p]
     lib.mpcb_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.mpcb_kernel_info.argtypes = [C.c_void_p] + [_ip] * 4
@@ -260,14 +263,41 @@ class MpcBatchEngine:
             setattr(r, name, C.cast(C.c_void_p(ptr), _dp if ty == "f8" else _ip))
         return r
 
-    def rollout(self, bufs, step0: int, step1: int, stream: Optional[int] = None):
-        """Asynchronous launch of closed-loop steps [step0, step1) into device buffers."""
+    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None):
+        """Asynchronous launch of closed-loop steps [step0, step1) into device buffers.  `yref`: the task reference schedules of
+        the batch, a contiguous float64 device tensor [batch, Nsim + N, 5] (N the longest horizon; schedule_tensor) -- the same one
+        for every launch of a run -- or None for the packed references (mpcb_rollout)."""
         if stream is None:
             import torch
 
             stream = torch.cuda.current_stream(self.device).cuda_stream
         r = self._result_struct(bufs)
-        self._check(self.lib.mpcb_rollout(self._h, step0, step1, C.byref(r), C.c_void_p(stream)), "mpcb_rollout")
+        if yref is None:
+            self._check(self.lib.mpcb_rollout(self._h, step0, step1, C.byref(r), C.c_void_p(stream)), "mpcb_rollout")
+            return
+        pb = self._pb
+        if tuple(yref.shape) != (pb.batch, pb.Nsim + pb.N, 5) or not yref.is_contiguous() or str(yref.dtype) != "torch.float64":
+            raise ValueError(f"yref must be a contiguous float64 tensor [{pb.batch}, {pb.Nsim + pb.N}, 5], got {tuple(yref.shape)} {yref.dtype}")
+        self._check(self.lib.mpcb_rollout_ref(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp),
+                                              C.c_void_p(stream)), "mpcb_rollout_ref")
+
+    def queue_used(self) -> bool:
+        """Whether the last rollout launch went through the throughput engine's work queue (mpcb_queue_used)."""
+        rc = int(self.lib.mpcb_queue_used(self._h))
+        if rc < 0:
+            raise EngineError(f"mpcb_queue_used failed ({rc})")
+        return rc == 1
+
+    def schedule_tensor(self, cfgs: Sequence[Dict]):
+        """The reference schedules of a bucket (reference.stack) on this engine's device, or None when the configurations carry
+        none (a bucket is all or nothing: packing.bucket_key)."""
+        if not any(c.get("reference_schedule") is not None for c in cfgs):
+            return None
+        import torch
+
+        from . import reference
+
+        return torch.from_numpy(reference.stack(cfgs)).to(torch.device("cuda", self.device))
 
     def sync(self):
         self._check(self.lib.mpcb_sync(self._h), "mpcb_sync")
@@ -413,10 +443,11 @@ class MpcBatchEngine:
         """setup + all steps; returns (problem, dict of device tensors). Synchronous."""
         pb = self.setup(cfgs, chain)
         bufs = self.alloc_results(pb)
+        yref = self.schedule_tensor(cfgs)      # sampled and stacked once; every chunk gets the same array
         chunk = step_chunk if step_chunk and step_chunk > 0 else pb.Nsim
         self.last_kernel_ms = []
         for s0 in range(0, pb.Nsim, chunk):
-            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk))
+            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref)
             self.sync()
             self.last_kernel_ms.append(self.kernel_ms())
         return pb, bufs
@@ -428,7 +459,10 @@ class MpcBatchEngine:
 
     # ------------------------------------------------------------------ host-buffer path
     def run_host_buffers(self, cfgs: Sequence[Dict], chain) -> Dict[str, np.ndarray]:
-        """Same through mpcb_run (library-owned device buffers, numpy in/out, no torch)."""
+        """Same through mpcb_run (library-owned device buffers, numpy in/out, no torch).  mpcb_run takes no reference schedule:
+        configurations that carry one are refused."""
+        if any(c.get("reference_schedule") is not None for c in cfgs):
+            raise ValueError("mpcb_run takes no reference schedule: run configurations with a reference_schedule through run() / run_device()")
         pb = make_problem(cfgs)
         params = packing.pack_batch(cfgs)
         robot = np.ascontiguousarray(chain.packed(cfgs[0]["t_ee"]), dtype=np.float64)

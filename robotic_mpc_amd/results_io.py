@@ -101,7 +101,7 @@ def load_archive(path: str) -> Dict[str, np.ndarray]:
             raise ValueError(f"{path}: unsupported format version {ver}")
         arch = {k: f[k] for k in f.files}
     if ver == 1:
-        from . import analysis
+        from . import analysis, reference
         from .config import resolve_config
 
         K = len(arch["names"])
@@ -111,7 +111,7 @@ def load_archive(path: str) -> Dict[str, np.ndarray]:
             c = resolve_config(json.loads(str(arch["configs"][i])))
             n = int(arch["nsim"][i])
             e = analysis.compute_errors(arch["ee_pose"][i][:, :n + 1], arch["ee_vel"][i][:, :n + 1], c["coeffs"], c["t_ee"],
-                                        c["px_ref"], c["vy_ref"])
+                                        c["px_ref"], c["vy_ref"], yref=reference.log_rows(c))
             err[i, :, :n + 1] = analysis.errors_rows(e)
         arch["errors"] = err
         arch["plant_time"] = np.zeros_like(arch["solver_time"])

@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import analysis, config as cfgmod, packing, robots
+from . import analysis, config as cfgmod, packing, reference, robots
 
 
 def chain_for(cfg: Dict) -> robots.KinematicChain:
@@ -179,7 +179,7 @@ class Simulator:
             return analysis.errors_dict(self._errors_rows)
         sm = self.simulation_model
         return analysis.compute_errors(sm._ee_pose_log, sm._ee_velocity_log, self.resolved["coeffs"], self.translation,
-                                       self.px_ref, self.vy_ref)
+                                       self.px_ref, self.vy_ref, yref=reference.log_rows(self.resolved))
 
     @cached_property
     def metrics(self):
@@ -205,8 +205,12 @@ class Simulator:
     def get_data(self):
         self._need_run("data")
         sm = self.simulation_model
-        return analysis.compute_data(sm.z, sm.u, sm._ee_pose_log, self.wcv, self.dt, self.mpc.px_ref, self.mpc.vy_ref,
+        data = analysis.compute_data(sm.z, sm.u, sm._ee_pose_log, self.wcv, self.dt, self.mpc.px_ref, self.mpc.vy_ref,
                                      self.prediction_horizon)
+        rows = reference.log_rows(self.resolved)
+        if rows is not None:
+            data["reference_schedule"] = rows      # [Nsim + 1, 5]: the targets in force at every logged column
+        return data
 
     def get_analysis(self):
         self._need_run("analysis")
@@ -313,12 +317,13 @@ class _EngineRunner:
         pb = eng.setup(cfgs, chain)
         with torch.cuda.stream(stream):
             bufs = eng.alloc_results(pb)
-            eng.rollout(bufs, 0, pb.Nsim, stream=stream.cuda_stream)
+            yref = eng.schedule_tensor(cfgs)   # the bucket's reference schedules, or None (kept alive by the ticket)
+            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream)
             summary = eng.summary(bufs, stream=stream.cuda_stream)
-        return eng, stream, bufs, summary
+        return eng, stream, bufs, summary, yref
 
     def collect(self, ticket):
-        eng, stream, bufs, summary = ticket
+        eng, stream, bufs, summary, _yref = ticket
         try:
             stream.synchronize()
             eng.sync()                  # (also reports a failed work-queue hand-off of the throughput engine)

@@ -16,7 +16,11 @@ SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_kernel.hip")
 STEP_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_step.hip")
 # the throughput engine's controller step kernel (a module of its own as well): its passes are the rollout's, under HOT_STREAM
 STREAM_STEP_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_step.hip")
-SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC)
+# the kernels of the rollout against a reference schedule (mpcb_rollout_ref; modules of their own): the rollout kernels with the
+# REF passes, under budgets of their own below
+ROLLOUT_REF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_ref.hip")
+STREAM_ROLLOUT_REF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_ref.hip")
+SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC)
 
 
 def scan(asm_text):
@@ -61,6 +65,12 @@ BUDGET = {
     "10merit_pass": 210, "se8lin_pass": 8, "se9log_state": 8,
     "18mpc_rollout_kernelILi8ELi1E": 340, "18mpc_rollout_kernelILi4ELi2E": 330, "18mpc_rollout_kernelILi4ELi1E": 258,
     "17mpc_stream_kernelId": 160, "17mpc_stream_kernelIf": 160,
+    # the scheduled rollout (recorded: 224 / 293 / 61 for the kernel bodies, 127 for the throughput engine's; its NLP pass against the
+    # window, with the plant lane's reference row, 37 / 38 / 2; lin_pass<true> 3)
+    "22mpc_rollout_ref_kernelILi8ELi1E": 246, "22mpc_rollout_ref_kernelILi4ELi2E": 322, "22mpc_rollout_ref_kernelILi4ELi1E": 68,
+    "21mpc_stream_ref_kernelId": 140,
+    "DevExecILi8ELi1EELb0EE10nlp_directILb1ELb1E": 41, "DevExecILi4ELi2EELb0EE10nlp_directILb1ELb1E": 42,
+    "DevExecILi4ELi1EELb0EE10nlp_directILb1ELb1E": 8,
 }
 
 
@@ -110,9 +120,13 @@ def compile_asm(src, d, extra):
 
 def main():
     hits, spills = [], {}
+    from concurrent.futures import ThreadPoolExecutor
+
     with tempfile.TemporaryDirectory() as d:
-        for src in SOURCES:
-            text = compile_asm(src, d, sys.argv[1:])
+        # (the modules are independent: one hipcc each, side by side)
+        with ThreadPoolExecutor(max(1, min(len(SOURCES), len(os.sched_getaffinity(0))))) as pool:
+            texts = list(pool.map(lambda src: compile_asm(src, d, sys.argv[1:]), SOURCES))
+        for text in texts:
             hits += scan(text)
             for f, (n, limit) in scratch_ops(text).items():     # (a pass compiled in several modules: its worst count)
                 if f not in spills or n > spills[f][0]:
