@@ -384,7 +384,44 @@ int mpcb_controller_engine_for(const mpcb_problem *p, int ragged);
 int mpcb_rollout_ref(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
                      const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] or NULL */, void *stream);
 
-/* 1: the last mpcb_rollout / mpcb_rollout_ref launch of this handle went through the throughput engine's work queue, 0: it did
+/* ---- rollouts over a perturbed plant: model mismatch, input disturbance, measurement noise ---- */
+/* mpcb_rollout_ref whose built-in plant is not the model the controller predicts with.  With z the TRUE plant state (q; qdot) of
+ * simulation i:
+ *   z_0 = [q_0; qdot_0]
+ *   for t = 0 .. Nsim - 1:
+ *       xhat_t  = z_t + x_noise[i][t]                        what the controller sees
+ *       u_t     = u0 of mpcb_step_ref(xhat_t, window t of yref_sched, ref_changed = 1)
+ *       z_{t+1} = plant step (the configured integrator, wcv[i], dt) from z_t with the input u_t + u_dist[i][t]
+ * The solver memory carries as in mpcb_rollout_ref, the first step starts from the packed initial guess x_k = [q_0; qdot_0] (not from
+ * xhat_0), and there is no shift.  The logs record the truth: z, ee_pose, ee_rpy, ee_vel and errors come from z_t (errors against
+ * schedule row t, as in mpcb_rollout_ref), u[:, t + 1] = u_t is the COMMANDED input (not u_t + u_dist); cost, residuals, status,
+ * sqp_iter and qp_iter are those of the step solved from xhat_t.  The model keeps the bandwidths of parameter [8..13].
+ *
+ * Every member is a DEVICE pointer and may be NULL (= that perturbation off); the arrays are read during the launch only -- pass the
+ * same arrays to every launch of one run: what carries from one launch (and one work-queue item) to the next is the true state, and
+ * each forms its first feedback state from x_noise[step0].  No row Nsim is read.
+ *
+ * pert == NULL is mpcb_rollout_ref exactly (the same kernels, the same bits).  pert != NULL with all three members NULL is legal:
+ * the nominal loop through the kernels of the perturbed rollout (the scheduled rollout's results to rounding; its plant step runs
+ * after the solve, never inside the last NLP pass).  pert != NULL needs yref_sched (MPCB_EINVAL without: a run without a schedule
+ * passes the packed row [0, 1, 0, px_ref, vy_ref] on every row) and fp64 (MPCB_EINVAL with MPCB_PRECISION_FP32_RICCATI).
+ * MPCB_ESTATE on a controller handle or before mpcb_setup; the step-range rules of mpcb_rollout.  Whichever engine mpcb_setup chose
+ * runs it, work queue and ragged horizons included; mpcb_queue_used and mpcb_last_kernel_ms apply, and after such a launch
+ * mpcb_kernel_info reports the perturbed rollout's kernel.  The 30 values a step reads are fetched from global memory by the lanes
+ * that use them: no workspace, LDS or mpcb_workspace_bytes changes.  Measured at N = 100, 600 steps
+ * (profiles/rollout_pert_rate.txt, device time): 1.02x mpcb_rollout_ref's time at 256 simulations on the latency engine (the plant
+ * step and the log of the new state follow the solve), 1.001x at 4096 on the throughput engine (queued). */
+typedef struct {
+    const double *wcv;     /* [batch][6]        the plant's bandwidths                                  */
+    const double *u_dist;  /* [batch][Nsim][6]  added to u_t before the plant step                      */
+    const double *x_noise; /* [batch][Nsim][12] added to z_t to form the feedback state of step t       */
+} mpcb_plant_pert;
+
+int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
+                      const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
+                      void *stream);
+
+/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert launch of this handle went through the throughput engine's work queue, 0: it did
  * not (< 0: error).  Host state only. */
 int mpcb_queue_used(mpcb_handle *h);
 

@@ -39,7 +39,11 @@ EXTENSION_DEFAULTS = {"translation_ee_t": (0.0, 0.0, 0.1), "urdf_path": None, "e
                       "qp_fast_path": True,
                       # time-varying task reference of the rollout (reference.py): None -- regulate to px_ref / vy_ref -- or a
                       # JSON-serialisable spec {"kind": "table" | "serpentine", ...}; fp64 only
-                      "reference_schedule": None}
+                      "reference_schedule": None,
+                      # what makes the rollout's built-in plant differ from the prediction model (plant.py): None -- the nominal
+                      # plant -- or a JSON-serialisable spec {"wcv_scale": ..., "input_disturbance": ..., "measurement_noise": ...};
+                      # fp64 only
+                      "plant_perturbation": None}
 # codes of the parameter record (include/mpcbatch.h [7]); RK4 = 0 keeps default records unchanged
 PLANT_INTEGRATORS = {"RK4": 0, "Euler": 1, "RK2": 2, "RK3": 3}
 
@@ -262,8 +266,18 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
         # (the number of rows of a table, and everything else, against this run's Nsim + N)
         reference.sample({"reference_schedule": schedule, "Nsim": Nsim, "N": N, "dt": dt, "px_ref": float(cfg["px_ref"]),
                           "vy_ref": float(cfg["vy_ref"])})
+    perturbation = cfg["plant_perturbation"]
+    if perturbation is not None:
+        from . import plant
+
+        if cfg["riccati_precision"] == "fp32":
+            raise ValueError("a plant_perturbation is offered with riccati_precision='fp64' only")
+        plant.validate(perturbation)
+        perturbation = copy.deepcopy(dict(perturbation))
+        # (the number of rows of a table against this run's Nsim)
+        plant.sample({"plant_perturbation": perturbation, "Nsim": Nsim, "dt": dt, "wcv": wcv})
     return {
-        "reference_schedule": schedule,
+        "reference_schedule": schedule, "plant_perturbation": perturbation,
         "robot_name": cfg["robot_name"], "urdf_path": cfg["urdf_path"], "ee_frame": cfg["ee_frame"],
         "N": N, "Nsim": Nsim, "dt": dt,
         "solver_type": SOLVER_RTI if so["nlp_solver_type"] == "SQP_RTI" else SOLVER_SQP,

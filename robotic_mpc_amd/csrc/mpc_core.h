@@ -3183,10 +3183,20 @@ struct Engine {
     // the fast path's right-hand side, which the closing pass therefore does not form), its cost and residual norms are those of the
     // new iterate against that window, and log column t measures the task errors against schedule row t.  Everything else carries as
     // without a schedule; there is no shift.
+    // PERT (with REF; the kernels of mpcb_rollout_pert, mpc_rollout_pert.hip): the built-in plant is not the model -- `pert` holds
+    // this simulation's plant bandwidths, input disturbance and measurement noise (each may be null).  TRUE state and FEEDBACK state
+    // part ways: sm.xhat is what the solve sees, z_t + x_noise[t]; the true z_t stays in sm.logv[24..35] from one plant step to the
+    // next (no pass of a REF step touches those: the in-pass plant lane and the fast path's right-hand side are off), the plant
+    // step starts from it, with u_t + u_dist[t] and the plant's bandwidths, and the log is taken while sm.xhat still equals the new
+    // true state -- the noise of step t + 1 is added after it, and only when step t + 1 runs in this launch: across a launch
+    // boundary w.state[ST_Z] carries the truth, and the entry adds x_noise[step0].  Step t is control_step (nlp_step<false>), its
+    // plant step follows the solve.
     struct NoSched {};
-    template <bool REF = false>
-    MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {})
+    template <bool REF = false, bool PERT = false>
+    MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {},
+                        typename std::conditional<PERT, PlantPert, NoSched>::type pert = {})
     {
+        static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
         Ws &w = c.w;
@@ -3204,6 +3214,16 @@ struct Engine {
             });
             load_carry(lin_valid);
         }
+        if constexpr (PERT) {
+            // sm.xhat holds the true z_{step0}: keep it, and form the feedback state of the first step of this launch
+            ex.par([&](int lane) {
+                if (lane < NX) {
+                    const double zt = sm.xhat[lane];
+                    sm.logv[24 + lane] = zt;
+                    if (pert.x_noise) sm.xhat[lane] = zt + pert.x_noise[(size_t)step0 * NX + lane];
+                }
+            });
+        }
         TaskRef ref{nullptr};                       // (REF) the window of step i
         const auto lin = [&](double alpha, bool do_update, bool sqp_mult, double *r4, bool do_plant, bool fuse_commit, bool want_rhs) {
             if constexpr (REF) return nlp_direct<true, true>(alpha, do_update, sqp_mult, r4, do_plant, fuse_commit, false, ref);
@@ -3213,6 +3233,10 @@ struct Engine {
             if constexpr (REF) return line_search<true>(sqp_iter, ref);
             else return line_search(sqp_iter);
         };
+        typename std::conditional<PERT, typename Ex::template PerLane<double>, NoSched>::type wc_plant;   // (PERT) the plant's bandwidth of this lane's joint, in a register
+        if constexpr (PERT) ex.wpar([&](int lane) {
+            wc_plant.at(lane) = lane < 6 ? (pert.wcv ? pert.wcv[lane] : P.wcv[lane]) : 0.0;
+        });
         for (int i = step0; i < step1; i++) {
             int sqp_iter = 0, qp_iter = 0;
             double res4[4] = {0, 0, 0, 0}, cost = 0.0;
@@ -3222,11 +3246,24 @@ struct Engine {
                 ref = TaskRef{sched + (size_t)i * NTASK};
                 lin_valid = false;
             }
-            const int status = nlp_step<true>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
+            const int status = nlp_step<!PERT>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
             const double t1 = ex.clock();
             PROF_T0(tp);
             // u = solver.get(0,'u'); RK4 plant step (simulation_model.py:111-117) -- unless the last NLP pass has done it
             ex.par([&](int lane) {
+                if constexpr (PERT) {
+                    // the perturbed plant: from the TRUE state, with the disturbed input; u0 logs the commanded one
+                    if (lane < 6) {
+                        const int j = lane;
+                        const double u = w.G1[O_U + j];
+                        const double ud = pert.u_dist ? u + pert.u_dist[(size_t)i * NU + j] : u;
+                        double qn, vn;
+                        nlp::plant_rk(P, wc_plant.at(lane), sm.logv[24 + j], sm.logv[30 + j], ud, qn, vn);
+                        sm.logv[24 + j] = qn;
+                        sm.logv[30 + j] = vn;
+                        sm.u0[j] = u;
+                    }
+                } else
                 if (lane < 6 && !plant_done) {
                     const int j = lane;
                     const double u = w.G1[O_U + j];
@@ -3247,6 +3284,12 @@ struct Engine {
             });
             if constexpr (REF) log_lo = ex.uni(log_state<true>(out, inst, i + 1, log_lo, plant_done, sched + (size_t)(i + 1) * NTASK));
             else log_lo = ex.uni(log_state(out, inst, i + 1, log_lo, plant_done));
+            if constexpr (PERT) {
+                // the feedback state of step i + 1, when this launch runs it (no row Nsim exists; the next launch forms its own)
+                if (i + 1 < step1 && pert.x_noise) ex.par([&](int lane) {
+                    if (lane < NX) sm.xhat[lane] += pert.x_noise[(size_t)(i + 1) * NX + lane];
+                });
+            }
             const double t2 = ex.clock();
             // plant_time: what is left of it here + the plant lane's own time inside the NLP pass
             ex.par([&](int lane) { if (lane == 0) out.plant_time[sb + i] = (t2 - t1) + (plant_done ? sm.ret[6] : 0.0); });

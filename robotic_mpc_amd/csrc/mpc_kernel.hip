@@ -78,6 +78,15 @@ void launch_rollout_ref(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipSt
 void launch_stream_rollout_ref(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
                                size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
                                long long timeout_ticks, const double *yref_sched);
+// ... and those of the rollout over a perturbed plant (mpcb_rollout_pert): mpc_rollout_pert.hip, mpc_stream_rollout_pert.hip
+const void *rollout_pert_kernel(int waves_per_sim, int wpe);
+const void *stream_rollout_pert_kernel();
+void launch_rollout_pert(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                         const InstParams *params, double *ws_base, size_t ws_stride, const Outputs &out, int step0, int step1,
+                         int pool_doubles, const double *yref_sched, const PlantPert &pert);
+void launch_stream_rollout_pert(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                                size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
+                                long long timeout_ticks, const double *yref_sched, const PlantPert &pert);
 }  // namespace mpcb
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
@@ -270,6 +279,7 @@ struct mpcb_handle {
     int *d_queue = nullptr;    // throughput engine, work-queue launches: counter, error flag, per-simulation progress
     size_t queue_cap = 0;
     bool queue_used = false;   // the last launch went through the work queue (mpcb_sync checks its error flag)
+    bool pert_used = false;    // the last rollout launch was a perturbed one (mpcb_kernel_info reports its kernel)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t last_stream = nullptr;
     bool timed = false;
@@ -511,6 +521,7 @@ static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *param
     }
     h->ready = true;
     h->next_step = 0;
+    h->pert_used = false;
     h->timed = false;
     h->controller = controller;
     h->reset_next = true;
@@ -551,11 +562,12 @@ static const void *latency_kernel(const mpcb_handle *h)
 // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
 // handle can ask for, right before the launch
 // (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens, 3 of mpcb_step_sens_w, 4 / 5 of
-// mpcb_step_term without / with sens, 6 of mpcb_rollout_ref)
+// mpcb_step_term without / with sens, 6 of mpcb_rollout_ref, 7 of mpcb_rollout_pert)
 static int raise_lds_limit(mpcb_handle *h, int step = 0)
 {
     static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(step == 6 ? rollout_ref_kernel(h->waves_per_sim, h->wpe)
+    HIPCHK(h, hipFuncSetAttribute(step == 7 ? rollout_pert_kernel(h->waves_per_sim, h->wpe)
+                                  : step == 6 ? rollout_ref_kernel(h->waves_per_sim, h->wpe)
                                   : step == 5 ? step_term_sens_kernel(h->waves_per_sim, h->wpe)
                                   : step == 4 ? step_term_kernel(h->waves_per_sim, h->wpe)
                                   : step == 3 ? step_sensw_kernel(h->waves_per_sim, h->wpe)
@@ -587,11 +599,25 @@ int mpcb_rollout(mpcb_handle *h, int step0, int step1, const mpcb_result *o, voi
 // argument differ)
 int mpcb_rollout_ref(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, void *stream)
 {
+    return mpcb_rollout_pert(h, step0, step1, o, yref_sched, nullptr, stream);
+}
+
+// (pert == NULL: the kernels above, chosen by yref_sched; otherwise those of the perturbed rollout, mpc_rollout_pert.hip /
+// mpc_stream_rollout_pert.hip, through the same launch path with one argument more)
+int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                      void *stream)
+{
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
     if (h->controller) return fail(h, MPCB_ESTATE, "mpcb_rollout on a controller handle (mpcb_setup_controller): use mpcb_step");
     if (yref_sched && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
         return fail(h, MPCB_EINVAL, "mpcb_rollout_ref: a reference schedule is offered in fp64 only (no fp32 Riccati leg)");
+    if (pert_ && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_pert: a perturbed plant is offered in fp64 only (no fp32 Riccati leg)");
+    if (pert_ && !yref_sched)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_pert: a perturbed rollout needs a reference schedule (the packed rows when there is none)");
+    PlantPert pert{nullptr, nullptr, nullptr};
+    if (pert_) pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -631,7 +657,11 @@ int mpcb_rollout_ref(mpcb_handle *h, int step0, int step1, const mpcb_result *o,
         const long long qticks = queue_timeout_ticks(h->pb, chunk);
         HIPCHK(h, hipEventRecord(h->ev0, s));
         const dim3 sgrid((unsigned)(queued ? nslots : h->pb.batch));
-        if (yref_sched)
+        h->pert_used = pert_ != nullptr;
+        if (pert_)
+            launch_stream_rollout_pert(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
+                                       yref_sched, pert);
+        else if (yref_sched)
             launch_stream_rollout_ref(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
                                       yref_sched);
         else if (h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
@@ -648,10 +678,14 @@ int mpcb_rollout_ref(mpcb_handle *h, int step0, int step1, const mpcb_result *o,
         return MPCB_OK;
     }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    if (int rc = raise_lds_limit(h, yref_sched ? 6 : 0)) return rc;
+    if (int rc = raise_lds_limit(h, pert_ ? 7 : yref_sched ? 6 : 0)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
     const dim3 grid((unsigned)h->pb.batch);
-    if (yref_sched)
+    h->pert_used = pert_ != nullptr;
+    if (pert_)
+        launch_rollout_pert(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
+                            h->pool_doubles, yref_sched, pert);
+    else if (yref_sched)
         launch_rollout_ref(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
                            h->pool_doubles, yref_sched);
     else if (h->waves_per_sim == 8)
@@ -840,6 +874,8 @@ int mpcb_kernel_info(mpcb_handle *h, int *vgprs, int *sgprs, int *lds_bytes, int
     hipFuncAttributes a;
     if (h->engine == 1 && h->controller) {
         HIPCHK(h, hipFuncGetAttributes(&a, stream_step_kernel()));
+    } else if (h->pert_used && !h->controller) {             // (the last rollout launch was mpcb_rollout_pert: its kernel)
+        HIPCHK(h, hipFuncGetAttributes(&a, h->engine == 1 ? stream_rollout_pert_kernel() : rollout_pert_kernel(h->waves_per_sim, h->wpe)));
     } else if (h->engine == 1) {
         HIPCHK(h, hipFuncGetAttributes(&a, h->pb.precision == MPCB_PRECISION_FP32_RICCATI ? (const void *)mpc_stream_kernel<float>
                                                                                           : (const void *)mpc_stream_kernel<double>));

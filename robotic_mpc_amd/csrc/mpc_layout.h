@@ -218,6 +218,20 @@ struct TaskRef {
     const double *y;
 };
 
+// The plant perturbation of ONE simulation in a perturbed rollout (mpcb_plant_pert with the simulation's offsets applied): device
+// pointers, each null = that perturbation off.  Read from global memory by the lanes that use them, during the launch only.
+struct PlantPert {
+    const double *wcv;      // [6]        the plant's bandwidths (the model keeps InstParams::wcv)
+    const double *u_dist;   // [Nsim][6]  added to u_t before the plant step
+    const double *x_noise;  // [Nsim][12] added to z_t to form the feedback state of step t
+};
+// ... of simulation `inst` of a launch (`a`: the three [batch][...] arrays)
+MPC_HD PlantPert plant_pert_of(const PlantPert &a, int inst, int Nsim)
+{
+    return PlantPert{a.wcv ? a.wcv + (size_t)inst * 6 : nullptr, a.u_dist ? a.u_dist + (size_t)inst * Nsim * 6 : nullptr,
+                     a.x_noise ? a.x_noise + (size_t)inst * Nsim * 12 : nullptr};
+}
+
 // One instance's workspace: five stage-major group arrays + persistent scalars.
 struct Ws {
     double *G1, *G2, *G3, *G4, *G5, *PH, *state;

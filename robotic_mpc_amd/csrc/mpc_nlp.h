@@ -39,6 +39,33 @@ MPC_HD void plant_rk(const InstParams &P, int j, double q, double v, double u, d
     }
 }
 
+// The same with the joint's bandwidth given (the perturbed rollout, mpcb_rollout_pert: the plant's `wc` is not the model's P.wcv[j]).
+// The formulas are restated, not shared: the function above keeps its code.
+MPC_HD void plant_rk(const InstParams &P, double wc, double q, double v, double u, double &qn, double &vn)
+{
+    const double dt = P.dt;
+    const int integ = (int)P.integ;
+    const double k1q = v, k1v = -wc * v + wc * u;
+    const double v2 = v + 0.5 * dt * k1v;
+    const double k2q = v2, k2v = -wc * v2 + wc * u;
+    if (integ == 1) {
+        qn = q + dt * k1q; vn = v + dt * k1v;
+    } else if (integ == 2) {
+        qn = q + dt * k2q; vn = v + dt * k2v;
+    } else if (integ == 3) {
+        const double v3 = v - dt * k1v + 2.0 * dt * k2v;
+        const double k3q = v3, k3v = -wc * v3 + wc * u;
+        qn = q + (dt / 6) * (k1q + 4.0 * k2q + k3q); vn = v + (dt / 6) * (k1v + 4.0 * k2v + k3v);
+    } else {
+        const double v3 = v + 0.5 * dt * k2v;
+        const double k3q = v3, k3v = -wc * v3 + wc * u;
+        const double v4 = v + dt * k3v;
+        const double k4q = v4, k4v = -wc * v4 + wc * u;
+        qn = q + (dt / 6) * k1q + (dt / 3) * k2q + (dt / 3) * k3q + (dt / 6) * k4q;
+        vn = v + (dt / 6) * k1v + (dt / 3) * k2v + (dt / 3) * k3v + (dt / 6) * k4v;
+    }
+}
+
 // ---- SQP line search: MERIT_BACKTRACKING (trajectory_optimizer.py:68; acados alpha_reduction, alpha_min) -------------------------
 // trial steps 1, 0.7, 0.49, ... while >= 0.05
 constexpr double LS_REDUCTION = 0.7, LS_ALPHA_MIN = 0.05;

@@ -2263,12 +2263,25 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 // t).  Step i is control_step against the window sched + i * NTASK with ref_changed set, followed by the plant step: it linearises at
 // its start against its own window, and forms its own cost and residual norms against it -- the next step's first pass runs against
 // the next window, so nothing is deferred.  Everything else carries as without a schedule; there is no shift.
-template <class FT, bool REF = false>
+// PERT (with REF; the kernel of mpcb_rollout_pert, mpc_stream_rollout_pert.hip): the built-in plant is not the model -- `pert_` holds this
+// simulation's plant bandwidths, input disturbance and measurement noise (each may be null).  sm.xhat is the FEEDBACK state of the
+// solve, z_t + x_noise[t]; the TRUE z_t stays in sm.logv[24..35] from one plant step to the next (no pass of the step touches those),
+// the plant step starts from it with u_t + u_dist[t] and the plant's bandwidths (a register of the six plant lanes), and the log is
+// taken while sm.xhat still equals the new true state: the noise of step t + 1 is added after it, and only when step t + 1 belongs to
+// this launch or work item -- across a launch boundary and a work-queue hand-off w.state[ST_Z] carries the truth, and the entry adds
+// x_noise[step0].
+template <class FT, bool REF = false, bool PERT = false>
 SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
-                    const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched_ = {})
+                    const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched_ = {},
+                    typename std::conditional<PERT, PlantPert, NoSched>::type pert_ = {})
 {
+    static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
     const double *sched = nullptr;
     if constexpr (REF) sched = uni_ref(TaskRef{sched_}).y;
+    const double *p_wcv = nullptr, *p_ud = nullptr, *p_xn = nullptr;
+    if constexpr (PERT) {
+        p_wcv = uni_ref(TaskRef{pert_.wcv}).y; p_ud = uni_ref(TaskRef{pert_.u_dist}).y; p_xn = uni_ref(TaskRef{pert_.x_noise}).y;
+    }
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
     const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), Nsim = pb.Nsim, T1 = Nsim + 1;
@@ -2287,6 +2300,18 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
     } else {
         if (lane < NX) sm.xhat[lane] = w.state[ST_Z + lane];
         c.load(w.state);
+        fence();
+    }
+    double wc_plant = 0.0;              // (PERT) the plant's bandwidth of this lane's joint
+    if constexpr (PERT) {
+        // sm.xhat holds the true z_{step0}: keep it, and form the feedback state of the first step of this launch / work item
+        fence();
+        if (lane < NX) {
+            const double zt = sm.xhat[lane];
+            sm.logv[24 + lane] = zt;
+            if (p_xn) sm.xhat[lane] = zt + p_xn[(size_t)step0 * NX + lane];
+        }
+        if (lane < 6) wc_plant = p_wcv ? p_wcv[lane] : P.wcv[lane];
         fence();
     }
     const auto lin = [](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass(alpha, do_update, sqp_mult, slot); };
@@ -2314,6 +2339,19 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if (lane == 0) { w.state[ST_PROF + 6] += t1 - t0; }
 #endif
         // u = solver.get(0,'u'); plant step (simulation_model.py:93-117)
+        if constexpr (PERT) {
+            // the perturbed plant: from the TRUE state, with the disturbed input; u0 logs the commanded one
+            if (lane < 6) {
+                const int j = lane;
+                const double u = w.G1[O_U + j];
+                const double ud = p_ud ? u + p_ud[(size_t)i * NU + j] : u;
+                double qn, vn;
+                nlp::plant_rk(P, wc_plant, sm.logv[24 + j], sm.logv[30 + j], ud, qn, vn);
+                sm.logv[24 + j] = qn;
+                sm.logv[30 + j] = vn;
+                sm.u0[j] = u;
+            }
+        } else
         if (lane < 6) {
             const int j = lane;
             const double u = w.G1[O_U + j];
@@ -2330,6 +2368,12 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         fence();
         if constexpr (REF) log_lo = uni(log_state<true>(out, inst, T1, i + 1, log_lo, sched + (size_t)(i + 1) * NTASK));
         else log_lo = uni(log_state(out, inst, T1, i + 1, log_lo));
+        if constexpr (PERT) {
+            // the feedback state of step i + 1, when this launch / work item runs it (no row Nsim exists; the next one forms its own)
+            fence();
+            if (i + 1 < step1 && p_xn && lane < NX) sm.xhat[lane] += p_xn[(size_t)(i + 1) * NX + lane];
+            fence();
+        }
         const double t2 = wclock();
         if (lane == 0) out.plant_time[sbase + i] = t2 - t1;
 #ifdef MPCB_SPROF

@@ -78,6 +78,11 @@ class EngineError(RuntimeError):
     pass
 
 
+class MpcbPlantPert(C.Structure):
+    """mpcb_plant_pert (include/mpcbatch.h): device pointers, each may be NULL."""
+    _fields_ = [("wcv", C.POINTER(C.c_double)), ("u_dist", C.POINTER(C.c_double)), ("x_noise", C.POINTER(C.c_double))]
+
+
 class MpcbStepSensOut(C.Structure):
     """mpcb_step_sens_out (include/mpcbatch.h): device pointers."""
     _fields_ = [("du0_dx", C.POINTER(C.c_double)), ("du0_dyref", C.POINTER(C.c_double)), ("valid", C.POINTER(C.c_int))]
@@ -88,7 +93,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
             "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
-            "mpcb_rollout_ref", "mpcb_queue_used")
+            "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -123,6 +128,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_setup.argtypes = [C.c_void_p, C.POINTER(MpcbProblem), _dp, _dp]
     lib.mpcb_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), C.c_void_p]
     lib.mpcb_rollout_ref.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.c_void_p]
+    lib.mpcb_rollout_pert.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), C.c_void_p]
     lib.mpcb_queue_used.argtypes = [C.c_void_p]
     lib.mpcb_sync.argtypes = [C.c_void_p]
     lib.mpcb_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
@@ -263,10 +269,15 @@ class MpcBatchEngine:
             setattr(r, name, C.cast(C.c_void_p(ptr), _dp if ty == "f8" else _ip))
         return r
 
-    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None):
+    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None):
         """Asynchronous launch of closed-loop steps [step0, step1) into device buffers.  `yref`: the task reference schedules of
         the batch, a contiguous float64 device tensor [batch, Nsim + N, 5] (N the longest horizon; schedule_tensor) -- the same one
-        for every launch of a run -- or None for the packed references (mpcb_rollout)."""
+        for every launch of a run -- or None for the packed references (mpcb_rollout).  `pert`: the plant perturbation of the
+        batch (mpcb_rollout_pert; perturbation_tensors), a dict of contiguous float64 device tensors "wcv" [batch, 6], "u_dist"
+        [batch, Nsim, 6], "x_noise" [batch, Nsim, 12], each may be missing or None -- the same ones for every launch of a run; it
+        needs `yref` (schedule_tensor supplies the packed rows when the configurations carry no schedule)."""
+        if pert is not None:
+            return self._rollout_pert(bufs, step0, step1, yref, pert, stream)
         if stream is None:
             import torch
 
@@ -275,11 +286,52 @@ class MpcBatchEngine:
         if yref is None:
             self._check(self.lib.mpcb_rollout(self._h, step0, step1, C.byref(r), C.c_void_p(stream)), "mpcb_rollout")
             return
+        self._check_yref(yref)
+        self._check(self.lib.mpcb_rollout_ref(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp),
+                                              C.c_void_p(stream)), "mpcb_rollout_ref")
+
+    def _check_yref(self, yref):
         pb = self._pb
         if tuple(yref.shape) != (pb.batch, pb.Nsim + pb.N, 5) or not yref.is_contiguous() or str(yref.dtype) != "torch.float64":
             raise ValueError(f"yref must be a contiguous float64 tensor [{pb.batch}, {pb.Nsim + pb.N}, 5], got {tuple(yref.shape)} {yref.dtype}")
-        self._check(self.lib.mpcb_rollout_ref(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp),
-                                              C.c_void_p(stream)), "mpcb_rollout_ref")
+
+    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream):
+        """rollout(pert=): every shape is checked before the library is called."""
+        pb = self._pb
+        shapes = {"wcv": (pb.batch, 6), "u_dist": (pb.batch, pb.Nsim, 6), "x_noise": (pb.batch, pb.Nsim, 12)}
+        extra = set(pert) - set(shapes)
+        if extra:
+            raise ValueError(f"pert has the keys {tuple(shapes)} (got {sorted(pert)})")
+        if yref is None:
+            raise ValueError("a perturbed rollout needs yref: schedule_tensor(cfgs) supplies the packed rows when there is no schedule")
+        self._check_yref(yref)
+        p = MpcbPlantPert()
+        for name, shape in shapes.items():
+            t = pert.get(name)
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or not t.is_contiguous() or str(t.dtype) != "torch.float64" or not t.is_cuda:
+                raise ValueError(f"pert[{name!r}] must be a contiguous float64 device tensor {list(shape)}, got {tuple(t.shape)} {t.dtype}")
+            setattr(p, name, C.cast(C.c_void_p(t.data_ptr()), _dp))
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._result_struct(bufs)
+        self._check(self.lib.mpcb_rollout_pert(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
+                                               C.c_void_p(stream)), "mpcb_rollout_pert")
+
+    def perturbation_tensors(self, cfgs: Sequence[Dict]):
+        """The plant perturbations of a bucket (plant.stack) on this engine's device -- {"wcv", "u_dist", "x_noise"} -- or None when
+        the configurations carry none (a bucket is all or nothing: packing.bucket_key)."""
+        if not any(c.get("plant_perturbation") is not None for c in cfgs):
+            return None
+        import torch
+
+        from . import plant
+
+        dev = torch.device("cuda", self.device)
+        return {k: torch.from_numpy(v).to(dev) for k, v in plant.stack(cfgs).items()}
 
     def queue_used(self) -> bool:
         """Whether the last rollout launch went through the throughput engine's work queue (mpcb_queue_used)."""
@@ -290,12 +342,19 @@ class MpcBatchEngine:
 
     def schedule_tensor(self, cfgs: Sequence[Dict]):
         """The reference schedules of a bucket (reference.stack) on this engine's device, or None when the configurations carry
-        none (a bucket is all or nothing: packing.bucket_key)."""
-        if not any(c.get("reference_schedule") is not None for c in cfgs):
-            return None
-        import torch
-
+        none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation: the perturbed rollout
+        always tracks a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
         from . import reference
+
+        if not any(c.get("reference_schedule") is not None for c in cfgs):
+            if not any(c.get("plant_perturbation") is not None for c in cfgs):
+                return None
+            import torch
+
+            rows = int(cfgs[0]["Nsim"]) + max(int(c["N"]) for c in cfgs)
+            packed = np.stack([reference.packed_rows(c, rows) for c in cfgs])
+            return torch.from_numpy(np.ascontiguousarray(packed)).to(torch.device("cuda", self.device))
+        import torch
 
         return torch.from_numpy(reference.stack(cfgs)).to(torch.device("cuda", self.device))
 
@@ -444,10 +503,11 @@ class MpcBatchEngine:
         pb = self.setup(cfgs, chain)
         bufs = self.alloc_results(pb)
         yref = self.schedule_tensor(cfgs)      # sampled and stacked once; every chunk gets the same array
+        pert = self.perturbation_tensors(cfgs)
         chunk = step_chunk if step_chunk and step_chunk > 0 else pb.Nsim
         self.last_kernel_ms = []
         for s0 in range(0, pb.Nsim, chunk):
-            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref)
+            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert)
             self.sync()
             self.last_kernel_ms.append(self.kernel_ms())
         return pb, bufs
@@ -460,9 +520,11 @@ class MpcBatchEngine:
     # ------------------------------------------------------------------ host-buffer path
     def run_host_buffers(self, cfgs: Sequence[Dict], chain) -> Dict[str, np.ndarray]:
         """Same through mpcb_run (library-owned device buffers, numpy in/out, no torch).  mpcb_run takes no reference schedule:
-        configurations that carry one are refused."""
+        configurations that carry one are refused, and so are configurations with a plant perturbation."""
         if any(c.get("reference_schedule") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no reference schedule: run configurations with a reference_schedule through run() / run_device()")
+        if any(c.get("plant_perturbation") is not None for c in cfgs):
+            raise ValueError("mpcb_run takes no plant perturbation: run configurations with a plant_perturbation through run() / run_device()")
         pb = make_problem(cfgs)
         params = packing.pack_batch(cfgs)
         robot = np.ascontiguousarray(chain.packed(cfgs[0]["t_ee"]), dtype=np.float64)

@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import analysis, config as cfgmod, packing, reference, robots
+from . import analysis, config as cfgmod, packing, plant, reference, robots
 
 
 def chain_for(cfg: Dict) -> robots.KinematicChain:
@@ -210,6 +210,7 @@ class Simulator:
         rows = reference.log_rows(self.resolved)
         if rows is not None:
             data["reference_schedule"] = rows      # [Nsim + 1, 5]: the targets in force at every logged column
+        data.update(plant.realised(self.resolved))  # "input_disturbance" [Nsim, 6] / "measurement_noise" [Nsim, 12] when configured
         return data
 
     def get_analysis(self):
@@ -318,9 +319,10 @@ class _EngineRunner:
         with torch.cuda.stream(stream):
             bufs = eng.alloc_results(pb)
             yref = eng.schedule_tensor(cfgs)   # the bucket's reference schedules, or None (kept alive by the ticket)
-            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream)
+            pert = eng.perturbation_tensors(cfgs)   # ... and its plant perturbations, or None (likewise)
+            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert)
             summary = eng.summary(bufs, stream=stream.cuda_stream)
-        return eng, stream, bufs, summary, yref
+        return eng, stream, bufs, summary, (yref, pert)
 
     def collect(self, ticket):
         eng, stream, bufs, summary, _yref = ticket
@@ -336,6 +338,15 @@ class _EngineRunner:
         out["summary"] = summary
         out["_kernel_ms"] = ms
         return out
+
+
+def _set_path(config: Dict[str, Any], parts: Sequence[str], val) -> None:
+    """config[parts[0]][parts[1]]...[parts[-1]] = val, every dict on the way copied (the base configuration is not aliased)."""
+    node = config
+    for p in parts[:-1]:
+        node[p] = dict(node.get(p) or {})
+        node = node[p]
+    node[parts[-1]] = val
 
 
 class SimulationManager:
@@ -395,6 +406,9 @@ class SimulationManager:
                 for param_path, val in zip(param_paths, values):
                     if "." in param_path:
                         parts = param_path.split(".")
+                        if len(parts) > 2:      # (e.g. plant_perturbation.measurement_noise.seed: every level copied)
+                            _set_path(config, parts, val)
+                            continue
                         config[parts[0]] = dict(config.get(parts[0]) or {})
                         config[parts[0]][parts[1]] = val
                     else:

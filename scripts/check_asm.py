@@ -20,7 +20,11 @@ STREAM_STEP_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_step
 # REF passes, under budgets of their own below
 ROLLOUT_REF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_ref.hip")
 STREAM_ROLLOUT_REF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_ref.hip")
-SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC)
+# the kernels of the rollout over a perturbed plant (mpcb_rollout_pert; modules of their own): the scheduled rollout's with the PERT
+# plant step, under budgets of their own below
+ROLLOUT_PERT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_pert.hip")
+STREAM_ROLLOUT_PERT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_pert.hip")
+SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC, ROLLOUT_PERT_SRC, STREAM_ROLLOUT_PERT_SRC)
 
 
 def scan(asm_text):
@@ -71,6 +75,10 @@ BUDGET = {
     "21mpc_stream_ref_kernelId": 140,
     "DevExecILi8ELi1EELb0EE10nlp_directILb1ELb1E": 41, "DevExecILi4ELi2EELb0EE10nlp_directILb1ELb1E": 42,
     "DevExecILi4ELi1EELb0EE10nlp_directILb1ELb1E": 8,
+    # the perturbed rollout (recorded: 232 / 300 / 61 for the kernel bodies, 140 for the throughput engine's; its NLP pass is the
+    # scheduled rollout's, 33 / 36 / 2 here without the plant lane's work)
+    "23mpc_rollout_pert_kernelILi8ELi1E": 255, "23mpc_rollout_pert_kernelILi4ELi2E": 330, "23mpc_rollout_pert_kernelILi4ELi1E": 68,
+    "22mpc_stream_pert_kernelId": 154,
 }
 
 
