@@ -421,8 +421,31 @@ int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *o
                       const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
                       void *stream);
 
-/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert launch of this handle went through the throughput engine's work queue, 0: it did
- * not (< 0: error).  Host state only. */
+/* ---- rollouts with the joint-wise terminal cost and a table of terminal references ---- */
+/* mpcb_rollout_pert whose step t closes the horizon of every simulation i with the terminal cost of mpcb_step_term (the QP terms,
+ * the cost and the stationarity rows are described in the comment there):
+ *   l_N(x) = 1/2 (x - term_xref[i][t])' P_i (x - term_xref[i][t])   at the last stage of the simulation's own horizon,
+ * P_i the six 2x2 joint blocks term_blocks[i] = pqq[6] | pqv[6] | pvv[6], constant over the run; row t of term_xref[i] is x_e of step
+ * t, so a tracking task can move the terminal reference with the tool.  It is the closed loop
+ *   u_t = u0 of mpcb_step_term(xhat_t, window t of yref_sched, ref_changed = 1, term = [term_blocks[i] | term_xref[i][t]])
+ * over the plant of mpcb_rollout_pert (pert == NULL: the nominal plant; the same kernels serve both).  A step linearises again at its
+ * start, so a new row needs nothing else: nothing new carries between steps, launches or work-queue items, and there is no shift.
+ * Both arrays are DEVICE pointers read during the launch only, by uniform loads where stage N uses them -- 18 + 12 doubles per step,
+ * no [batch][Nsim][30] table, no workspace, LDS or mpcb_workspace_bytes change; pass the same arrays to every launch of one run.
+ * Keep every block positive semidefinite; nothing is validated.  All-zero blocks are no terminal cost, through these kernels.
+ *
+ * term_blocks == NULL is mpcb_rollout_pert exactly (the same kernels, the same bits; term_xref is then ignored).  MPCB_EINVAL:
+ * term_blocks with MPCB_PRECISION_FP32_RICCATI, on a full-SQP problem, without yref_sched (a run without a schedule passes the
+ * packed row on every row) or without term_xref.  MPCB_ESTATE on a controller handle or before mpcb_setup; the step-range rules of
+ * mpcb_rollout.  Whichever engine mpcb_setup chose runs it, work queue and ragged horizons included; mpcb_queue_used and
+ * mpcb_last_kernel_ms apply, and after such a launch mpcb_kernel_info reports this rollout's kernel. */
+int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
+                      const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
+                      const double *term_blocks /* DEVICE [batch][18] or NULL */,
+                      const double *term_xref /* DEVICE [batch][Nsim][12] */, void *stream);
+
+/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term launch of this handle went through the throughput
+ * engine's work queue, 0: it did not (< 0: error).  Host state only. */
 int mpcb_queue_used(mpcb_handle *h);
 
 #ifdef __cplusplus

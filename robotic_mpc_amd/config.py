@@ -43,7 +43,11 @@ EXTENSION_DEFAULTS = {"translation_ee_t": (0.0, 0.0, 0.1), "urdf_path": None, "e
                       # what makes the rollout's built-in plant differ from the prediction model (plant.py): None -- the nominal
                       # plant -- or a JSON-serialisable spec {"wcv_scale": ..., "input_disturbance": ..., "measurement_noise": ...};
                       # fp64 only
-                      "plant_perturbation": None}
+                      "plant_perturbation": None,
+                      # the joint-wise terminal cost that closes every step's horizon in a rollout (terminal.py): None -- no
+                      # terminal cost -- or a JSON-serialisable spec {"weight": {"kind": "lqr" | "blocks", ...}, "reference":
+                      # {"kind": "constant" | "table", ...}}; SQP_RTI and fp64 only
+                      "terminal_cost": None}
 # codes of the parameter record (include/mpcbatch.h [7]); RK4 = 0 keeps default records unchanged
 PLANT_INTEGRATORS = {"RK4": 0, "Euler": 1, "RK2": 2, "RK3": 3}
 
@@ -276,8 +280,20 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
         perturbation = copy.deepcopy(dict(perturbation))
         # (the number of rows of a table against this run's Nsim)
         plant.sample({"plant_perturbation": perturbation, "Nsim": Nsim, "dt": dt, "wcv": wcv})
+    term = cfg["terminal_cost"]
+    if term is not None:
+        from . import terminal
+
+        if so["nlp_solver_type"] != "SQP_RTI":
+            raise ValueError("a terminal_cost is offered with nlp_solver_type='SQP_RTI' only")
+        if cfg["riccati_precision"] == "fp32":
+            raise ValueError("a terminal_cost is offered with riccati_precision='fp64' only")
+        terminal.validate(term)
+        term = copy.deepcopy(dict(term))
+        # (the number of rows of a table against this run's Nsim; the LQR design against this model)
+        terminal.sample({"terminal_cost": term, "Nsim": Nsim, "dt": dt, "wcv": wcv})
     return {
-        "reference_schedule": schedule, "plant_perturbation": perturbation,
+        "reference_schedule": schedule, "plant_perturbation": perturbation, "terminal_cost": term,
         "robot_name": cfg["robot_name"], "urdf_path": cfg["urdf_path"], "ee_frame": cfg["ee_frame"],
         "N": N, "Nsim": Nsim, "dt": dt,
         "solver_type": SOLVER_RTI if so["nlp_solver_type"] == "SQP_RTI" else SOLVER_SQP,

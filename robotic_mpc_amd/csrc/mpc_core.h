@@ -147,7 +147,10 @@ MPC_HD void load_constants(Ex &ex, const InstParams *P, const Robot *rb)
 
 // TERM (the kernels of mpcb_step_term only): the controller step with the joint-wise terminal cost of mpc_nlp.h term_* -- a compile-time
 // flag of the engine, so that every pass control_step reaches sees it and the engines of all other kernels are the code they were.
-template <class Ex, bool TERM = false>
+// TERM = TERM_TABLE (the kernels of mpcb_rollout_term only, mpc_rollout_term.hip): the same engine for rollout<true, true>, whose
+// record is two arrays -- the simulation's constant blocks, and the row of its table of terminal references that the step reads.
+// An int, not a bool, so that the step's record accessor and with it the kernels of mpcb_step_term stay the code they are.
+template <class Ex, int TERM = 0>
 struct Engine {
     static constexpr int NT = Ex::NT;  // lanes per simulation
     Ex &ex;
@@ -161,8 +164,13 @@ struct Engine {
     bool commit_pending, rhs_valid;
     // TERM: this simulation's terminal-cost record [pqq 6 | pqv 6 | pvv 6 | x_e 12] in the step's device buffer (control_step sets it).
     // Wavefront-uniform and needed at stage N only: the passes read it from there where they use it (TermRec), never through LDS.
+    // TERM_TABLE: `term` is two pointers -- p, the simulation's 18 constant block entries, and x, the 12 of x_e: row t of its reference
+    // table (rollout sets it at every step t).
     struct NoTerm {};
-    typename std::conditional<TERM, const double *, NoTerm>::type term;
+    struct TermPtrs {
+        const double *p, *x;
+    };
+    typename std::conditional<TERM == TERM_TABLE, TermPtrs, typename std::conditional<TERM != 0, const double *, NoTerm>::type>::type term;
 #ifdef MPCB_PROFILE
     double prof[NPROF];
 #endif
@@ -412,9 +420,15 @@ struct Engine {
         const double *p;
         MPC_HD double operator[](int i) const { return gld(p + i); }
     };
-    MPC_HD TermRec term_rec() const
+    // (TERM_TABLE: entry i of the record comes from the blocks' array below TM_XE and from the reference's row from there on)
+    struct TermTabRec {
+        const double *p, *x;
+        MPC_HD double operator[](int i) const { return gld(i < nlp::TM_XE ? p + i : x + (i - nlp::TM_XE)); }
+    };
+    MPC_HD auto term_rec() const
     {
-        if constexpr (TERM) return TermRec{ex.uni(term)};
+        if constexpr (TERM == TERM_TABLE) return TermTabRec{ex.uni(term.p), ex.uni(term.x)};
+        else if constexpr (TERM) return TermRec{ex.uni(term)};
         else return TermRec{nullptr};
     }
 
@@ -657,7 +671,7 @@ struct Engine {
                         for (int i = 0; i < W2_LIN; i++) rec[i] = 0.0;
                         if constexpr (TERM) {
                             // l_N at the terminal state: this lane's stage has no residual of its own
-                            const TermRec tm = term_rec();
+                            const auto tm = term_rec();
                             const double *g1 = G1 + (size_t)k * W1;
 #pragma unroll
                             for (int j = 0; j < 6; j++) csum += nlp::term_cost(tm, j, gld(g1 + O_X + j), gld(g1 + O_X + 6 + j));
@@ -1192,7 +1206,7 @@ struct Engine {
         // diagonal) and its entries e = lane, lane + WAVE of the packed P_N record
         typename Ex::template PerLane<double> tqq, tqv, tvv, tpm[(NPM + WAVE - 1) / WAVE];
         if constexpr (TERM) {
-            const TermRec tm = term_rec();
+            const auto tm = term_rec();
             ex.seq([&](int lane) {
                 const int a = lane < 36 ? lane / 6 : 0, b = lane < 36 ? lane % 6 : 0;
                 const bool dg = lane < 36 && a == b;
@@ -3191,12 +3205,18 @@ struct Engine {
     // true state -- the noise of step t + 1 is added after it, and only when step t + 1 runs in this launch: across a launch
     // boundary w.state[ST_Z] carries the truth, and the entry adds x_noise[step0].  Step t is control_step (nlp_step<false>), its
     // plant step follows the solve.
+    // TERM_TABLE (the engine's flag, with REF and PERT; the kernels of mpcb_rollout_term, mpc_rollout_term.hip): step t's QP is closed by the
+    // joint-wise terminal cost of `tt` -- this simulation's constant blocks, and row t of its reference table as x_e.  The step
+    // linearises again at its start (REF), so the new row needs nothing else, and nothing of it carries to the next step or launch.
     struct NoSched {};
     template <bool REF = false, bool PERT = false>
     MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {},
-                        typename std::conditional<PERT, PlantPert, NoSched>::type pert = {})
+                        typename std::conditional<PERT, PlantPert, NoSched>::type pert = {},
+                        typename std::conditional<TERM == TERM_TABLE, TermTab, NoSched>::type tt = {})
     {
         static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
+        static_assert(!TERM || (TERM == TERM_TABLE && REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
+        if constexpr (TERM == TERM_TABLE) term.p = tt.blocks;
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
         Ws &w = c.w;
@@ -3246,6 +3266,7 @@ struct Engine {
                 ref = TaskRef{sched + (size_t)i * NTASK};
                 lin_valid = false;
             }
+            if constexpr (TERM == TERM_TABLE) term.x = tt.x_ref + (size_t)i * NX;
             const int status = nlp_step<!PERT>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
             const double t1 = ex.clock();
             PROF_T0(tp);
@@ -3409,7 +3430,7 @@ struct Engine {
     // gradient falls by P e_i when x_e,i grows (mpc_nlp.h term_sens) -- two products per entry, by the lanes that hold M_N.
     template <bool SW = false>
     MPC_PASS void sens_pass(double *dx, double *dy, int *valid, bool exact, typename std::conditional<SW, double *, NoDw>::type dw_ = {},
-                            typename std::conditional<TERM, double *, NoDw>::type dxe_ = {})
+                            typename std::conditional<TERM != 0, double *, NoDw>::type dxe_ = {})
     {
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;

@@ -87,6 +87,15 @@ void launch_rollout_pert(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipS
 void launch_stream_rollout_pert(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
                                 size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
                                 long long timeout_ticks, const double *yref_sched, const PlantPert &pert);
+// ... and those of the rollout with the joint-wise terminal cost (mpcb_rollout_term): mpc_rollout_term.hip, mpc_stream_rollout_term.hip
+const void *rollout_term_kernel(int waves_per_sim, int wpe);
+const void *stream_rollout_term_kernel();
+void launch_rollout_term(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
+                         const InstParams *params, double *ws_base, size_t ws_stride, const Outputs &out, int step0, int step1,
+                         int pool_doubles, const double *yref_sched, const PlantPert &pert, const TermTab &term);
+void launch_stream_rollout_term(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
+                                size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
+                                long long timeout_ticks, const double *yref_sched, const PlantPert &pert, const TermTab &term);
 }  // namespace mpcb
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
@@ -280,6 +289,7 @@ struct mpcb_handle {
     size_t queue_cap = 0;
     bool queue_used = false;   // the last launch went through the work queue (mpcb_sync checks its error flag)
     bool pert_used = false;    // the last rollout launch was a perturbed one (mpcb_kernel_info reports its kernel)
+    bool term_used = false;    // ... one with a terminal cost (likewise)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t last_stream = nullptr;
     bool timed = false;
@@ -522,6 +532,7 @@ static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *param
     h->ready = true;
     h->next_step = 0;
     h->pert_used = false;
+    h->term_used = false;
     h->timed = false;
     h->controller = controller;
     h->reset_next = true;
@@ -562,11 +573,12 @@ static const void *latency_kernel(const mpcb_handle *h)
 // the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
 // handle can ask for, right before the launch
 // (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens, 3 of mpcb_step_sens_w, 4 / 5 of
-// mpcb_step_term without / with sens, 6 of mpcb_rollout_ref, 7 of mpcb_rollout_pert)
+// mpcb_step_term without / with sens, 6 of mpcb_rollout_ref, 7 of mpcb_rollout_pert, 8 of mpcb_rollout_term)
 static int raise_lds_limit(mpcb_handle *h, int step = 0)
 {
     static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(step == 7 ? rollout_pert_kernel(h->waves_per_sim, h->wpe)
+    HIPCHK(h, hipFuncSetAttribute(step == 8 ? rollout_term_kernel(h->waves_per_sim, h->wpe)
+                                  : step == 7 ? rollout_pert_kernel(h->waves_per_sim, h->wpe)
                                   : step == 6 ? rollout_ref_kernel(h->waves_per_sim, h->wpe)
                                   : step == 5 ? step_term_sens_kernel(h->waves_per_sim, h->wpe)
                                   : step == 4 ? step_term_kernel(h->waves_per_sim, h->wpe)
@@ -607,6 +619,15 @@ int mpcb_rollout_ref(mpcb_handle *h, int step0, int step1, const mpcb_result *o,
 int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
                       void *stream)
 {
+    return mpcb_rollout_term(h, step0, step1, o, yref_sched, pert_, nullptr, nullptr, stream);
+}
+
+// (term_blocks == NULL: the kernels above, chosen by pert and yref_sched; otherwise those of the rollout with a terminal cost,
+// mpc_rollout_term.hip / mpc_stream_rollout_term.hip, through the same launch path with one argument more -- a null pert is the
+// nominal plant inside them)
+int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                      const double *term_blocks, const double *term_xref, void *stream)
+{
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
     if (h->controller) return fail(h, MPCB_ESTATE, "mpcb_rollout on a controller handle (mpcb_setup_controller): use mpcb_step");
@@ -616,8 +637,17 @@ int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *o
         return fail(h, MPCB_EINVAL, "mpcb_rollout_pert: a perturbed plant is offered in fp64 only (no fp32 Riccati leg)");
     if (pert_ && !yref_sched)
         return fail(h, MPCB_EINVAL, "mpcb_rollout_pert: a perturbed rollout needs a reference schedule (the packed rows when there is none)");
+    if (term_blocks && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_term: a terminal cost is offered in fp64 only (no fp32 Riccati leg)");
+    if (term_blocks && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_term: a terminal cost is offered with SQP_RTI only");
+    if (term_blocks && !yref_sched)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_term: a rollout with a terminal cost needs a reference schedule (the packed rows when there is none)");
+    if (term_blocks && !term_xref)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_term: term_blocks needs term_xref, the table of terminal references");
     PlantPert pert{nullptr, nullptr, nullptr};
     if (pert_) pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
+    const TermTab term{term_blocks, term_xref};
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -658,7 +688,11 @@ int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *o
         HIPCHK(h, hipEventRecord(h->ev0, s));
         const dim3 sgrid((unsigned)(queued ? nslots : h->pb.batch));
         h->pert_used = pert_ != nullptr;
-        if (pert_)
+        h->term_used = term_blocks != nullptr;
+        if (term_blocks)
+            launch_stream_rollout_term(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
+                                       yref_sched, pert, term);
+        else if (pert_)
             launch_stream_rollout_pert(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
                                        yref_sched, pert);
         else if (yref_sched)
@@ -678,11 +712,15 @@ int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *o
         return MPCB_OK;
     }
     const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    if (int rc = raise_lds_limit(h, pert_ ? 7 : yref_sched ? 6 : 0)) return rc;
+    if (int rc = raise_lds_limit(h, term_blocks ? 8 : pert_ ? 7 : yref_sched ? 6 : 0)) return rc;
     HIPCHK(h, hipEventRecord(h->ev0, s));
     const dim3 grid((unsigned)h->pb.batch);
     h->pert_used = pert_ != nullptr;
-    if (pert_)
+    h->term_used = term_blocks != nullptr;
+    if (term_blocks)
+        launch_rollout_term(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
+                            h->pool_doubles, yref_sched, pert, term);
+    else if (pert_)
         launch_rollout_pert(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
                             h->pool_doubles, yref_sched, pert);
     else if (yref_sched)
@@ -874,6 +912,8 @@ int mpcb_kernel_info(mpcb_handle *h, int *vgprs, int *sgprs, int *lds_bytes, int
     hipFuncAttributes a;
     if (h->engine == 1 && h->controller) {
         HIPCHK(h, hipFuncGetAttributes(&a, stream_step_kernel()));
+    } else if (h->term_used && !h->controller) {             // (the last rollout launch was mpcb_rollout_term with blocks: its kernel)
+        HIPCHK(h, hipFuncGetAttributes(&a, h->engine == 1 ? stream_rollout_term_kernel() : rollout_term_kernel(h->waves_per_sim, h->wpe)));
     } else if (h->pert_used && !h->controller) {             // (the last rollout launch was mpcb_rollout_pert: its kernel)
         HIPCHK(h, hipFuncGetAttributes(&a, h->engine == 1 ? stream_rollout_pert_kernel() : rollout_pert_kernel(h->waves_per_sim, h->wpe)));
     } else if (h->engine == 1) {

@@ -232,6 +232,21 @@ MPC_HD PlantPert plant_pert_of(const PlantPert &a, int inst, int Nsim)
                      a.x_noise ? a.x_noise + (size_t)inst * Nsim * 12 : nullptr};
 }
 
+// Value of the engines' TERM flag in the kernels of mpcb_rollout_term: the terminal-cost record is two arrays (1, or true: the one
+// record of mpcb_step_term).
+constexpr int TERM_TABLE = 2;
+// The terminal cost of ONE simulation in a rollout (mpcb_rollout_term; the simulation's offsets applied): its constant joint blocks
+// [pqq 6 | pqv 6 | pvv 6] and its table of terminal references, row t = x_e of step t.  Device pointers, read during the launch only.
+struct TermTab {
+    const double *blocks;   // [18]
+    const double *x_ref;    // [Nsim][12]
+};
+// ... of simulation `inst` of a launch (`a`: the two [batch][...] arrays)
+MPC_HD TermTab term_tab_of(const TermTab &a, int inst, int Nsim)
+{
+    return TermTab{a.blocks + (size_t)inst * 18, a.x_ref + (size_t)inst * Nsim * 12};
+}
+
 // One instance's workspace: five stage-major group arrays + persistent scalars.
 struct Ws {
     double *G1, *G2, *G3, *G4, *G5, *PH, *state;

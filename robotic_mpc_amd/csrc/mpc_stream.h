@@ -334,20 +334,34 @@ SE_DEV void sweep(Bundle<NI, BI> &bin, int N, int lane, F &&body)
 // flag of control_step and of every pass it reaches that sees stage N's cost; this simulation's record [pqq 6 | pqv 6 | pvv 6 | x_e 12]
 // travels with it as an argument -- an empty struct, no register, in every other kernel.  The record is wavefront-uniform and needed
 // at stage N only: the passes read it from the step's device buffer where they use it (TermRec), never through LDS.
-template <bool TERM>
+// TERM = TERM_TABLE (the kernel of mpcb_rollout_term only): the record is two arrays -- `p` the simulation's 18 constant block entries,
+// `x` the 12 of x_e, the row of its table of terminal references that the step reads (TermTabRec).  An int, not a bool, so that the
+// step's argument and accessor, and with them the kernels of mpcb_step_term, stay the code they are.
+template <int TERM>
 struct TermArg {};
 template <>
-struct TermArg<true> {
+struct TermArg<1> {
     const double *p;
+};
+template <>
+struct TermArg<TERM_TABLE> {
+    const double *p, *x;
 };
 struct TermRec {
     const MPC_GLOBAL double *p;
     SE_DEV double operator[](int i) const { return p[i]; }
 };
-template <bool TERM>
-SE_DEV TermRec term_rec(TermArg<TERM> t)
+// (entry i of the record: the blocks' array below TM_XE, the reference's row from there on)
+struct TermTabRec {
+    const MPC_GLOBAL double *p, *x;
+    SE_DEV double operator[](int i) const { return i < nlp::TM_XE ? p[i] : x[i - nlp::TM_XE]; }
+};
+template <int TERM>
+SE_DEV auto term_rec(TermArg<TERM> t)
 {
-    if constexpr (TERM) return TermRec{(const MPC_GLOBAL double *)uni_ref(TaskRef{t.p}).y};
+    if constexpr (TERM == TERM_TABLE)
+        return TermTabRec{(const MPC_GLOBAL double *)uni_ref(TaskRef{t.p}).y, (const MPC_GLOBAL double *)uni_ref(TaskRef{t.x}).y};
+    else if constexpr (TERM) return TermRec{(const MPC_GLOBAL double *)uni_ref(TaskRef{t.p}).y};
     else return TermRec{nullptr};
 }
 
@@ -402,7 +416,7 @@ struct IpmNorms {
 // multiplier step stored with stage k+1; pi_{k-1} travels in LDS from the previous iteration.
 //   in  : G1 row | G3 [DW..DT] | G2 [R..GV]            (234 doubles)
 //   out : G1 [QW..QT] | G2 [R,Y] | G2 [GAM|GT|RB] | G3 [RG|RD|RM]   (196 doubles)
-template <int MODE, bool TERM = false>
+template <int MODE, int TERM = 0>
 SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {})
 {
     static_assert(MODE == 0 || MODE == 1, "warm start or Newton step");
@@ -671,7 +685,7 @@ SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {})
 // three phases U | Y | S,D and the same arithmetic per element).  ~17 batches of loads per pass instead of 101 stages of chain;
 // while a batch is in flight the SIMD's other simulation runs.  y of every stage waits in the (idle) ring between Y and S.
 // (residual_items_ok: beside RING_DOUBLES above)
-template <bool TERM = false>
+template <int TERM = 0>
 SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {})
 {
     SSmem &sm = g_ssm;
@@ -948,7 +962,7 @@ SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {})
 // (an accepted fast-path candidate that has become the iterate by a flip of the index, fast_commit / ipm_solve).
 // TERM: stage N's joint items take the terminal cost -- its term of the cost, P (X_N - x_e) in the stationarity rows and in the
 // right-hand side's gt (mpc_nlp.h term_*).
-template <bool NORMS, bool RHS, bool SQPM = false, bool TERM = false>
+template <bool NORMS, bool RHS, bool SQPM = false, int TERM = 0>
 SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = {})
 {
     SSmem &sm = g_ssm;
@@ -1010,7 +1024,7 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = 
                 double tgq = 0.0, tgv = 0.0;
                 if constexpr (TERM) {
                     if (k == N) {
-                        const TermRec tr = term_rec(tm);
+                        const auto tr = term_rec(tm);
                         nlp::term_grad(tr, j, qj, vj, tgq, tgv);
                         if (NORMS) csum += nlp::term_cost(tr, j, qj, vj);
                     }
@@ -1137,7 +1151,7 @@ struct FactLane {
 
 // FASTF (fast path): the record goes out without its tail [w | R~^-1] -- only the corrector reads that (48 of 232 scalars).
 // TERM: the recursion starts from P_N = lm I + P, the joint blocks of the terminal weight (mpc_nlp.h term_hess).
-template <class FT, bool FASTF = false, bool TERM = false>
+template <class FT, bool FASTF = false, int TERM = 0>
 SE_PASS void fact_pass(TermArg<TERM> tm = {})
 {
     SSmem &sm = g_ssm;
@@ -1211,7 +1225,7 @@ SE_PASS void fact_pass(TermArg<TERM> tm = {})
             // terminal stage: no cost, no bounds -> P_N = lm I ; p_N = gt_x ; R~, S~ of stage N-1
             if constexpr (TERM) {
                 // every entry of the P_N record written once, by one lane, with its value; the rest of the row zero
-                const TermRec tr = term_rec(tm);
+                const auto tr = term_rec(tm);
                 double hqq[6], hqv[6], hvv[6];
 #pragma unroll
                 for (int i = 0; i < 6; i++) { hqq[i] = nlp::term_hess(tr, i, i); hqv[i] = nlp::term_hess(tr, i, 6 + i); hvv[i] = nlp::term_hess(tr, 6 + i, 6 + i); }
@@ -1754,7 +1768,7 @@ SE_PASS void fast_commit(bool embed_x0)
 // `fast_accepted` (out, optional): whether this QP is the accepted fast-path candidate (mpc_step's hook asks).
 // FULLFACT (the kernel of mpcb_step_sens): the fast path's factor records go out whole, tail [w | R~^-1] included -- sens_pass reads
 // R~_0^-1; the same factorisation, 48 more scalars stored per stage.
-template <class FT, bool FULLFACT = false, bool TERM = false>
+template <class FT, bool FULLFACT = false, int TERM = 0>
 SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_prev = nullptr, int *cur = nullptr, bool *fast_accepted = nullptr,
                      TermArg<TERM> tm = {})
 {
@@ -2169,7 +2183,7 @@ struct StepStats {
 // while G2 still holds the linearisation the QP was built from; `exact`: the QP was solved by an accepted fast-path attempt.
 struct NoHook {};
 // TERM (SQP_RTI): `tm` is the terminal cost of the QP, the cost and the stationarity rows (TermArg).
-template <class FT, class Lin, class Search, class AfterQp = NoHook, bool TERM = false>
+template <class FT, class Lin, class Search, class AfterQp = NoHook, int TERM = 0>
 SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer, AfterQp &&after_qp = AfterQp{},
                           TermArg<TERM> tm = {})
 {
@@ -2270,12 +2284,18 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 // taken while sm.xhat still equals the new true state: the noise of step t + 1 is added after it, and only when step t + 1 belongs to
 // this launch or work item -- across a launch boundary and a work-queue hand-off w.state[ST_Z] carries the truth, and the entry adds
 // x_noise[step0].
-template <class FT, bool REF = false, bool PERT = false>
+// TERM (with REF and PERT; the kernel of mpcb_rollout_term, mpc_stream_rollout_term.hip): step t's QP is closed by the joint-wise terminal
+// cost of `tt_` -- this simulation's constant blocks, and row t of its reference table as x_e -- at the simulation's own last stage.
+// The step linearises again at its start (REF), so the new row needs nothing else, and nothing of it carries to the next step, launch
+// or work item.
+template <class FT, bool REF = false, bool PERT = false, bool TERM = false>
 SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                     const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched_ = {},
-                    typename std::conditional<PERT, PlantPert, NoSched>::type pert_ = {})
+                    typename std::conditional<PERT, PlantPert, NoSched>::type pert_ = {},
+                    typename std::conditional<TERM, TermTab, NoSched>::type tt_ = {})
 {
     static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
+    static_assert(!TERM || (REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
     const double *sched = nullptr;
     if constexpr (REF) sched = uni_ref(TaskRef{sched_}).y;
     const double *p_wcv = nullptr, *p_ud = nullptr, *p_xn = nullptr;
@@ -2326,6 +2346,11 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if constexpr (REF) {
             const TaskRef ref{sched + (size_t)i * NTASK};
             c.lin_valid = false;
+            if constexpr (TERM)
+                s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
+                                 [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false, NoHook{},
+                                 TermArg<TERM_TABLE>{tt_.blocks, tt_.x_ref + (size_t)i * NX});
+            else
             s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
                              [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false);
         } else {

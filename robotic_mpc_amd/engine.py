@@ -93,7 +93,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
             "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
-            "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert")
+            "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -129,6 +129,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_rollout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), C.c_void_p]
     lib.mpcb_rollout_ref.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.c_void_p]
     lib.mpcb_rollout_pert.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), C.c_void_p]
+    lib.mpcb_rollout_term.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, _dp,
+                                      C.c_void_p]
     lib.mpcb_queue_used.argtypes = [C.c_void_p]
     lib.mpcb_sync.argtypes = [C.c_void_p]
     lib.mpcb_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
@@ -269,13 +271,18 @@ class MpcBatchEngine:
             setattr(r, name, C.cast(C.c_void_p(ptr), _dp if ty == "f8" else _ip))
         return r
 
-    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None):
+    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None, term=None):
         """Asynchronous launch of closed-loop steps [step0, step1) into device buffers.  `yref`: the task reference schedules of
         the batch, a contiguous float64 device tensor [batch, Nsim + N, 5] (N the longest horizon; schedule_tensor) -- the same one
         for every launch of a run -- or None for the packed references (mpcb_rollout).  `pert`: the plant perturbation of the
         batch (mpcb_rollout_pert; perturbation_tensors), a dict of contiguous float64 device tensors "wcv" [batch, 6], "u_dist"
         [batch, Nsim, 6], "x_noise" [batch, Nsim, 12], each may be missing or None -- the same ones for every launch of a run; it
-        needs `yref` (schedule_tensor supplies the packed rows when the configurations carry no schedule)."""
+        needs `yref` (schedule_tensor supplies the packed rows when the configurations carry no schedule).  `term`: the joint-wise
+        terminal cost of the batch (mpcb_rollout_term; terminal_tensors), a dict of contiguous float64 device tensors "blocks"
+        [batch, 18] (pqq 6 | pqv 6 | pvv 6) and "x_ref" [batch, Nsim, 12] (row t: the terminal reference of step t), both
+        required -- the same ones for every launch of a run; it needs `yref` likewise, and takes `pert` or the nominal plant."""
+        if term is not None:
+            return self._rollout_pert(bufs, step0, step1, yref, pert, stream, term)
         if pert is not None:
             return self._rollout_pert(bufs, step0, step1, yref, pert, stream)
         if stream is None:
@@ -295,9 +302,26 @@ class MpcBatchEngine:
         if tuple(yref.shape) != (pb.batch, pb.Nsim + pb.N, 5) or not yref.is_contiguous() or str(yref.dtype) != "torch.float64":
             raise ValueError(f"yref must be a contiguous float64 tensor [{pb.batch}, {pb.Nsim + pb.N}, 5], got {tuple(yref.shape)} {yref.dtype}")
 
-    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream):
-        """rollout(pert=): every shape is checked before the library is called."""
+    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None):
+        """rollout(pert=, term=): every shape is checked before the library is called."""
         pb = self._pb
+        tp = {}
+        if term is not None:
+            tshapes = {"blocks": (pb.batch, 18), "x_ref": (pb.batch, pb.Nsim, 12)}
+            if not isinstance(term, dict) or set(term) != set(tshapes):
+                raise ValueError(f"term has the keys {tuple(tshapes)} (got {sorted(term) if isinstance(term, dict) else type(term).__name__})")
+            if yref is None:
+                raise ValueError("a rollout with a terminal cost needs yref: schedule_tensor(cfgs) supplies the packed rows when there is "
+                                 "no schedule")
+            for name, shape in tshapes.items():
+                t = term[name]
+                if t is None or not hasattr(t, "data_ptr") or tuple(t.shape) != shape or not t.is_contiguous() \
+                        or str(t.dtype) != "torch.float64" or not t.is_cuda or t.device.index != self.device:
+                    raise ValueError(f"term[{name!r}] must be a contiguous float64 tensor {list(shape)} on cuda:{self.device}, got "
+                                     f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t).__name__)} "
+                                     f"{getattr(t, 'device', '')}".rstrip())
+                tp[name] = C.cast(C.c_void_p(t.data_ptr()), _dp)
+            pert = {} if pert is None else pert
         shapes = {"wcv": (pb.batch, 6), "u_dist": (pb.batch, pb.Nsim, 6), "x_noise": (pb.batch, pb.Nsim, 12)}
         extra = set(pert) - set(shapes)
         if extra:
@@ -318,8 +342,25 @@ class MpcBatchEngine:
 
             stream = torch.cuda.current_stream(self.device).cuda_stream
         r = self._result_struct(bufs)
+        if term is not None:
+            self._check(self.lib.mpcb_rollout_term(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
+                                                   tp["blocks"], tp["x_ref"], C.c_void_p(stream)), "mpcb_rollout_term")
+            return
         self._check(self.lib.mpcb_rollout_pert(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
                                                C.c_void_p(stream)), "mpcb_rollout_pert")
+
+    def terminal_tensors(self, cfgs: Sequence[Dict]):
+        """The terminal costs of a bucket (terminal.stack) on this engine's device -- {"blocks", "x_ref"} -- or None when the
+        configurations carry none (a bucket is all or nothing: packing.bucket_key)."""
+        if not any(c.get("terminal_cost") is not None for c in cfgs):
+            return None
+        import torch
+
+        from . import terminal
+
+        dev = torch.device("cuda", self.device)
+        blocks, x_ref = terminal.stack(cfgs)
+        return {"blocks": torch.from_numpy(blocks).to(dev), "x_ref": torch.from_numpy(x_ref).to(dev)}
 
     def perturbation_tensors(self, cfgs: Sequence[Dict]):
         """The plant perturbations of a bucket (plant.stack) on this engine's device -- {"wcv", "u_dist", "x_noise"} -- or None when
@@ -342,12 +383,12 @@ class MpcBatchEngine:
 
     def schedule_tensor(self, cfgs: Sequence[Dict]):
         """The reference schedules of a bucket (reference.stack) on this engine's device, or None when the configurations carry
-        none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation: the perturbed rollout
-        always tracks a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
+        none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation or a terminal cost: those
+        rollouts always track a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
         from . import reference
 
         if not any(c.get("reference_schedule") is not None for c in cfgs):
-            if not any(c.get("plant_perturbation") is not None for c in cfgs):
+            if not any(c.get("plant_perturbation") is not None or c.get("terminal_cost") is not None for c in cfgs):
                 return None
             import torch
 
@@ -504,10 +545,11 @@ class MpcBatchEngine:
         bufs = self.alloc_results(pb)
         yref = self.schedule_tensor(cfgs)      # sampled and stacked once; every chunk gets the same array
         pert = self.perturbation_tensors(cfgs)
+        term = self.terminal_tensors(cfgs)
         chunk = step_chunk if step_chunk and step_chunk > 0 else pb.Nsim
         self.last_kernel_ms = []
         for s0 in range(0, pb.Nsim, chunk):
-            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert)
+            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert, term=term)
             self.sync()
             self.last_kernel_ms.append(self.kernel_ms())
         return pb, bufs
@@ -520,11 +562,13 @@ class MpcBatchEngine:
     # ------------------------------------------------------------------ host-buffer path
     def run_host_buffers(self, cfgs: Sequence[Dict], chain) -> Dict[str, np.ndarray]:
         """Same through mpcb_run (library-owned device buffers, numpy in/out, no torch).  mpcb_run takes no reference schedule:
-        configurations that carry one are refused, and so are configurations with a plant perturbation."""
+        configurations that carry one are refused, and so are configurations with a plant perturbation or a terminal cost."""
         if any(c.get("reference_schedule") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no reference schedule: run configurations with a reference_schedule through run() / run_device()")
         if any(c.get("plant_perturbation") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no plant perturbation: run configurations with a plant_perturbation through run() / run_device()")
+        if any(c.get("terminal_cost") is not None for c in cfgs):
+            raise ValueError("mpcb_run takes no terminal cost: run configurations with a terminal_cost through run() / run_device()")
         pb = make_problem(cfgs)
         params = packing.pack_batch(cfgs)
         robot = np.ascontiguousarray(chain.packed(cfgs[0]["t_ee"]), dtype=np.float64)

@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import analysis, config as cfgmod, packing, plant, reference, robots
+from . import analysis, config as cfgmod, packing, plant, reference, robots, terminal
 
 
 def chain_for(cfg: Dict) -> robots.KinematicChain:
@@ -211,6 +211,7 @@ class Simulator:
         if rows is not None:
             data["reference_schedule"] = rows      # [Nsim + 1, 5]: the targets in force at every logged column
         data.update(plant.realised(self.resolved))  # "input_disturbance" [Nsim, 6] / "measurement_noise" [Nsim, 12] when configured
+        data.update(terminal.realised(self.resolved))  # "terminal_reference" [Nsim, 12] / "terminal_blocks" [6, 3] likewise
         return data
 
     def get_analysis(self):
@@ -320,9 +321,10 @@ class _EngineRunner:
             bufs = eng.alloc_results(pb)
             yref = eng.schedule_tensor(cfgs)   # the bucket's reference schedules, or None (kept alive by the ticket)
             pert = eng.perturbation_tensors(cfgs)   # ... and its plant perturbations, or None (likewise)
-            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert)
+            term = eng.terminal_tensors(cfgs)       # ... and its terminal costs, or None (likewise)
+            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert, term=term)
             summary = eng.summary(bufs, stream=stream.cuda_stream)
-        return eng, stream, bufs, summary, (yref, pert)
+        return eng, stream, bufs, summary, (yref, pert, term)
 
     def collect(self, ticket):
         eng, stream, bufs, summary, _yref = ticket

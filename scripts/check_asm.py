@@ -24,7 +24,12 @@ STREAM_ROLLOUT_REF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stre
 # plant step, under budgets of their own below
 ROLLOUT_PERT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_pert.hip")
 STREAM_ROLLOUT_PERT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_pert.hip")
-SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC, ROLLOUT_PERT_SRC, STREAM_ROLLOUT_PERT_SRC)
+# the kernels of the rollout with a terminal cost (mpcb_rollout_term; modules of their own): the perturbed rollout's on the engine
+# built with its TERM flag, under budgets of their own below
+ROLLOUT_TERM_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_term.hip")
+STREAM_ROLLOUT_TERM_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_term.hip")
+SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC, ROLLOUT_PERT_SRC, STREAM_ROLLOUT_PERT_SRC,
+           ROLLOUT_TERM_SRC, STREAM_ROLLOUT_TERM_SRC)
 
 
 def scan(asm_text):
@@ -73,12 +78,18 @@ BUDGET = {
     # window, with the plant lane's reference row, 37 / 38 / 2; lin_pass<true> 3)
     "22mpc_rollout_ref_kernelILi8ELi1E": 246, "22mpc_rollout_ref_kernelILi4ELi2E": 322, "22mpc_rollout_ref_kernelILi4ELi1E": 68,
     "21mpc_stream_ref_kernelId": 140,
-    "DevExecILi8ELi1EELb0EE10nlp_directILb1ELb1E": 41, "DevExecILi4ELi2EELb0EE10nlp_directILb1ELb1E": 42,
-    "DevExecILi4ELi1EELb0EE10nlp_directILb1ELb1E": 8,
+    "DevExecILi8ELi1EELi0EE10nlp_directILb1ELb1E": 41, "DevExecILi4ELi2EELi0EE10nlp_directILb1ELb1E": 42,
+    "DevExecILi4ELi1EELi0EE10nlp_directILb1ELb1E": 8,
     # the perturbed rollout (recorded: 232 / 300 / 61 for the kernel bodies, 140 for the throughput engine's; its NLP pass is the
     # scheduled rollout's, 33 / 36 / 2 here without the plant lane's work)
     "23mpc_rollout_pert_kernelILi8ELi1E": 255, "23mpc_rollout_pert_kernelILi4ELi2E": 330, "23mpc_rollout_pert_kernelILi4ELi1E": 68,
     "22mpc_stream_pert_kernelId": 154,
+    # the rollout with a terminal cost (recorded: 228 / 301 / 65 for the kernel bodies, 143 for the throughput engine's; its NLP pass
+    # with the stage-N terms of the terminal cost 50 / 49 / 2)
+    "23mpc_rollout_term_kernelILi8ELi1E": 251, "23mpc_rollout_term_kernelILi4ELi2E": 331, "23mpc_rollout_term_kernelILi4ELi1E": 72,
+    "22mpc_stream_term_kernelId": 157,
+    "DevExecILi8ELi1EELi2EE10nlp_directILb1ELb1E": 55, "DevExecILi4ELi2EELi2EE10nlp_directILb1ELb1E": 54,
+    "DevExecILi4ELi1EELi2EE10nlp_directILb1ELb1E": 8,
 }
 
 
