@@ -18,8 +18,10 @@
 #include "../../include/mpcbatch.h"
 #include "mpc_core.h"
 #include "mpc_devexec.h"
+#include "mpc_launch.h"
 #include "mpc_pack.h"
 #include "mpc_stream.h"
+#include "mpc_stream_queue.h"
 
 using namespace mpcb;
 
@@ -29,74 +31,8 @@ static_assert(offsetof(StepIO, yref) == sizeof(mpcb_step_io), "ABI struct mismat
 static_assert(MPCB_NREF == NTASK, "task reference width");
 static_assert(sizeof(Robot) == MPCB_NROBOT * sizeof(double), "robot layout");
 
-// The controller step kernels live in their own translation unit, mpc_step.hip: instantiated here, next to the rollout kernels,
-// they change the rollout kernels' code (the LDS lowering numbers the kernels of a module and passes the id to every pass).
-namespace mpcb {
-const void *step_kernel(int waves_per_sim, int wpe);
-void launch_step(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                 const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
-// ... and the throughput engine's step kernel in mpc_stream_step.hip, for the same reason
-const void *stream_step_kernel();
-void launch_stream_step(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                        size_t ws_stride, const StepIO &io, int reset);
-// ... and the kernels of both engines that read a per-simulation warm-start mode (mpcb_step_warm): mpc_step_warm.hip, mpc_stream_step_warm.hip
-const void *step_warm_kernel(int waves_per_sim, int wpe);
-void launch_step_warm(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                      const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
-void launch_stream_step_warm(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                             size_t ws_stride, const StepIO &io, int reset);
-// ... those that also write the sensitivity of u0 to the cost weights (mpcb_step_sens_w): mpc_step_sensw.hip, mpc_stream_step_sensw.hip
-const void *step_sensw_kernel(int waves_per_sim, int wpe);
-void launch_step_sensw(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                       const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
-void launch_stream_step_sensw(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                              size_t ws_stride, const StepIO &io, int reset);
-// ... those of the step with a joint-wise terminal cost (mpcb_step_term), without and with the sensitivity pass: mpc_step_term.hip,
-// mpc_step_term_sens.hip, mpc_stream_step_term.hip, mpc_stream_step_term_sens.hip
-const void *step_term_kernel(int waves_per_sim, int wpe);
-void launch_step_term(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                      const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
-const void *step_term_sens_kernel(int waves_per_sim, int wpe);
-void launch_step_term_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                           const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
-void launch_stream_step_term(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                             size_t ws_stride, const StepIO &io, int reset);
-void launch_stream_step_term_sens(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                                  size_t ws_stride, const StepIO &io, int reset);
-// ... and those that also write the sensitivities of u0 (mpcb_step_sens): mpc_step_sens.hip, mpc_stream_step_sens.hip
-const void *step_sens_kernel(int waves_per_sim, int wpe);
-void launch_step_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                      const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles);
-void launch_stream_step_sens(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                             size_t ws_stride, const StepIO &io, int reset);
-// ... and the rollout kernels of both engines that track a task reference schedule (mpcb_rollout_ref): mpc_rollout_ref.hip,
-// mpc_stream_rollout_ref.hip
-const void *rollout_ref_kernel(int waves_per_sim, int wpe);
-void launch_rollout_ref(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                        const InstParams *params, double *ws_base, size_t ws_stride, const Outputs &out, int step0, int step1,
-                        int pool_doubles, const double *yref_sched);
-void launch_stream_rollout_ref(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                               size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
-                               long long timeout_ticks, const double *yref_sched);
-// ... and those of the rollout over a perturbed plant (mpcb_rollout_pert): mpc_rollout_pert.hip, mpc_stream_rollout_pert.hip
-const void *rollout_pert_kernel(int waves_per_sim, int wpe);
-const void *stream_rollout_pert_kernel();
-void launch_rollout_pert(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                         const InstParams *params, double *ws_base, size_t ws_stride, const Outputs &out, int step0, int step1,
-                         int pool_doubles, const double *yref_sched, const PlantPert &pert);
-void launch_stream_rollout_pert(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                                size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
-                                long long timeout_ticks, const double *yref_sched, const PlantPert &pert);
-// ... and those of the rollout with the joint-wise terminal cost (mpcb_rollout_term): mpc_rollout_term.hip, mpc_stream_rollout_term.hip
-const void *rollout_term_kernel(int waves_per_sim, int wpe);
-const void *stream_rollout_term_kernel();
-void launch_rollout_term(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                         const InstParams *params, double *ws_base, size_t ws_stride, const Outputs &out, int step0, int step1,
-                         int pool_doubles, const double *yref_sched, const PlantPert &pert, const TermTab &term);
-void launch_stream_rollout_term(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                                size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
-                                long long timeout_ticks, const double *yref_sched, const PlantPert &pert, const TermTab &term);
-}  // namespace mpcb
+// The kernels of the controller step and of the rollout variants live in translation units of their own (mpc_step.hip says why:
+// instantiated here, next to the rollout kernels, they change the rollout kernels' code).  mpc_launch.h declares the getter of each.
 
 // WPE = 1: one wavefront per SIMD owns the whole 512-entry register file (one simulation per CU: batch <= #CUs, and
 // the 1 / 2 / 8-wavefront geometries).  WPE = 2: 256 registers, two 4-wavefront simulations resident per CU -- the
@@ -120,70 +56,15 @@ __global__ __launch_bounds__(WAVE *NWV, WPE) void mpc_rollout_kernel(Problem pb,
 #ifndef MPCB_STREAM_WPE
 #define MPCB_STREAM_WPE 2
 #endif
-// Two launch shapes:
-//   * one workgroup per simulation, all of [step0, step1) (queue == nullptr);
-//   * WORK QUEUE (batch larger than the wavefronts resident at once): the grid is the resident set, every wavefront
-//     pops items (simulation, chunk of `chunk_steps` closed-loop steps) off an atomic counter, chunk-major -- all
-//     simulations advance together, fast wavefronts take more items, and the launch ends within one chunk of the
-//     balanced time instead of with the slowest pair of whole simulations.  Chunk c of a simulation follows chunk c-1,
-//     which may have run on any CU: the finishing wavefront releases (stores drained, agent-scope release, progress
-//     counter), the next one polls the counter and acquires (MI355X_MICROARCH.md, hand-off recipe).  An item's
-//     predecessor was popped earlier, so it is running or done: no wavefront ever waits for work nobody has taken.  A
-//     bounded poll (`timeout_ticks` of the 100 MHz clock, queue_timeout_ticks below) turns a broken hand-off into an error flag, never a hang.
-//   queue[0] item counter, queue[1] error flag, queue[2 + i] chunks of simulation i done in this launch.
-// The bound is a bug guard, not a schedule: a waiting item's predecessor is always running, so it is sized from the WORK LIMIT of
-// one chunk (queue_timeout_ticks below), never from typical times -- a legitimately slow chunk (full SQP at a long horizon, every
-// QP running to qp_solver_iter_max) must not trip it and take the whole bucket down.
-// (The kernel of the scheduled rollout, mpc_stream_rollout_ref.hip, repeats this loop: moved into a shared function template over
-// the body, it compiled this kernel to other code than it has here.)
+// The launch loop -- one workgroup per simulation, or the work queue over (simulation, chunk of steps) items -- is
+// mpc_stream_queue.h's, shared with the rollout variants of this engine.
 template <class FT>
 __global__ __launch_bounds__(WAVE, MPCB_STREAM_WPE) void mpc_stream_kernel(Problem pb, const Robot *__restrict__ rbd, const InstParams *__restrict__ params,
                                                                            double *ws_base, size_t ws_stride, Outputs out, int step0, int step1,
                                                                            int *queue, int chunk_steps, long long timeout_ticks)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const bool queued = queue != nullptr;
-    const int n_chunks = queued ? (step1 - step0 + chunk_steps - 1) / chunk_steps : 1;
-    const int n_items = n_chunks * pb.batch;
-    for (;;) {
-        int inst = blockIdx.x, s0 = step0, s1 = step1, c = 0;
-        if (queued) {
-            int q = 0;
-            if (threadIdx.x == 0) q = __hip_atomic_fetch_add(&queue[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            q = __builtin_amdgcn_readfirstlane(q);
-            if (q >= n_items) break;
-            c = q / pb.batch;
-            inst = q - c * pb.batch;
-            s0 = step0 + c * chunk_steps;
-            s1 = s0 + chunk_steps < step1 ? s0 + chunk_steps : step1;
-            if (c > 0) {
-                int ok = 1;
-                if (threadIdx.x == 0) {
-                    const long long t_end = (long long)wall_clock64() + timeout_ticks;
-                    while (__hip_atomic_load(&queue[2 + inst], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c) {
-                        if ((long long)wall_clock64() > t_end || __hip_atomic_load(&queue[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                            __hip_atomic_store(&queue[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            ok = 0;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(32);
-                    }
-                }
-                ok = __builtin_amdgcn_readfirstlane(ok);
-                if (!ok) break;                                           // error flag set: every wavefront drains out
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // this CU's L1 may hold lines of an earlier chunk
-                __builtin_amdgcn_s_waitcnt(0);
-            }
-        } else if (inst >= pb.batch) {
-            break;
-        }
-        se::rollout<FT>(pb, params, rbd, ws_base, ws_stride, out, inst, s0, s1);
-        if (!queued) break;
-        __builtin_amdgcn_s_waitcnt(0);                                    // every store of this chunk has been acknowledged
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __builtin_amdgcn_s_waitcnt(0);
-        if (threadIdx.x == 0) __hip_atomic_store(&queue[2 + inst], c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    MPCB_STREAM_QUEUE_LOOP(se::rollout<FT>(pb, params, rbd, ws_base, ws_stride, out, inst, s0, s1))
 #endif
 }
 
@@ -267,6 +148,10 @@ __global__ void mpc_debug_task_lin_kernel(int n, Robot rb, const InstParams *__r
 }
 
 // ------------------------------------------------------------------------------------ host
+// The variants of the controller step and the kinds of rollout; each is one kernel (family) per engine, see with_kernel below.
+enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS };
+enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM };
+
 struct mpcb_handle {
     int device = -1;
     std::string err;
@@ -288,8 +173,7 @@ struct mpcb_handle {
     int *d_queue = nullptr;    // throughput engine, work-queue launches: counter, error flag, per-simulation progress
     size_t queue_cap = 0;
     bool queue_used = false;   // the last launch went through the work queue (mpcb_sync checks its error flag)
-    bool pert_used = false;    // the last rollout launch was a perturbed one (mpcb_kernel_info reports its kernel)
-    bool term_used = false;    // ... one with a terminal cost (likewise)
+    RolloutKind last_rollout = ROLLOUT_BASE;   // of the last rollout launch (mpcb_kernel_info reports its kernel)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t last_stream = nullptr;
     bool timed = false;
@@ -326,6 +210,121 @@ static int check_problem(mpcb_handle *h, const mpcb_problem *p)
     if (p->precision == MPCB_PRECISION_FP32_RICCATI && p->solver_type != MPCB_SOLVER_SQP_RTI)
         return fail(h, MPCB_EINVAL, "the fp32 Riccati leg is validated for SQP_RTI only");
     return MPCB_OK;
+}
+
+// ---- the launch path: (handle, variant) -> kernel -> one launch site per signature, between the handle's two events
+// the kernels of mpcb_rollout are this unit's own (the order of these two functions is the order of the kernels in the module)
+static RolloutFn rollout_kernel(int waves_per_sim, int wpe) { return MPCB_GEOMETRY_KERNEL(RolloutFn, mpc_rollout_kernel, waves_per_sim, wpe); }
+static StreamRolloutFn stream_rollout_kernel(int precision)
+{
+    return precision == MPCB_PRECISION_FP32_RICCATI ? mpc_stream_kernel<float> : mpc_stream_kernel<double>;
+}
+
+// The kernel that runs a step variant, or a kind of rollout, on the handle's engine and geometry: calls f with its typed pointer
+// (mpc_launch.h) and returns what f returns.  The launch, the LDS ceiling and mpcb_kernel_info all ask here.
+template <class F>
+static int with_kernel(const mpcb_handle *h, StepVariant v, F &&f)
+{
+    const int nw = h->waves_per_sim, wpe = h->wpe;
+    if (h->engine == 1)
+        return f(v == STEP_TERM_SENS ? stream_step_term_sens_kernel() : v == STEP_TERM ? stream_step_term_kernel()
+                 : v == STEP_SENSW   ? stream_step_sensw_kernel()     : v == STEP_SENS ? stream_step_sens_kernel()
+                 : v == STEP_WARM    ? stream_step_warm_kernel()      : stream_step_kernel());
+    return f(v == STEP_TERM_SENS ? step_term_sens_kernel(nw, wpe) : v == STEP_TERM ? step_term_kernel(nw, wpe)
+             : v == STEP_SENSW   ? step_sensw_kernel(nw, wpe)     : v == STEP_SENS ? step_sens_kernel(nw, wpe)
+             : v == STEP_WARM    ? step_warm_kernel(nw, wpe)      : step_kernel(nw, wpe));
+}
+template <class F>
+static int with_kernel(const mpcb_handle *h, RolloutKind kind, F &&f)
+{
+    const int nw = h->waves_per_sim, wpe = h->wpe;
+    if (h->engine == 1)
+        return kind == ROLLOUT_TERM ? f(stream_rollout_term_kernel()) : kind == ROLLOUT_PERT ? f(stream_rollout_pert_kernel())
+             : kind == ROLLOUT_REF  ? f(stream_rollout_ref_kernel())  : f(stream_rollout_kernel(h->pb.precision));
+    return kind == ROLLOUT_TERM ? f(rollout_term_kernel(nw, wpe)) : kind == ROLLOUT_PERT ? f(rollout_pert_kernel(nw, wpe))
+         : kind == ROLLOUT_REF  ? f(rollout_ref_kernel(nw, wpe))  : f(rollout_kernel(nw, wpe));
+}
+
+// what a launch passes besides the handle's own state; each signature takes the members it declares
+struct StepArgs { StepIO io; int reset; };
+struct RolloutArgs {
+    unsigned grid; Outputs out; int step0, step1;
+    int *queue; int chunk_steps; long long timeout_ticks;   // throughput engine
+    const double *yref_sched; PlantPert pert; TermTab term;  // ref / pert / term
+};
+
+// Every kernel starts (pb, robot record, params, ws_base, ws_stride).  Latency engine: the record by value, a workgroup of
+// waves_per_sim wavefronts, the dynamic-LDS pool.  Throughput engine: the record in device memory, one wavefront, static LDS only.
+template <class K, class... A>
+static void latency_launch(K k, const mpcb_handle *h, unsigned grid, hipStream_t s, const A &...a)
+{
+    hipLaunchKernelGGL(k, dim3(grid), dim3(WAVE * h->waves_per_sim), (size_t)h->pool_doubles * sizeof(double), s, h->pb, h->rb, h->d_params,
+                       h->d_ws, h->ws_stride, a...);
+}
+template <class K, class... A>
+static void stream_launch(K k, const mpcb_handle *h, unsigned grid, hipStream_t s, const A &...a)
+{
+    hipLaunchKernelGGL(k, dim3(grid), dim3(WAVE), 0, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, a...);
+}
+static void launch(StepFn k, const mpcb_handle *h, hipStream_t s, const StepArgs &a)
+{
+    latency_launch(k, h, (unsigned)h->pb.batch, s, a.io, a.reset, h->pool_doubles);
+}
+static void launch(StreamStepFn k, const mpcb_handle *h, hipStream_t s, const StepArgs &a)
+{
+    stream_launch(k, h, (unsigned)h->pb.batch, s, a.io, a.reset);   // no work queue: one launch is one step of every simulation
+}
+static void launch(RolloutFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles);
+}
+static void launch(RolloutRefFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched);
+}
+static void launch(RolloutPertFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert);
+}
+static void launch(RolloutTermFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.term);
+}
+static void launch(StreamRolloutFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks);
+}
+static void launch(StreamRolloutRefFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched);
+}
+static void launch(StreamRolloutPertFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert);
+}
+static void launch(StreamRolloutTermFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.term);
+}
+
+// One launch of `variant`'s kernel on stream s, between the two events mpcb_last_kernel_ms reads.  Latency engine: the dynamic-LDS
+// ceiling is a process-wide attribute of the kernel, not of this handle, so it is raised to the largest pool any handle can ask
+// for, right before the launch.
+template <class V, class Args>
+static int timed_launch(mpcb_handle *h, V variant, hipStream_t s, const Args &args)
+{
+    return with_kernel(h, variant, [&](auto k) {
+        static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
+        if (h->engine != 1)
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        HIPCHK(h, hipEventRecord(h->ev0, s));
+        launch(k, h, s, args);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipEventRecord(h->ev1, s));
+        h->last_stream = s;
+        h->timed = true;
+        return MPCB_OK;
+    });
 }
 
 extern "C" {
@@ -531,8 +530,7 @@ static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *param
     }
     h->ready = true;
     h->next_step = 0;
-    h->pert_used = false;
-    h->term_used = false;
+    h->last_rollout = ROLLOUT_BASE;
     h->timed = false;
     h->controller = controller;
     h->reset_next = true;
@@ -559,34 +557,6 @@ int mpcb_controller_engine_for(const mpcb_problem *p, int ragged)
 {
     if (!p || p->N < 1 || p->batch < 1) return MPCB_EINVAL;
     return pick_controller_engine(p, ragged != 0);
-}
-
-// the latency engine's kernel for the handle's geometry: the step kernel on a controller handle, the rollout kernel otherwise
-static const void *latency_kernel(const mpcb_handle *h)
-{
-    if (h->controller) return step_kernel(h->waves_per_sim, h->wpe);
-    return h->waves_per_sim == 8 ? (const void *)mpc_rollout_kernel<8>
-         : h->waves_per_sim == 4 ? (h->wpe == 2 ? (const void *)mpc_rollout_kernel<4, 2> : (const void *)mpc_rollout_kernel<4>)
-         : h->waves_per_sim == 2 ? (const void *)mpc_rollout_kernel<2> : (const void *)mpc_rollout_kernel<1>;
-}
-
-// the dynamic-LDS ceiling is a process-wide attribute of the kernel, not of this handle: always raise it to the largest pool any
-// handle can ask for, right before the launch
-// (`step`: 0 the kernel of mpcb_rollout / mpcb_step, 1 of mpcb_step_warm, 2 of mpcb_step_sens, 3 of mpcb_step_sens_w, 4 / 5 of
-// mpcb_step_term without / with sens, 6 of mpcb_rollout_ref, 7 of mpcb_rollout_pert, 8 of mpcb_rollout_term)
-static int raise_lds_limit(mpcb_handle *h, int step = 0)
-{
-    static const int max_lds = (160 * 1024 - (int)sizeof(Smem) - 64) / 16 * 16;
-    HIPCHK(h, hipFuncSetAttribute(step == 8 ? rollout_term_kernel(h->waves_per_sim, h->wpe)
-                                  : step == 7 ? rollout_pert_kernel(h->waves_per_sim, h->wpe)
-                                  : step == 6 ? rollout_ref_kernel(h->waves_per_sim, h->wpe)
-                                  : step == 5 ? step_term_sens_kernel(h->waves_per_sim, h->wpe)
-                                  : step == 4 ? step_term_kernel(h->waves_per_sim, h->wpe)
-                                  : step == 3 ? step_sensw_kernel(h->waves_per_sim, h->wpe)
-                                  : step == 2 ? step_sens_kernel(h->waves_per_sim, h->wpe)
-                                  : step == 1 ? step_warm_kernel(h->waves_per_sim, h->wpe) : latency_kernel(h),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    return MPCB_OK;
 }
 
 // Hand-off timeout of the work-queue launch in ticks of the 100 MHz clock: the most work one chunk of one simulation can be
@@ -645,9 +615,6 @@ int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o
         return fail(h, MPCB_EINVAL, "mpcb_rollout_term: a rollout with a terminal cost needs a reference schedule (the packed rows when there is none)");
     if (term_blocks && !term_xref)
         return fail(h, MPCB_EINVAL, "mpcb_rollout_term: term_blocks needs term_xref, the table of terminal references");
-    PlantPert pert{nullptr, nullptr, nullptr};
-    if (pert_) pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
-    const TermTab term{term_blocks, term_xref};
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -657,8 +624,15 @@ int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o
         return fail(h, MPCB_EINVAL, "every result array must be provided");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    Outputs out;
-    std::memcpy(&out, o, sizeof out);
+    const RolloutKind kind = term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
+    RolloutArgs args{};
+    args.yref_sched = yref_sched;
+    if (pert_) args.pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
+    args.term = TermTab{term_blocks, term_xref};
+    std::memcpy(&args.out, o, sizeof args.out);
+    args.step0 = step0;
+    args.step1 = step1;
+    args.grid = (unsigned)h->pb.batch;
     if (h->engine == 1) {
         // at least as many simulations as resident wavefronts: work queue over (simulation, chunk of steps) items.
         // Measured at N=100, 600 steps (profiles/r02_work_queue.txt): batch 4096 890 -> 968 k steps/s, 2560 668 -> 939 k,
@@ -684,67 +658,13 @@ int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o
             queue = h->d_queue;
         }
         h->queue_used = queued;
-        const long long qticks = queue_timeout_ticks(h->pb, chunk);
-        HIPCHK(h, hipEventRecord(h->ev0, s));
-        const dim3 sgrid((unsigned)(queued ? nslots : h->pb.batch));
-        h->pert_used = pert_ != nullptr;
-        h->term_used = term_blocks != nullptr;
-        if (term_blocks)
-            launch_stream_rollout_term(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
-                                       yref_sched, pert, term);
-        else if (pert_)
-            launch_stream_rollout_pert(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
-                                       yref_sched, pert);
-        else if (yref_sched)
-            launch_stream_rollout_ref(sgrid, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1, queue, chunk, qticks,
-                                      yref_sched);
-        else if (h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
-            hipLaunchKernelGGL(mpc_stream_kernel<float>, sgrid, dim3(WAVE), 0, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out,
-                               step0, step1, queue, chunk, qticks);
-        else
-            hipLaunchKernelGGL(mpc_stream_kernel<double>, sgrid, dim3(WAVE), 0, s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, out,
-                               step0, step1, queue, chunk, qticks);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipEventRecord(h->ev1, s));
-        h->last_stream = s;
-        h->timed = true;
-        h->next_step = step1;
-        return MPCB_OK;
+        args.grid = (unsigned)(queued ? nslots : h->pb.batch);
+        args.queue = queue;
+        args.chunk_steps = chunk;
+        args.timeout_ticks = queue_timeout_ticks(h->pb, chunk);
     }
-    const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    if (int rc = raise_lds_limit(h, term_blocks ? 8 : pert_ ? 7 : yref_sched ? 6 : 0)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev0, s));
-    const dim3 grid((unsigned)h->pb.batch);
-    h->pert_used = pert_ != nullptr;
-    h->term_used = term_blocks != nullptr;
-    if (term_blocks)
-        launch_rollout_term(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
-                            h->pool_doubles, yref_sched, pert, term);
-    else if (pert_)
-        launch_rollout_pert(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
-                            h->pool_doubles, yref_sched, pert);
-    else if (yref_sched)
-        launch_rollout_ref(h->waves_per_sim, h->wpe, grid, lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, out, step0, step1,
-                           h->pool_doubles, yref_sched);
-    else if (h->waves_per_sim == 8)
-        hipLaunchKernelGGL(mpc_rollout_kernel<8>, grid, dim3(WAVE * 8), lds, s, h->pb, h->rb, h->d_params, h->d_ws,
-                           h->ws_stride, out, step0, step1, h->pool_doubles);
-    else if (h->waves_per_sim == 4 && h->wpe == 2)
-        hipLaunchKernelGGL((mpc_rollout_kernel<4, 2>), grid, dim3(WAVE * 4), lds, s, h->pb, h->rb, h->d_params, h->d_ws,
-                           h->ws_stride, out, step0, step1, h->pool_doubles);
-    else if (h->waves_per_sim == 4)
-        hipLaunchKernelGGL(mpc_rollout_kernel<4>, grid, dim3(WAVE * 4), lds, s, h->pb, h->rb, h->d_params, h->d_ws,
-                           h->ws_stride, out, step0, step1, h->pool_doubles);
-    else if (h->waves_per_sim == 2)
-        hipLaunchKernelGGL(mpc_rollout_kernel<2>, grid, dim3(WAVE * 2), lds, s, h->pb, h->rb, h->d_params, h->d_ws,
-                           h->ws_stride, out, step0, step1, h->pool_doubles);
-    else
-        hipLaunchKernelGGL(mpc_rollout_kernel<1>, grid, dim3(WAVE), lds, s, h->pb, h->rb, h->d_params, h->d_ws,
-                           h->ws_stride, out, step0, step1, h->pool_doubles);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, s));
-    h->last_stream = s;
-    h->timed = true;
+    h->last_rollout = kind;
+    if (int rc = timed_launch(h, kind, s, args)) return rc;
     h->next_step = step1;
     return MPCB_OK;
 }
@@ -821,10 +741,11 @@ static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref,
     if (term && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
         return fail(h, MPCB_EINVAL, "mpcb_step_term: the terminal cost is offered with SQP_RTI; this controller runs full SQP");
     if (du0_dxe && (!sens || !term)) return fail(h, MPCB_EINVAL, "mpcb_step_term: du0_dxe needs sens (du0_dx and valid) and term");
-    const int variant = term ? (sens ? 5 : 4) : du0_dw ? 3 : sens ? 2 : warm ? 1 : 0;
+    const StepVariant variant = term ? (sens ? STEP_TERM_SENS : STEP_TERM) : du0_dw ? STEP_SENSW : sens ? STEP_SENS : warm ? STEP_WARM : STEP_BASE;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    StepIO sio;
+    StepArgs args;
+    StepIO &sio = args.io;
     std::memcpy(&sio, io, sizeof(mpcb_step_io));
     sio.yref = yref;
     // (new weights, or a new terminal cost, make the carried linearisation stale exactly as a new reference does)
@@ -834,50 +755,8 @@ static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref,
     sio.term = term;
     sio.du0_dxe = du0_dxe;
     if (sens) { sio.du0_dx = sens->du0_dx; sio.du0_dyref = sens->du0_dyref; sio.sens_valid = sens->valid; }
-    const int rs = (reset != 0 || h->reset_next) ? 1 : 0;
-    if (h->engine == MPCB_ENGINE_STREAM) {
-        // throughput engine: one wavefront per simulation, static LDS only, no work queue
-        HIPCHK(h, hipEventRecord(h->ev0, s));
-        if (variant == 5) launch_stream_step_term_sens(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
-        else if (variant == 4) launch_stream_step_term(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
-        else if (variant == 3) launch_stream_step_sensw(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
-        else if (variant == 2) launch_stream_step_sens(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
-        else if (variant == 1) launch_stream_step_warm(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
-        else launch_stream_step(dim3((unsigned)h->pb.batch), s, h->pb, h->d_rb, h->d_params, h->d_ws, h->ws_stride, sio, rs);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipEventRecord(h->ev1, s));
-        h->last_stream = s;
-        h->timed = true;
-        h->queue_used = false;
-        h->reset_next = false;
-        h->weights_changed = false;
-        return MPCB_OK;
-    }
-    const size_t lds = (size_t)h->pool_doubles * sizeof(double);
-    if (int rc = raise_lds_limit(h, variant)) return rc;
-    HIPCHK(h, hipEventRecord(h->ev0, s));
-    if (variant == 5)
-        launch_step_term_sens(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride,
-                              sio, rs, h->pool_doubles);
-    else if (variant == 4)
-        launch_step_term(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
-                         rs, h->pool_doubles);
-    else if (variant == 3)
-        launch_step_sensw(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
-                          rs, h->pool_doubles);
-    else if (variant == 2)
-        launch_step_sens(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
-                         rs, h->pool_doubles);
-    else if (variant == 1)
-        launch_step_warm(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio,
-                         rs, h->pool_doubles);
-    else
-        launch_step(h->waves_per_sim, h->wpe, dim3((unsigned)h->pb.batch), lds, s, h->pb, h->rb, h->d_params, h->d_ws, h->ws_stride, sio, rs,
-                    h->pool_doubles);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev1, s));
-    h->last_stream = s;
-    h->timed = true;
+    args.reset = (reset != 0 || h->reset_next) ? 1 : 0;
+    if (int rc = timed_launch(h, variant, s, args)) return rc;
     h->queue_used = false;
     h->reset_next = false;
     h->weights_changed = false;
@@ -910,17 +789,11 @@ int mpcb_kernel_info(mpcb_handle *h, int *vgprs, int *sgprs, int *lds_bytes, int
 {
     if (!h) return MPCB_EINVAL;
     hipFuncAttributes a;
-    if (h->engine == 1 && h->controller) {
-        HIPCHK(h, hipFuncGetAttributes(&a, stream_step_kernel()));
-    } else if (h->term_used && !h->controller) {             // (the last rollout launch was mpcb_rollout_term with blocks: its kernel)
-        HIPCHK(h, hipFuncGetAttributes(&a, h->engine == 1 ? stream_rollout_term_kernel() : rollout_term_kernel(h->waves_per_sim, h->wpe)));
-    } else if (h->pert_used && !h->controller) {             // (the last rollout launch was mpcb_rollout_pert: its kernel)
-        HIPCHK(h, hipFuncGetAttributes(&a, h->engine == 1 ? stream_rollout_pert_kernel() : rollout_pert_kernel(h->waves_per_sim, h->wpe)));
-    } else if (h->engine == 1) {
-        HIPCHK(h, hipFuncGetAttributes(&a, h->pb.precision == MPCB_PRECISION_FP32_RICCATI ? (const void *)mpc_stream_kernel<float>
-                                                                                          : (const void *)mpc_stream_kernel<double>));
-    } else
-    HIPCHK(h, hipFuncGetAttributes(&a, latency_kernel(h)));
+    auto attributes = [&](auto k) { HIPCHK(h, hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k))); return MPCB_OK; };
+    // a controller handle: the base step kernel whatever variant ran last; otherwise the kernel of the last rollout launch, where a
+    // scheduled rollout counts as the base one
+    const RolloutKind kind = h->last_rollout == ROLLOUT_REF ? ROLLOUT_BASE : h->last_rollout;
+    if (int rc = h->controller ? with_kernel(h, STEP_BASE, attributes) : with_kernel(h, kind, attributes)) return rc;
     if (vgprs) *vgprs = a.numRegs;
     if (sgprs) *sgprs = 0;
     if (lds_bytes) *lds_bytes = (int)a.sharedSizeBytes;

@@ -11,6 +11,7 @@
 
 #include "mpc_core.h"
 #include "mpc_devexec.h"
+#include "mpc_launch.h"
 
 // yref_sched: [batch][Nsim + N][NTASK], N = pb.N; pert: the three [batch][...] arrays of mpcb_plant_pert (each may be null);
 // term: blocks [batch][18] and x_ref [batch][Nsim][12] (neither null)
@@ -31,34 +32,5 @@ __global__ __launch_bounds__(WAVE *NWV, WPE) void mpc_rollout_term_kernel(Proble
 }
 
 namespace mpcb {
-
-// the kernel of a geometry (hipFuncSetAttribute / hipFuncGetAttributes)
-const void *rollout_term_kernel(int waves_per_sim, int wpe)
-{
-    return waves_per_sim == 8 ? (const void *)mpc_rollout_term_kernel<8>
-         : waves_per_sim == 4 ? (wpe == 2 ? (const void *)mpc_rollout_term_kernel<4, 2> : (const void *)mpc_rollout_term_kernel<4>)
-         : waves_per_sim == 2 ? (const void *)mpc_rollout_term_kernel<2> : (const void *)mpc_rollout_term_kernel<1>;
-}
-
-void launch_rollout_term(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                         const InstParams *params, double *ws_base, size_t ws_stride, const Outputs &out, int step0, int step1,
-                         int pool_doubles, const double *yref_sched, const PlantPert &pert, const TermTab &term)
-{
-    if (waves_per_sim == 8)
-        hipLaunchKernelGGL(mpc_rollout_term_kernel<8>, grid, dim3(WAVE * 8), lds, s, pb, rb, params, ws_base, ws_stride, out, step0, step1,
-                           pool_doubles, yref_sched, pert, term);
-    else if (waves_per_sim == 4 && wpe == 2)
-        hipLaunchKernelGGL((mpc_rollout_term_kernel<4, 2>), grid, dim3(WAVE * 4), lds, s, pb, rb, params, ws_base, ws_stride, out, step0,
-                           step1, pool_doubles, yref_sched, pert, term);
-    else if (waves_per_sim == 4)
-        hipLaunchKernelGGL(mpc_rollout_term_kernel<4>, grid, dim3(WAVE * 4), lds, s, pb, rb, params, ws_base, ws_stride, out, step0, step1,
-                           pool_doubles, yref_sched, pert, term);
-    else if (waves_per_sim == 2)
-        hipLaunchKernelGGL(mpc_rollout_term_kernel<2>, grid, dim3(WAVE * 2), lds, s, pb, rb, params, ws_base, ws_stride, out, step0, step1,
-                           pool_doubles, yref_sched, pert, term);
-    else
-        hipLaunchKernelGGL(mpc_rollout_term_kernel<1>, grid, dim3(WAVE), lds, s, pb, rb, params, ws_base, ws_stride, out, step0, step1,
-                           pool_doubles, yref_sched, pert, term);
-}
-
+RolloutTermFn rollout_term_kernel(int waves_per_sim, int wpe) { return MPCB_GEOMETRY_KERNEL(RolloutTermFn, mpc_rollout_term_kernel, waves_per_sim, wpe); }
 }  // namespace mpcb

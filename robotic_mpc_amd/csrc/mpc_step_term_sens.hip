@@ -10,6 +10,7 @@
 
 #include "mpc_core.h"
 #include "mpc_devexec.h"
+#include "mpc_launch.h"
 
 template <int NWV, int WPE = 1>
 __global__ __launch_bounds__(WAVE *NWV, WPE) __attribute__((disable_tail_calls)) void mpc_step_term_sens_kernel(Problem pb, Robot rb, const InstParams *__restrict__ params,
@@ -25,27 +26,5 @@ __global__ __launch_bounds__(WAVE *NWV, WPE) __attribute__((disable_tail_calls))
 }
 
 namespace mpcb {
-
-const void *step_term_sens_kernel(int waves_per_sim, int wpe)
-{
-    return waves_per_sim == 8 ? (const void *)mpc_step_term_sens_kernel<8>
-         : waves_per_sim == 4 ? (wpe == 2 ? (const void *)mpc_step_term_sens_kernel<4, 2> : (const void *)mpc_step_term_sens_kernel<4>)
-         : waves_per_sim == 2 ? (const void *)mpc_step_term_sens_kernel<2> : (const void *)mpc_step_term_sens_kernel<1>;
-}
-
-void launch_step_term_sens(int waves_per_sim, int wpe, dim3 grid, size_t lds, hipStream_t s, const Problem &pb, const Robot &rb,
-                      const InstParams *params, double *ws_base, size_t ws_stride, const StepIO &io, int reset, int pool_doubles)
-{
-    if (waves_per_sim == 8)
-        hipLaunchKernelGGL(mpc_step_term_sens_kernel<8>, grid, dim3(WAVE * 8), lds, s, pb, rb, params, ws_base, ws_stride, io, reset, pool_doubles);
-    else if (waves_per_sim == 4 && wpe == 2)
-        hipLaunchKernelGGL((mpc_step_term_sens_kernel<4, 2>), grid, dim3(WAVE * 4), lds, s, pb, rb, params, ws_base, ws_stride, io, reset, pool_doubles);
-    else if (waves_per_sim == 4)
-        hipLaunchKernelGGL(mpc_step_term_sens_kernel<4>, grid, dim3(WAVE * 4), lds, s, pb, rb, params, ws_base, ws_stride, io, reset, pool_doubles);
-    else if (waves_per_sim == 2)
-        hipLaunchKernelGGL(mpc_step_term_sens_kernel<2>, grid, dim3(WAVE * 2), lds, s, pb, rb, params, ws_base, ws_stride, io, reset, pool_doubles);
-    else
-        hipLaunchKernelGGL(mpc_step_term_sens_kernel<1>, grid, dim3(WAVE), lds, s, pb, rb, params, ws_base, ws_stride, io, reset, pool_doubles);
-}
-
+StepFn step_term_sens_kernel(int waves_per_sim, int wpe) { return MPCB_GEOMETRY_KERNEL(StepFn, mpc_step_term_sens_kernel, waves_per_sim, wpe); }
 }  // namespace mpcb

@@ -2,11 +2,9 @@
 // on the THROUGHPUT engine: se::rollout<double, true> (mpc_stream.h), the closed loop whose step t tracks the window [t, t + N_i) of
 // each simulation's schedule and whose error log measures column t against schedule row t.
 //
-// A translation unit of its own for the reason given in mpc_step.hip.  The two launch shapes of mpc_stream_kernel (mpc_kernel.hip,
-// where the protocol is described): one wavefront per simulation, or the work queue over (simulation, chunk of steps) items.  The
-// pop / poll / release loop is REPEATED here, not shared: as a function template over the body in mpc_stream.h it compiled
-// mpc_stream_kernel to other code than it has with the loop written out (same resources, other schedule), and the flagship kernel
-// keeps its code.  A change to the protocol is a change to both.  fp64 only.
+// A translation unit of its own for the reason given in mpc_step.hip.  The two launch shapes of mpc_stream_kernel (mpc_kernel.hip):
+// one wavefront per simulation, or the work queue over (simulation, chunk of steps) items, through the loop they all share
+// (mpc_stream_queue.h, where the protocol is described).  fp64 only.
 //
 // disable_tail_calls, as in mpc_stream_step.hip: the first pass of a step is called before anything local has escaped here as well.
 #include <hip/hip_runtime.h>
@@ -14,7 +12,9 @@
 #ifndef MPCB_STREAM_WPE
 #define MPCB_STREAM_WPE 2
 #endif
+#include "mpc_launch.h"
 #include "mpc_stream.h"
+#include "mpc_stream_queue.h"
 
 using namespace mpcb;
 
@@ -26,61 +26,10 @@ __global__ __launch_bounds__(WAVE, MPCB_STREAM_WPE) __attribute__((disable_tail_
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     const size_t rows = (size_t)pb.Nsim + pb.N;
-    const bool queued = queue != nullptr;
-    const int n_chunks = queued ? (step1 - step0 + chunk_steps - 1) / chunk_steps : 1;
-    const int n_items = n_chunks * pb.batch;
-    for (;;) {
-        int inst = blockIdx.x, s0 = step0, s1 = step1, c = 0;
-        if (queued) {
-            int q = 0;
-            if (threadIdx.x == 0) q = __hip_atomic_fetch_add(&queue[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            q = __builtin_amdgcn_readfirstlane(q);
-            if (q >= n_items) break;
-            c = q / pb.batch;
-            inst = q - c * pb.batch;
-            s0 = step0 + c * chunk_steps;
-            s1 = s0 + chunk_steps < step1 ? s0 + chunk_steps : step1;
-            if (c > 0) {
-                int ok = 1;
-                if (threadIdx.x == 0) {
-                    const long long t_end = (long long)wall_clock64() + timeout_ticks;
-                    while (__hip_atomic_load(&queue[2 + inst], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c) {
-                        if ((long long)wall_clock64() > t_end || __hip_atomic_load(&queue[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                            __hip_atomic_store(&queue[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            ok = 0;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(32);
-                    }
-                }
-                ok = __builtin_amdgcn_readfirstlane(ok);
-                if (!ok) break;                                           // error flag set: every wavefront drains out
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // this CU's L1 may hold lines of an earlier chunk
-                __builtin_amdgcn_s_waitcnt(0);
-            }
-        } else if (inst >= pb.batch) {
-            break;
-        }
-        se::rollout<FT, true>(pb, params, rbd, ws_base, ws_stride, out, inst, s0, s1, yref_sched + (size_t)inst * rows * NTASK);
-        if (!queued) break;
-        __builtin_amdgcn_s_waitcnt(0);                                    // every store of this chunk has been acknowledged
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __builtin_amdgcn_s_waitcnt(0);
-        if (threadIdx.x == 0) __hip_atomic_store(&queue[2 + inst], c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    MPCB_STREAM_QUEUE_LOOP(se::rollout<FT, true>(pb, params, rbd, ws_base, ws_stride, out, inst, s0, s1, yref_sched + (size_t)inst * rows * NTASK))
 #endif
 }
 
 namespace mpcb {
-
-const void *stream_rollout_ref_kernel() { return (const void *)mpc_stream_ref_kernel<double>; }
-
-void launch_stream_rollout_ref(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                               size_t ws_stride, const Outputs &out, int step0, int step1, int *queue, int chunk_steps,
-                               long long timeout_ticks, const double *yref_sched)
-{
-    hipLaunchKernelGGL(mpc_stream_ref_kernel<double>, grid, dim3(WAVE), 0, s, pb, rbd, params, ws_base, ws_stride, out, step0, step1, queue,
-                       chunk_steps, timeout_ticks, yref_sched);
-}
-
+StreamRolloutRefFn stream_rollout_ref_kernel() { return mpc_stream_ref_kernel<double>; }
 }  // namespace mpcb

@@ -13,6 +13,7 @@
 #ifndef MPCB_STREAM_WPE
 #define MPCB_STREAM_WPE 2
 #endif
+#include "mpc_launch.h"
 #include "mpc_stream.h"
 
 using namespace mpcb;
@@ -29,13 +30,5 @@ __global__ __launch_bounds__(WAVE, MPCB_STREAM_WPE) __attribute__((disable_tail_
 }
 
 namespace mpcb {
-
-const void *stream_step_kernel() { return (const void *)mpc_stream_step_kernel; }
-
-void launch_stream_step(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                        size_t ws_stride, const StepIO &io, int reset)
-{
-    hipLaunchKernelGGL(mpc_stream_step_kernel, grid, dim3(WAVE), 0, s, pb, rbd, params, ws_base, ws_stride, io, reset);
-}
-
+StreamStepFn stream_step_kernel() { return mpc_stream_step_kernel; }
 }  // namespace mpcb

@@ -9,6 +9,7 @@
 #ifndef MPCB_STREAM_WPE
 #define MPCB_STREAM_WPE 2
 #endif
+#include "mpc_launch.h"
 #include "mpc_stream.h"
 
 using namespace mpcb;
@@ -25,11 +26,5 @@ __global__ __launch_bounds__(WAVE, MPCB_STREAM_WPE) __attribute__((disable_tail_
 }
 
 namespace mpcb {
-
-void launch_stream_step_warm(dim3 grid, hipStream_t s, const Problem &pb, const Robot *rbd, const InstParams *params, double *ws_base,
-                             size_t ws_stride, const StepIO &io, int reset)
-{
-    hipLaunchKernelGGL(mpc_stream_step_warm_kernel, grid, dim3(WAVE), 0, s, pb, rbd, params, ws_base, ws_stride, io, reset);
-}
-
+StreamStepFn stream_step_warm_kernel() { return mpc_stream_step_warm_kernel; }
 }  // namespace mpcb

@@ -49,6 +49,22 @@ BOUNDARIES = {
     (8, 2): dict(pool=9152, sweep=[(1, "resident"), (26, "register")], merit=[(1, 128, 2), (128, 256, 2), (256, 512, 1)],
                  lanes_below_stages=512, seams=[113, 225, 337, 449]),
 }
+# The GPU tests force a geometry through MPCB_WAVES_PER_SIM and MPCB_SIMS_PER_CU.  PICKED_4_2 is (4, 2) as mpcb_setup picks it by itself at
+# two simulations per CU: only MPCB_SIMS_PER_CU is set, and the <4, 2> kernels (two wavefronts per SIMD, 256 registers) run -- forcing
+# MPCB_WAVES_PER_SIM = 4 as well selects the <4> kernels on the same pool.
+PICKED_4_2 = (4, 2, "picked")
+
+
+def force_geometry(monkeypatch, geo):
+    if geo != PICKED_4_2:
+        monkeypatch.setenv("MPCB_WAVES_PER_SIM", str(geo[0]))
+    monkeypatch.setenv("MPCB_SIMS_PER_CU", str(geo[1]))
+
+
+def geo_name(geo):
+    return "w%d_s%d" % geo[:2] + ("_picked" if geo == PICKED_4_2 else "")
+
+
 # (wavefronts, N, sweep) -> the smallest pool (doubles, even) at which horizon N takes that sweep
 EDGE_POOLS = {
     (4, 25, "resident"): 9052,     # lay_resident_ok: scratch of exactly 4096 doubles (the chunked factorisation's floor)

@@ -17,7 +17,7 @@ sys.path.insert(0, HERE)
 import dense_qp_cases as dc  # noqa: E402
 import sens_cases as scs  # noqa: E402
 import sens_checks as sc  # noqa: E402
-from test_boundaries import BOUNDARIES  # noqa: E402
+from test_boundaries import BOUNDARIES, PICKED_4_2, force_geometry, geo_name  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +25,12 @@ pytestmark = pytest.mark.gpu
 RUNS = [("latency", None, ("N1-rand",)), ("latency", None, ("N9-rand",)), ("latency", None, ("N80-rand",)), ("latency", None, ("N130-rand",)),
         ("stream", None, ("N1-rand",)), ("stream", None, ("N7-rand",)), ("stream", None, ("N40-rand",)),
         ("stream", None, ("N3-rand", "N12-rand", "N40-rand"))] + \
-       [("latency", geo, ("N%d-rand" % N,)) for geo in sorted(BOUNDARIES) for N in (20, 130)]
+       [("latency", geo, ("N%d-rand" % N,)) for geo in sorted(BOUNDARIES) for N in (20, 130)] + [("latency", PICKED_4_2, ("N20-rand",))]
 _MEASURED = {}
 
 
 def _run_id(r):
-    return "%s%s-%s" % (r[0], "" if r[1] is None else "-w%d_s%d" % r[1], "+".join(r[2]))
+    return "%s%s-%s" % (r[0], "" if r[1] is None else "-" + geo_name(r[1]), "+".join(r[2]))
 
 
 def _dump():
@@ -44,8 +44,7 @@ def _clean(monkeypatch, geo=None):
     for k in ("MPCB_WAVES_PER_SIM", "MPCB_SIMS_PER_CU", "MPCB_ENGINE"):
         monkeypatch.delenv(k, raising=False)
     if geo is not None:
-        monkeypatch.setenv("MPCB_WAVES_PER_SIM", str(geo[0]))
-        monkeypatch.setenv("MPCB_SIMS_PER_CU", str(geo[1]))
+        force_geometry(monkeypatch, geo)
 
 
 def _controller(cases, engine):
@@ -83,10 +82,10 @@ def test_reset_step_sensitivities_against_dense(monkeypatch, engine, geo, cids):
     ctl.close()
     assert info["engine"] == (1 if engine == "stream" else 0), info
     if geo is not None:
-        assert info["waves_per_sim"] == geo[0] and info["pool_bytes"] == 8 * BOUNDARIES[geo]["pool"], info
+        assert info["waves_per_sim"] == geo[0] and info["pool_bytes"] == 8 * BOUNDARIES[geo[:2]]["pool"], info
     Nmax = max(c["N"] for c in cases)
     assert out["du0_dx"].shape == (len(cases), 6, 12) and out["du0_dyref"].shape == (len(cases), Nmax, 5, 6)
-    tag = "%s%s" % (engine, "" if geo is None else "-w%d_s%d" % geo) + ("-ragged" if len(cases) > 1 else "")
+    tag = "%s%s" % (engine, "" if geo is None else "-" + geo_name(geo)) + ("-ragged" if len(cases) > 1 else "")
     for i, c in enumerate(cases):
         assert out["status"][i] == 0 and out["qp_iter"][i] == 1 and out["sens_valid"][i] == 1, (c["id"], out["qp_iter"][i])
         # (rows past the simulation's own horizon are exactly zero: checked inside)

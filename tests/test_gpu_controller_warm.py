@@ -58,10 +58,12 @@ def _schedule(cfgs, N, k):
 
 
 @pytest.mark.parametrize("engine", ["latency", "stream"])
-@pytest.mark.parametrize("N,B,waves", [(1, 8, None), (2, 8, None), (20, 8, None), (100, 8, 8), (40, 6, 4)])
-def test_shifted_rti_step_is_the_exact_qp_step_from_the_shifted_iterate(orc, ur10_rb, engine, N, B, waves):
+@pytest.mark.parametrize("N,B,waves", [(1, 8, None), (2, 8, None), (20, 8, None), (100, 8, 8), (40, 6, 4), (12, 3, 2), (12, 3, 1)])
+def test_shifted_rti_step_is_the_exact_qp_step_from_the_shifted_iterate(orc, ur10_rb, monkeypatch, engine, N, B, waves):
     from robotic_mpc_amd import BatchController, robots
 
+    if waves is not None and waves < 4:      # <2> and <1>: mpcb_setup never picks them by itself
+        monkeypatch.setenv("MPCB_WAVES_PER_SIM", str(waves))
     steps = 12
     raw = _raw(B, N, steps, seed=4, so=TIGHT_QP)
     cfgs = _resolve(raw)

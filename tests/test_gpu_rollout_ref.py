@@ -157,8 +157,11 @@ def _tracking_case(orc, ur10, monkeypatch, eng, raw, waves, logged_sign_change, 
 
 
 # ------------------------------------------------------------------------------------------------------------ latency engine
-@pytest.mark.parametrize("n,N,steps,waves,logged", [(4, 12, 14, 4, True), (3, 100, 6, 8, False), (2, 224, 3, 8, False)])
+@pytest.mark.parametrize("n,N,steps,waves,logged", [(4, 12, 14, 4, True), (3, 100, 6, 8, False), (2, 224, 3, 8, False),
+                                                    (4, 12, 14, 2, True), (4, 12, 14, 1, True)])
 def test_latency_engine_tracks_the_schedule(orc, ur10, monkeypatch, n, N, steps, waves, logged):
+    if waves < 4:      # <2> and <1>: mpcb_setup never picks them by itself
+        monkeypatch.setenv("MPCB_WAVES_PER_SIM", str(waves))
     _tracking_case(orc, ur10, monkeypatch, "latency", _raw(n, N, steps, seed=1), waves, logged)
 
 

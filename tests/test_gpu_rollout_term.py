@@ -106,8 +106,10 @@ def _case(orc, ur10, monkeypatch, eng, raw, seed, waves, check=None, weights=trc
 
 
 # ------------------------------------------------------------------------------------------------------------ latency engine
-@pytest.mark.parametrize("n,N,steps,waves", [(4, 12, 14, 4), (3, 100, 6, 8), (2, 224, 3, 8)])
+@pytest.mark.parametrize("n,N,steps,waves", [(4, 12, 14, 4), (3, 100, 6, 8), (2, 224, 3, 8), (4, 12, 14, 2), (4, 12, 14, 1)])
 def test_latency_engine_with_a_terminal_cost_over_the_perturbed_plant(orc, ur10, monkeypatch, n, N, steps, waves):
+    if waves < 4:      # <2> and <1>: mpcb_setup never picks them by itself
+        monkeypatch.setenv("MPCB_WAVES_PER_SIM", str(waves))
     _case(orc, ur10, monkeypatch, "latency", tp._raw(n, N, steps, seed=1), 1, waves)
 
 

@@ -18,7 +18,7 @@ import dense_qp as dq  # noqa: E402
 import dense_qp_cases as dc  # noqa: E402
 import dense_qp_terminal as dqt  # noqa: E402
 import terminal_cases as tc  # noqa: E402
-from test_boundaries import BOUNDARIES, _named  # noqa: E402
+from test_boundaries import BOUNDARIES, PICKED_4_2, _named, force_geometry, geo_name  # noqa: E402
 from test_gpu_dense_qp import GEOMETRY_HORIZONS  # noqa: E402
 from test_terminal_cases import BY_ID, CASES, chained_tolerance, check_step, record  # noqa: E402
 
@@ -33,18 +33,18 @@ FORCED = {geo: (20, BOUNDARIES[geo]["sweep"][1][0] - 1, BOUNDARIES[geo]["sweep"]
           for geo, Ns in GEOMETRY_HORIZONS.items()}
 RUNS = [(e, None, N) for e in ("stream", "latency") for N in sorted(GROUPS)] + \
        [("latency", geo, N) for geo in sorted(FORCED) for N in FORCED[geo]]
+PICKED = [("latency", PICKED_4_2, 20)]      # beside the table that test_run_list_is_complete counts
 
 
 def _run_id(r):
-    return "%s%s-N%d" % (r[0], "" if r[1] is None else "-w%d_s%d" % r[1], r[2])
+    return "%s%s-N%d" % (r[0], "" if r[1] is None else "-" + geo_name(r[1]), r[2])
 
 
 def _clean(monkeypatch, geo=None):
     for k in ("MPCB_WAVES_PER_SIM", "MPCB_SIMS_PER_CU", "MPCB_ENGINE"):
         monkeypatch.delenv(k, raising=False)
     if geo is not None:
-        monkeypatch.setenv("MPCB_WAVES_PER_SIM", str(geo[0]))
-        monkeypatch.setenv("MPCB_SIMS_PER_CU", str(geo[1]))
+        force_geometry(monkeypatch, geo)
 
 
 def controller(cases, engine, terminal=True):
@@ -69,7 +69,7 @@ def test_run_list_is_complete():
     assert {BY_ID[c]["active"] for c in GROUPS[20]} == {False, True} and {BY_ID[c]["fast"] for c in GROUPS[20]} == {False, True}
 
 
-@pytest.mark.parametrize("engine,geo,N", RUNS, ids=[_run_id(r) for r in RUNS])
+@pytest.mark.parametrize("engine,geo,N", RUNS + PICKED, ids=[_run_id(r) for r in RUNS + PICKED])
 def test_reset_step_against_dense(monkeypatch, engine, geo, N):
     _clean(monkeypatch, geo)
     cases = [BY_ID[c] for c in GROUPS[N]]
@@ -79,9 +79,9 @@ def test_reset_step_against_dense(monkeypatch, engine, geo, N):
     ctl.close()
     assert info["engine"] == (1 if engine == "stream" else 0), info
     if geo is not None:
-        assert info["waves_per_sim"] == geo[0] and info["pool_bytes"] == 8 * BOUNDARIES[geo]["pool"], info
+        assert info["waves_per_sim"] == geo[0] and info["pool_bytes"] == 8 * BOUNDARIES[geo[:2]]["pool"], info
     for i, c in enumerate(cases):
-        check_step(c, out, i, "%s%s" % (engine, "" if geo is None else "-w%d_s%d" % geo), rtol_cost=1e-9)
+        check_step(c, out, i, "%s%s" % (engine, "" if geo is None else "-" + geo_name(geo)), rtol_cost=1e-9)
 
 
 def test_ragged_batch_on_the_stream_engine():

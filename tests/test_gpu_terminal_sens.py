@@ -1,7 +1,7 @@
 """BatchController.step(sens=True) with a terminal cost in force on the device (mpcb_step_term with sens, both engines): du0_dx,
 du0_dyref and du0_dxe against central differences of the dense KKT solve of the terminal QP, under the bounds of
 tests/test_terminal_sens.py: reset steps at N = 1, 2, 7, 20 and a stage-varying iterate, at the default geometry and at the forced
-latency geometries (1, 1), (4, 1), (8, 2)."""
+latency geometries (1, 1), (2, 1), (4, 1), (8, 2) and (4, 2) as mpcb_setup picks it."""
 import os
 import sys
 
@@ -13,14 +13,16 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 import terminal_cases as tc  # noqa: E402
+from test_boundaries import PICKED_4_2, geo_name  # noqa: E402
 from test_gpu_terminal import _clean, controller, numpy_step  # noqa: E402
 from test_terminal_cases import BY_ID, CHAINED_ORACLE_VS_DENSE_TERM, ORACLE_VS_DENSE_TERM  # noqa: E402
 from test_terminal_sens import RESET_HORIZONS, check_sens, reset_reference, stage_varying  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-GEOS = [("stream", None), ("latency", None), ("latency", (1, 1)), ("latency", (4, 1)), ("latency", (8, 2))]
-IDS = ["%s%s" % (e, "" if g is None else "-w%d_s%d" % g) for e, g in GEOS]
+GEOS = [("stream", None), ("latency", None), ("latency", (1, 1)), ("latency", (4, 1)), ("latency", (8, 2)), ("latency", (2, 1)),
+        ("latency", PICKED_4_2)]
+IDS = ["%s%s" % (e, "" if g is None else "-" + geo_name(g)) for e, g in GEOS]
 
 
 @pytest.mark.parametrize("engine,geo", GEOS, ids=IDS)
