@@ -64,6 +64,26 @@ constexpr int L2W = 114;
 #ifndef MPCB_FACT_PIPE
 #define MPCB_FACT_PIPE 1
 #endif
+// 1 (default): the recursion wavefront of the factorisation sweep takes LDS waits off its chain: the address of the K / R~^-1 column
+// is complete before the stage loop, phase B issues the reads of phase CA that do not depend on it (carried across the wave fence in
+// registers), and phase CA issues its K reads ahead of the K-independent arithmetic; 0: every read where it is used (A/B builds).
+// Reads move, no operation changes: the two builds agree bit for bit.  (It builds on MPCB_FACT_PIPE's phase B.)
+#ifndef MPCB_FACT_AHEAD
+#define MPCB_FACT_AHEAD 1
+#endif
+#if MPCB_FACT_AHEAD && MPCB_FACT_PIPE && !defined(MPCB_DIAG_NO_B) && !defined(MPCB_DIAG_NO_CA) && !defined(MPCB_DIAG_NO_LDL)
+#define MPCB_AHEAD_ON 1
+#else
+#define MPCB_AHEAD_ON 0
+#endif
+// Nothing is scheduled across this point on the device (compiler only, no instruction): pins the issue order of LDS reads against
+// arithmetic where MPCB_FACT_AHEAD places them.  Nothing to do in the host emulation.
+MPC_HD void sched_fence()
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
 #ifdef MPCB_PROFILE
 #define PROF_T0(v) const double v = ex.clock()
 #define PROF_ADD(i, v) prof[i] += ex.clock() - v
@@ -1154,6 +1174,21 @@ struct Engine {
     //       lane; lanes 40..51: m~ = p_{k+1} + P_{k+1} rb_k
     //   CA: P_k block = A'MA + H_xx + Gamma_q - S~' Kfb  (-> registers, LDS record), then at once
     //       R~, S~ of stage k-1; lanes 40..51: h_u, p_k
+    // Order of the LDS reads on the recursion wavefront (MPCB_FACT_AHEAD, the default; the instruction stream is checked against
+    // this, see profiles/fact_ahead_ab.txt):
+    //   B : R~ and the lane's right-hand side (14 reads), the first pivot as soon as R~(0,0) has landed, and behind the first
+    //       pivot's elimination the 14 reads of phase CA that do not depend on this phase: the lane's two columns of S~, then the
+    //       linearisation operands of the stage (ga, gb, gva, gvb, Gamma_q, Gamma_u).  They land under pivots 1..5 and cross the
+    //       wave fence in registers (28 doubles).  Nothing inside the stage loop is a scalar load: the address of the lane's
+    //       K / R~^-1 column is complete, pool base included, before the loop (a scalar load shares the LDS counter and returns
+    //       out of order, so every wait behind one is a full drain).
+    //   CA: the K reads first, directly behind the fence; the K-independent part of P_k (A'MA + H_xx + Gamma_q, from registers)
+    //       runs under their write -> read round trip, then the 24 K-dependent FMAs.  sched_fence() holds reads and
+    //       arithmetic in that issue order.
+    // With MPCB_FACT_AHEAD=0 every operand is read where it is used (CA: linearisation, S~, K, then all of the arithmetic; the
+    // K-independent part does NOT run under K's round trip there, the compiler schedules it in front of the S~ / K reads).
+    // The arithmetic of both phases and of next_stage is written with explicit fused multiply-adds (fmad) under contract(off): one evaluation order for
+    // every instantiation, every build switch and the host emulation.
     struct FactLane {
         double b1a, b2a, b1b, b2b, a12a, a22a, a12b, a22b;
         double hu_c;     // dt (2 w_u + w_qddot c_a^2 + lm) on the diagonal of R~, 0 off it
@@ -1185,6 +1220,12 @@ struct Engine {
         typename Ex::template PerLane<FactLane> fl;
         // MPCB_FACT_PIPE: where the lane stores its column of K / R~^-1: offset of the chunk, doubles per stage, doubles per row
         typename Ex::template PerLane<int> scb, sks, sst;
+#if MPCB_AHEAD_ON
+        typename Ex::template PerLane<double *> xcol;    // that column's address at stage 0 of the chunk's numbering (complete: pool included)
+        typename Ex::template PerLane<double> ah_s[12];  // the lane's two columns of S~ (sa, sva), read a phase ahead
+        typename Ex::template PerLane<double> ah_g[14];  // ga0..4, gb0..4, gva, gvb, Gamma_q, Gamma_u of the stage, read a phase ahead
+        (void)scb;
+#endif
         ex.seq([&](int lane) {
             sks.at(lane) = RES && lane < 12 ? 72 : WF;
             sst.at(lane) = lane < 12 ? 12 : 6;
@@ -1232,19 +1273,25 @@ struct Engine {
         // R~, S~ of stage `kd` from the lane's block of P_{kd+1}; also the A'MA block for stage kd
         // (gam_u = Gamma_u[a] of stage kd, loaded by the caller together with its other LDS reads: a load
         // inside the a == b branch would put a whole LDS round trip on the critical path)
+        // Evaluation order (every multiply-add below, phase B and the P_k block included): written out with fmad (mpc_ipm.h) under contract(off),
+        // so that it is the same in every instantiation and in the host emulation.  It is the order the <8,1> MODE 1 build had when
+        // contraction was left to the compiler: of a sum of two products one is rounded on its own, the other is fused into the add.
         auto next_stage = [&](int lane, FactLane &f, double gam_u, int sb) {
-            const double fq = f.b1a * f.mqq + f.b2a * f.mvq, fv = f.b1a * f.mqv + f.b2a * f.mvv;
-            double r = fq * f.b1b + fv * f.b2b + f.hu_c;
+#pragma clang fp contract(off)
+            const double fq = fmad(f.b2a, f.mvq, f.b1a * f.mqq);       // b1a mqq rounded, b2a mvq fused
+            const double fv = fmad(f.b1a, f.mqv, f.b2a * f.mvv);       // b2a mvv rounded, b1a mqv fused
+            double r = fmad(fq, f.b1b, fv * f.b2b) + f.hu_c;           // fv b2b rounded, fq b1b fused, then + hu_c
             r += f.a == f.b ? gam_u : 0.0;
             sm.Rt[f.a * 6 + f.b] = r;
             double *St = sm.St2[sb];
             St[f.a * 12 + f.b] = fq;
-            St[f.a * 12 + 6 + f.b] = fq * f.a12b + fv * f.a22b - f.huv_c;
-            const double cq = f.a12a * f.mqq + f.a22a * f.mvq, cv = f.a12a * f.mqv + f.a22a * f.mvv;
+            St[f.a * 12 + 6 + f.b] = fmad(fq, f.a12b, fv * f.a22b) - f.huv_c;   // fv a22b rounded, fq a12b fused, then - huv_c
+            const double cq = fmad(f.a12a, f.mqq, f.a22a * f.mvq);     // a22a mvq rounded, a12a mqq fused
+            const double cv = fmad(f.a12a, f.mqv, f.a22a * f.mvv);     // a22a mvv rounded, a12a mqv fused
             f.qqq = f.mqq;
-            f.qqv = f.mqq * f.a12b + f.mqv * f.a22b;
+            f.qqv = fmad(f.mqq, f.a12b, f.mqv * f.a22b);               // mqv a22b rounded, mqq a12b fused
             f.qvq = cq;
-            f.qvv = cq * f.a12b + cv * f.a22b;
+            f.qvv = fmad(cq, f.a12b, cv * f.a22b);                     // cv a22b rounded, cq a12b fused
             (void)lane;
         };
         // Three roles per window (Ex::overlap3), chunk index ci counts down the horizon:
@@ -1360,6 +1407,16 @@ struct Engine {
             double *vr = vr_of(ci), *vf = vf_of(ci);
             ex.await(&sm.flg[0], NBW * (ci + 1));          // this chunk's inputs have landed
             if (ci >= 2) ex.await(&sm.flg[1], NBW * ci);   // the factor buffer (that of chunk ci-2) is free
+#if MPCB_AHEAD_ON
+            // where the lane's column goes: K (the resident array, or the chunk record) for lanes < 12, R~^-1 (the chunk record) for
+            // the others; per stage it moves by `sks` doubles.  The whole address, once per chunk: nothing of it is looked up inside
+            // the stage loop (the pool's base is a scalar load, which would share the LDS counter there and force full drains)
+            ex.seq([&](int lane) {
+                double *rec = vf - (size_t)k0 * WF - FO;
+                double *kcol = RES ? rm.K + lane : rec + O_K + lane;
+                xcol.at(lane) = lane < 12 ? kcol : rec + O_RI + (lane - 12);
+            });
+#endif
             for (int k = k1; k >= k0; k--) {
                 const double *ric = vr + (size_t)(k - kl) * WR;
                 const double *ricd = ric - WR;           // stage k-1 (valid for k >= 1)
@@ -1405,11 +1462,90 @@ struct Engine {
                     continue;
                 }
                 // ---- B: LDL' (right-looking) + one right-hand side per lane
-#if !defined(MPCB_DIAG_NO_B) && MPCB_FACT_PIPE
+#if MPCB_AHEAD_ON
+                // MPCB_FACT_PIPE's phase B (below) with the reads placed along the pivot chain.  LDS returns in issue order and the
+                // counter tells at most 15 reads apart (a wait with more than that behind it waits for them too), so:
+                //   this phase's own reads first, R~ in front of the lane's right-hand side: 14 reads, the first pivot starts when
+                //   its own operand has landed;
+                //   behind the first pivot's elimination (R~ is in registers by then) what phase CA reads and this phase does not
+                //   write -- the lane's two columns of S~ and the linearisation operands of the stage, 14 reads -- in flight under
+                //   the rest of the chain, and carried across the wave fence in registers.
+                // The chain runs in the lanes that store (< 18), in two pieces under that one condition: written out, because the
+                // compiler gathers the chain into the storing lanes' branch anyway, and reads placed between its pieces in the source
+                // would all end up in front of it.  The reads run in every lane (a = b = 0 beyond lane 35).
+                ex.seq([&](int lane) {
+#pragma clang fp contract(off)
+                    const double *St = sm.St2[sb];
+                    const FactLane &f = fl.at(lane);
+                    const bool act = lane < 18;
+                    double A_[6][6];
+#pragma unroll
+                    for (int i = 0; i < 6; i++)
+#pragma unroll
+                        for (int j = 0; j <= i; j++) A_[i][j] = sm.Rt[i * 6 + j];
+                    double x[6], dinv[6];
+                    const int col = lane < 12 ? lane : 0;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) x[i] = St[i * 12 + col];   // unconditional loads, then select
+                    sched_fence();
+                    // column j of the LDL', and of L y = rhs once L(.,j) exists: the operations of the branch below
+                    auto ldl_column = [&](int j) {
+                        dinv[j] = fast_rcp(A_[j][j]);
+                        double lj[6];
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++) lj[i] = A_[i][j] * dinv[j];
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++)
+#pragma unroll
+                            for (int r = j + 1; r <= i; r++) A_[i][r] = fmad(-lj[i], A_[r][j], A_[i][r]);   // every update fused
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++) A_[i][j] = lj[i];   // L(i,j)
+                    };
+                    auto rhs_column = [&](int j) {
+#pragma unroll
+                        for (int i = j + 1; i < 6; i++) x[i] = fmad(-A_[i][j], x[j], x[i]);
+                    };
+                    if (act) ldl_column(0);
+                    {
+                        const double *gq = ric, *gv = ric + 30;
+                        // stage 0 has no stage below it: Gamma_u's address is clamped to its own row (phase CA uses neither there)
+                        const double *gu = (k > 0 ? ricd : ric) + 36;
+                        sched_fence();
+#pragma unroll
+                        for (int m = 0; m < 6; m++) { ah_s[m].at(lane) = St[m * 12 + f.a]; ah_s[6 + m].at(lane) = St[m * 12 + 6 + f.a]; }
+#pragma unroll
+                        for (int i = 0; i < 5; i++) { ah_g[i].at(lane) = gq[6 * i + f.a]; ah_g[5 + i].at(lane) = gq[6 * i + f.b]; }
+                        ah_g[10].at(lane) = gv[f.a]; ah_g[11].at(lane) = gv[f.b];
+                        ah_g[12].at(lane) = gam[6 + f.a]; ah_g[13].at(lane) = gu[f.a];
+                        sched_fence();
+                    }
+                    if (act) {
+#pragma unroll
+                        for (int i = 0; i < 6; i++) x[i] = lane < 12 ? x[i] : (i == lane - 12 ? 1.0 : 0.0);
+                        rhs_column(0);
+#pragma unroll
+                        for (int j = 1; j < 6; j++) { ldl_column(j); rhs_column(j); }
+                        // D^-1 y and L' x = y, column oriented, in the order described below
+                        x[5] *= dinv[5];
+#pragma unroll
+                        for (int i = 0; i < 5; i++) x[i] = fmad(x[i], dinv[i], -(A_[5][i] * x[5]));
+#pragma unroll
+                        for (int j = 4; j >= 0; j--) {
+#pragma unroll
+                            for (int i = 0; i < j; i++) x[i] = fmad(-A_[j][i], x[j], x[i]);
+                        }
+                        double *xp = xcol.at(lane) + k * sks.at(lane);
+                        const int st = sst.at(lane);
+#pragma unroll
+                        for (int i = 0; i < 6; i++) xp[i * st] = x[i];
+                    }
+                });
+#elif !defined(MPCB_DIAG_NO_B) && MPCB_FACT_PIPE
                 // The right-hand side is loaded with R~ and eliminated column by column as L appears (the same products in the same
                 // order per x[i] as a forward solve behind the loop); every lane does it, only lanes < 18 store, through one
                 // per-lane address: no exec-mask branches around the solve or between the K and the R~^-1 columns.
                 ex.seq([&](int lane) {
+#pragma clang fp contract(off)
                     const double *St = sm.St2[sb];
                     double A_[6][6];
 #pragma unroll
@@ -1442,18 +1578,21 @@ struct Engine {
 #pragma unroll
                         for (int i = j + 1; i < 6; i++)
 #pragma unroll
-                            for (int r = j + 1; r <= i; r++) A_[i][r] -= lj[i] * A_[r][j];
+                            for (int r = j + 1; r <= i; r++) A_[i][r] = fmad(-lj[i], A_[r][j], A_[i][r]);   // every update fused
 #pragma unroll
                         for (int i = j + 1; i < 6; i++) A_[i][j] = lj[i];   // L(i,j)
 #pragma unroll
-                        for (int i = j + 1; i < 6; i++) x[i] -= lj[i] * x[j];   // L y = rhs: column j, as soon as it exists
+                        for (int i = j + 1; i < 6; i++) x[i] = fmad(-lj[i], x[j], x[i]);   // L y = rhs: column j, as soon as it exists
                     }
+                    // D^-1 y and L' x = y, column oriented.  The scaling of x[i] is fused with the first back-substitution term:
+                    // x[i] = y[i] dinv[i] - L(5,i) x[5] with the SECOND product rounded; the columns 4..1 follow as fused updates
+                    x[5] *= dinv[5];
 #pragma unroll
-                    for (int i = 0; i < 6; i++) x[i] *= dinv[i];
+                    for (int i = 0; i < 5; i++) x[i] = fmad(x[i], dinv[i], -(A_[5][i] * x[5]));
 #pragma unroll
-                    for (int j = 5; j >= 0; j--) {         // L' x = y, column oriented
+                    for (int j = 4; j >= 0; j--) {
 #pragma unroll
-                        for (int i = 0; i < j; i++) x[i] -= A_[j][i] * x[j];
+                        for (int i = 0; i < j; i++) x[i] = fmad(-A_[j][i], x[j], x[i]);
                     }
                     if (lane < 18) {
                         double *xp = ex.pool() + (scb.at(lane) + k * sks.at(lane));
@@ -1464,6 +1603,7 @@ struct Engine {
                 });
 #elif !defined(MPCB_DIAG_NO_B)
                 ex.seq([&](int lane) {
+#pragma clang fp contract(off)
                     const double *St = sm.St2[sb];
                     double A_[6][6];
 #pragma unroll
@@ -1483,7 +1623,7 @@ struct Engine {
 #pragma unroll
                         for (int i = j + 1; i < 6; i++)
 #pragma unroll
-                            for (int r = j + 1; r <= i; r++) A_[i][r] -= lj[i] * A_[r][j];
+                            for (int r = j + 1; r <= i; r++) A_[i][r] = fmad(-lj[i], A_[r][j], A_[i][r]);   // every update fused
 #pragma unroll
                         for (int i = j + 1; i < 6; i++) A_[i][j] = lj[i];   // L(i,j)
                     }
@@ -1497,14 +1637,16 @@ struct Engine {
 #pragma unroll
                         for (int j = 0; j < 6; j++) {          // L y = rhs, column oriented
 #pragma unroll
-                            for (int i = j + 1; i < 6; i++) x[i] -= A_[i][j] * x[j];
+                            for (int i = j + 1; i < 6; i++) x[i] = fmad(-A_[i][j], x[j], x[i]);
                         }
+                        // D^-1 y and L' x = y, column oriented: as in the branch above
+                        x[5] *= dinv[5];
 #pragma unroll
-                        for (int i = 0; i < 6; i++) x[i] *= dinv[i];
+                        for (int i = 0; i < 5; i++) x[i] = fmad(x[i], dinv[i], -(A_[5][i] * x[5]));
 #pragma unroll
-                        for (int j = 5; j >= 0; j--) {         // L' x = y, column oriented
+                        for (int j = 4; j >= 0; j--) {
 #pragma unroll
-                            for (int i = 0; i < j; i++) x[i] -= A_[j][i] * x[j];
+                            for (int i = 0; i < j; i++) x[i] = fmad(-A_[j][i], x[j], x[i]);
                         }
                         if (lane < 12) {
 #pragma unroll
@@ -1518,6 +1660,7 @@ struct Engine {
 #endif
                 // ---- CA: P_k block, then R~/S~ of stage k-1
                 ex.seq([&](int lane) {
+#pragma clang fp contract(off)
 #ifdef MPCB_DIAG_NO_CA
                     if (lane == 0) ex.post(&sm.prog, Nl - k);
                     return;
@@ -1525,10 +1668,27 @@ struct Engine {
                     if (lane < 36) {
                         FactLane &f = fl.at(lane);
                         if (k > 0) {
+#if MPCB_AHEAD_ON
+                            // K first, directly behind the fence: its write -> read round trip runs under the K-independent part of
+                            // P_k, whose operands phase B has read (the hook keeps the arithmetic behind the reads in the issue order)
+                            double sa[6], sva[6], kb[6], kvb[6];
+#pragma unroll
+                            for (int m = 0; m < 6; m++) { kb[m] = kk[m * 12 + f.b]; kvb[m] = kk[m * 12 + 6 + f.b]; }
+                            sched_fence();
+#pragma unroll
+                            for (int m = 0; m < 6; m++) { sa[m] = ah_s[m].at(lane); sva[m] = ah_s[6 + m].at(lane); }
+                            const double ga0 = ah_g[0].at(lane), ga1 = ah_g[1].at(lane), ga2 = ah_g[2].at(lane), ga3 = ah_g[3].at(lane),
+                                         ga4 = ah_g[4].at(lane);
+                            const double gb0 = ah_g[5].at(lane), gb1 = ah_g[6].at(lane), gb2 = ah_g[7].at(lane), gb3 = ah_g[8].at(lane),
+                                         gb4 = ah_g[9].at(lane);
+                            const double gva = ah_g[10].at(lane), gvb = ah_g[11].at(lane);
+                            const double gam_q = ah_g[12].at(lane), gam_u = ah_g[13].at(lane);
+#else
                             const double *St = sm.St2[sb];
                             const double *gq = ric, *gv = ric + 30;
-                            // Operands in the order they can be used (LDS returns in issue order): the linearisation and S~ do not
-                            // depend on phase B, K does -- its write -> read round trip runs under the K-independent part of P_k.
+                            // Operands in the order they can be used (LDS returns in issue order): the linearisation and S~ first (they
+                            // do not depend on phase B), then K.  (The empty asm orders memory operations only: the arithmetic is
+                            // scheduled in front of the S~ / K reads all the same.)
                             const double ga0 = gq[f.a], ga1 = gq[6 + f.a], ga2 = gq[12 + f.a], ga3 = gq[18 + f.a], ga4 = gq[24 + f.a];
                             const double gb0 = gq[f.b], gb1 = gq[6 + f.b], gb2 = gq[12 + f.b], gb3 = gq[18 + f.b], gb4 = gq[24 + f.b];
                             const double gva = gv[f.a], gvb = gv[f.b];
@@ -1541,15 +1701,21 @@ struct Engine {
 #if defined(__HIP_DEVICE_COMPILE__)
                             asm volatile("" ::: "memory");    // keep that issue order
 #endif
-                            double pqq = f.qqq + (dw0 * ga0 * gb0 + dw1 * ga1 * gb1 + dw2 * ga2 * gb2 + dw3 * ga3 * gb3 + dw4 * ga4 * gb4) + f.lm_c;
-                            double pqv = f.qqv + dw4 * ga4 * gvb;
-                            double pvq = f.qvq + dw4 * gva * gb4;
-                            double pvv = f.qvv + dw4 * gva * gvb + (f.huv_c + f.lm_c);
+#endif
+                            // the task Hessian: (dw1 ga1) gb1 rounded, then the terms 0, 2, 3, 4 fused onto it in that order, each
+                            // as (dw_i ga_i) rounded times gb_i; the single terms of the other three blocks fused onto A'MA
+                            double hq = (dw1 * ga1) * gb1;
+                            hq = fmad(dw0 * ga0, gb0, hq); hq = fmad(dw2 * ga2, gb2, hq); hq = fmad(dw3 * ga3, gb3, hq);
+                            hq = fmad(dw4 * ga4, gb4, hq);
+                            double pqq = (f.qqq + hq) + f.lm_c;
+                            double pqv = fmad(dw4 * ga4, gvb, f.qqv);
+                            double pvq = fmad(dw4 * gva, gb4, f.qvq);
+                            double pvv = fmad(dw4 * gva, gvb, f.qvv) + (f.huv_c + f.lm_c);
                             pqq += f.a == f.b ? gam_q : 0.0;
 #pragma unroll
-                            for (int m = 0; m < 6; m++) {
-                                pqq -= sa[m] * kb[m]; pqv -= sa[m] * kvb[m];
-                                pvq -= sva[m] * kb[m]; pvv -= sva[m] * kvb[m];
+                            for (int m = 0; m < 6; m++) {           // - S~' K: every term fused, m ascending
+                                pqq = fmad(-sa[m], kb[m], pqq); pqv = fmad(-sa[m], kvb[m], pqv);
+                                pvq = fmad(-sva[m], kb[m], pvq); pvv = fmad(-sva[m], kvb[m], pvv);
                             }
                             f.mqq = pqq; f.mqv = pqv; f.mvq = pvq; f.mvv = pvv;
                             // R~, S~ of stage k-1 first (the next phase B waits for them), then the record of P_k

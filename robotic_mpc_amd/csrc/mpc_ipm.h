@@ -23,6 +23,18 @@ MPC_HD double fast_rcp(double d)
 #endif
 }
 
+// a b + c where the latency engine's Riccati stage pins its evaluation order (mpc_core.h fact_pass_t, under contract(off)): one rounding
+// on the device.  The host emulation rounds the product on its own, as its build (-ffp-contract=off) always has: it is held to the
+// oracle's unfused arithmetic at 1e-11, and the operands are in the order that gives it the sums it formed before.
+MPC_HD double fmad(double a, double b, double c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fma(a, b, c);
+#else
+    return a * b + c;
+#endif
+}
+
 namespace ipm {
 
 // which (stage, bounded component) pairs carry constraints (trajectory_optimizer.py:164-171): inputs j < 6 on stages 0..N-1,
