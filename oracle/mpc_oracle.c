@@ -926,6 +926,7 @@ struct orc_solver {
     unsigned char *mask;
     int fast_skip, fast_back; /* fast path: QPs left before the next attempt; length of the current suspension */
     int n_fast, n_reject;  /* diagnostics: accepted / rejected attempts */
+    double *yref;          /* per-stage task targets [N, 5], or NULL: the packed [0, 1, 0, px_ref, vy_ref] at every stage */
 };
 
 orc_solver *orc_solver_create(const orc_robot *rb, const orc_params *p)
@@ -970,8 +971,28 @@ void orc_solver_destroy(orc_solver *s)
     free(s->qw); free(s->qpi); free(s->qlam); free(s->qt);
     free(s->r); free(s->H); free(s->g); free(s->b); free(s->lb); free(s->ub);
     free(s->mw_dyn); free(s->mw_ineq); free(s->tx); free(s->tu);
-    free(s->wsmem); free(s->mask);
+    free(s->wsmem); free(s->mask); free(s->yref);
     free(s);
+}
+
+/* Task targets per stage, yref [N, 5] (copied), for every later step; NULL goes back to the packed targets. */
+void orc_solver_set_reference(orc_solver *s, const double *yref)
+{
+    free(s->yref);
+    s->yref = NULL;
+    if (!yref) return;
+    s->yref = (double *)malloc((size_t)s->N * 5 * sizeof(double));
+    if (s->yref) memcpy(s->yref, yref, (size_t)s->N * 5 * sizeof(double));
+}
+
+/* orc_stage_residual of stage k with its task rows taken against the solver's reference */
+static void solver_stage_residual(const orc_solver *s, int k, const double *x, const double *u, double *r, double *Jr)
+{
+    orc_stage_residual(&s->rb, &s->p, x, u, r, Jr);
+    if (s->yref) {
+        const double gref[5] = {0.0, 1.0, 0.0, s->p.px_ref, s->p.vy_ref};
+        for (int i = 0; i < 5; i++) r[i] += gref[i] - s->yref[(size_t)k * 5 + i];
+    }
 }
 
 void orc_solver_get_iterate(const orc_solver *s, double *x, double *u, double *pi)
@@ -994,7 +1015,7 @@ static double eval_cost(const orc_solver *s, const double *x, const double *u)
     double W[NR], r[NR], c = 0;
     weights17(&s->p, W);
     for (int k = 0; k < s->N; k++) {
-        orc_stage_residual(&s->rb, &s->p, x + (size_t)k * 12, u + (size_t)k * 6, r, NULL);
+        solver_stage_residual(s, k, x + (size_t)k * 12, u + (size_t)k * 6, r, NULL);
         double sk = 0;
         for (int i = 0; i < NR; i++) sk += W[i] * r[i] * r[i];
         c += 0.5 * s->p.dt * sk;
@@ -1018,7 +1039,7 @@ static void linearize(orc_solver *s)
         memset(Hk, 0, 324 * sizeof(double));
         memset(gk, 0, 18 * sizeof(double));
         if (k < N) {
-            orc_stage_residual(&s->rb, &s->p, xk, uk, rk, Jr);
+            solver_stage_residual(s, k, xk, uk, rk, Jr);
             double sk = 0;
             for (int i = 0; i < NR; i++) sk += W[i] * rk[i] * rk[i];
             s->cost += 0.5 * s->p.dt * sk;

@@ -131,6 +131,8 @@ int orc_solver_step(orc_solver *s, const double *xhat, double *u0, int *sqp_iter
                     double *res4, double *cost);
 /* copy out the iterate: x[N+1][12], u[N][6], pi[N][12] */
 void orc_solver_get_iterate(const orc_solver *s, double *x, double *u, double *pi);
+/* task targets per stage, yref[N][5] (copied), for every later step; NULL: the packed targets [0, 1, 0, px_ref, vy_ref] */
+void orc_solver_set_reference(orc_solver *s, const double *yref);
 
 #ifdef __cplusplus
 }

@@ -222,6 +222,11 @@ class Solver:
                                    C.byref(sqp), C.byref(qp), _ptr(res), C.byref(cost))
         return dict(status=st, u0=u0, sqp_iter=sqp.value, qp_iter=qp.value, res=res, cost=cost.value)
 
+    def set_reference(self, yref):
+        """Per-stage task targets yref [N, 5] for every later step; None goes back to the packed targets."""
+        y = None if yref is None else np.ascontiguousarray(yref, dtype=np.float64).reshape(self.N, 5)
+        lib().orc_solver_set_reference(self._h, None if y is None else _ptr(y))
+
     def iterate(self):
         x = np.zeros((self.N + 1, 12)); u = np.zeros((self.N, 6)); pi = np.zeros((self.N, 12))
         lib().orc_solver_get_iterate(self._h, _ptr(x), _ptr(u), _ptr(pi))

@@ -232,6 +232,7 @@ def solve_equality(qp, fixed_idx=(), fixed_val=()):
     and every other bound ignored.  Pivoted sparse LU of the full KKT matrix, then iterative refinement with the residual in
     np.longdouble until the correction is below 1e-15 relative or three steps are taken.  Returns dict(w: flat solution,
     dX, dU, mult: multipliers of the fixed components (sign of the Lagrangian 1/2 w'Hw + g'w + mult (w_j - v)),
+    nu [N+1, 12]: multipliers of the equalities in the same sign, row 0 of dx_0 = xhat - X_0, row k + 1 of stage k's dynamics,
     lu_vs_refined: max |plain LU - refined| on w, the conditioning estimate)."""
     fixed_idx = np.asarray(fixed_idx, dtype=int)
     K, rhs, n = _kkt(qp, fixed_idx, np.asarray(fixed_val, float))
@@ -251,7 +252,7 @@ def solve_equality(qp, fixed_idx=(), fixed_val=()):
     zf = z.astype(np.float64)
     w = zf[:n]
     dX, dU = qp.split(w)
-    return dict(w=w, dX=dX, dU=dU, mult=zf[n + 12 * (qp.N + 1):], lu_vs_refined=float(np.abs(z0[:n] - w).max()))
+    return dict(w=w, dX=dX, dU=dU, mult=zf[n + 12 * (qp.N + 1):], nu=zf[n:n + 12 * (qp.N + 1)].reshape(qp.N + 1, 12), lu_vs_refined=float(np.abs(z0[:n] - w).max()))
 
 
 ACTIVE_TOL = 1e-6
