@@ -333,6 +333,26 @@ int mpcb_step_term(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
                    const mpcb_step_sens_out *sens, const double *term /* DEVICE [batch][MPCB_NTERM] or NULL */, int term_changed,
                    double *du0_dxe /* DEVICE [batch][6][12] or NULL */, void *stream);
 
+/* ---- input disturbance in the prediction model (offset-free MPC) ---- */
+/* mpcb_step_warm whose prediction model carries a constant input disturbance (SQP_RTI controllers): dist[i] = d of simulation i, six
+ * doubles in rad/s (the units of u), a DEVICE array [batch][6] read during the launch only, like yref; constant over the horizon.
+ *   x_{k+1} = Ad x_k + Bd (u_k + d), k = 0 .. N-1;   qddot_k = (qdot_{k+1} - qdot_k) / dt of that model = cq_j (u_j + d_j - v_j).
+ * The input cost row stays u (not u + d) and the bounds on u stay lbu / ubu.  In the Gauss-Newton QP of the step at the iterate (X, U):
+ *   b_k = Ad X_k + Bd (U_k + d) - X_{k+1},   residual rows 11..16 gain (Sel Bd / dt) d,   g_k = dt Jr' W r with that residual,
+ * H_k is unchanged -- the Riccati factorisation, the fast-path test and the interior point are the ones of mpcb_step_warm.  The cost
+ * output and the stat / eq residual norms are those of this problem.  MPCB_WARM_SHIFT propagates the tail with this step's
+ * disturbance, x_N <- Ad x_N + Bd (u_{N-1} + d); the reset guess is unchanged (x_k = [q_0; qdot_0], u_k = 0).  d = 0 is the
+ * arithmetic of mpcb_step_warm.  Both engines run it, ragged horizons included on the throughput engine.
+ * dist_changed != 0 (d differs from the previous step's, or the disturbance was switched on or off) makes every simulation
+ * linearise again at the start of the step, exactly as ref_changed does.  An estimate that moves every step sets it every step.
+ * dist == NULL && dist_changed == 0 is mpcb_step_warm exactly (same kernels, same bits); dist == NULL with dist_changed != 0 is
+ * mpcb_step_warm from a fresh linearisation (the disturbance switched off).  MPCB_EINVAL: dist != NULL on a full-SQP controller.
+ * MPCB_ESTATE on a handle not set up as a controller.  The sensitivities (mpcb_step_sens), the weight sensitivity
+ * (mpcb_step_sens_w) and the terminal cost (mpcb_step_term) are not offered together with a disturbance; d u0 / d d is not
+ * offered, nor a per-stage disturbance profile, nor a rollout with an on-device observer. */
+int mpcb_step_dist(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const double *dist /* DEVICE [batch][6] or NULL */, int dist_changed, void *stream);
+
 /* ---- the controller step on either kernel family ---- */
 #define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
 #define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */

@@ -18,12 +18,13 @@ ARCH = "gfx950"
 # their own again), with the sensitivity of u0 to the cost weights on top of those (mpcb_step_sens_w; again modules of their own), and
 # the steps with a joint-wise terminal cost, without and with the sensitivity pass (mpcb_step_term; modules of their own as well),
 # and the rollout kernels of each engine that track a task reference schedule (mpcb_rollout_ref; modules of their own too), and those
-# of the rollout over a perturbed plant (mpcb_rollout_pert; likewise) and of the rollout with a terminal cost (mpcb_rollout_term)
+# of the rollout over a perturbed plant (mpcb_rollout_pert; likewise) and of the rollout with a terminal cost (mpcb_rollout_term),
+# and the steps with an input disturbance in the prediction model (mpcb_step_dist)
 SOURCES = ("mpc_kernel.hip", "mpc_step.hip", "mpc_stream_step.hip", "mpc_step_warm.hip", "mpc_stream_step_warm.hip",
            "mpc_step_sens.hip", "mpc_stream_step_sens.hip", "mpc_step_sensw.hip", "mpc_stream_step_sensw.hip",
            "mpc_step_term.hip", "mpc_stream_step_term.hip", "mpc_step_term_sens.hip", "mpc_stream_step_term_sens.hip",
            "mpc_rollout_ref.hip", "mpc_stream_rollout_ref.hip", "mpc_rollout_pert.hip", "mpc_stream_rollout_pert.hip",
-           "mpc_rollout_term.hip", "mpc_stream_rollout_term.hip")
+           "mpc_rollout_term.hip", "mpc_stream_rollout_term.hip", "mpc_step_dist.hip", "mpc_stream_step_dist.hip")
 
 
 def _stale(target: str) -> bool:

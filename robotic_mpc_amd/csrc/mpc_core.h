@@ -170,8 +170,21 @@ MPC_HD void load_constants(Ex &ex, const InstParams *P, const Robot *rb)
 // TERM = TERM_TABLE (the kernels of mpcb_rollout_term only, mpc_rollout_term.hip): the same engine for rollout<true, true>, whose
 // record is two arrays -- the simulation's constant blocks, and the row of its table of terminal references that the step reads.
 // An int, not a bool, so that the step's record accessor and with it the kernels of mpcb_step_term stay the code they are.
-template <class Ex, int TERM = 0>
-struct Engine {
+// DIST (the kernels of mpcb_step_dist only, mpc_step_dist.hip): the prediction model carries a constant input disturbance d [6] of the
+// simulation, x+ = Ad x + Bd (u + d): wherever the dynamics or qddot read u they read the effective input u + d (eff_u) -- the
+// dynamics defect, the qddot residual and its gradient rows, the shift's tail.  The input cost row and the bounds stay on u, the
+// stage Hessians are the ones they were, and passes that act on steps are linear in u and take no d.
+// DistPtr: with DIST this simulation's input disturbance d [6] in the step's device buffer (control_step sets it).  Wavefront-uniform:
+// the lanes that use an entry read it from there (eff_u), as the terminal record is read, never through LDS.  An empty base in every
+// other engine, so that their objects -- and the stack frames of their kernels -- are the ones they were.
+template <bool DIST>
+struct DistPtr {};
+template <>
+struct DistPtr<true> {
+    const double *dist = nullptr;
+};
+template <class Ex, int TERM = 0, bool DIST = false>
+struct Engine : DistPtr<DIST> {
     static constexpr int NT = Ex::NT;  // lanes per simulation
     Ex &ex;
     Ctx c;
@@ -452,12 +465,20 @@ struct Engine {
         else return TermRec{nullptr};
     }
 
+    // the input of joint j that the dynamics and qddot see: u_j + d_j with DIST (a uniform global load), u_j itself otherwise
+    MPC_HD double eff_u(int j, double u) const
+    {
+        if constexpr (DIST) return u + gld(ex.uni(this->dist) + j);
+        else return u;
+    }
+
     // The fast path's right-hand side of joint j at one stage (Gamma = 0): condensed gradient gt = g at (dw, pi, lam) = 0 with the
     // feedback step dx_0 = x_hat - x_0 embedded, and rb = b + A dx_0.  ONE function with explicit fused multiply-adds for its two
     // callers -- fast_rhs (a pass of its own: first attempt of a launch, SQP) and the residual-norm items of nlp_direct (SQP_RTI) -- so
     // that a run cut into several launches reproduces the single launch bit for bit whichever of them formed the right-hand side.
     struct RhsItem { double gtu, gtq, gtv, rbq, rbv; };
-    MPC_HD static RhsItem rhs_item(const InstParams &P, int j, bool st, bool inner, double uj, double vj, double dxq, double dxv,
+    // (ue: eff_u of uj, the input of the qddot rows; the input cost row takes uj)
+    MPC_HD static RhsItem rhs_item(const InstParams &P, int j, bool st, bool inner, double uj, double ue, double vj, double dxq, double dxv,
                                    double g0, double g1, double g2, double g3, double g4, double y0, double y1, double y2, double y3,
                                    double y4, double gv, double bdq, double bdv)
     {
@@ -465,7 +486,7 @@ struct Engine {
         const double vjn = vj + dxv;
         double s_ = g0 * y0;
         s_ = fma(g1, y1, s_); s_ = fma(g2, y2, s_); s_ = fma(g3, y3, s_); s_ = fma(g4, y4, s_);
-        const double tu = fma(c2, uj - vjn, 2.0 * P.w_u * uj), tv = fma(c2, vjn - uj, gv * y4);
+        const double tu = fma(c2, ue - vjn, 2.0 * P.w_u * uj), tv = fma(c2, vjn - ue, gv * y4);
         RhsItem o;
         o.gtu = st ? P.dt * tu : 0.0;
         o.gtq = st && inner ? P.dt * s_ : 0.0;
@@ -657,11 +678,11 @@ struct Engine {
                         double cu[6];
 #pragma unroll
                         for (int j = 0; j < 6; j++) {
-                            const double uj = uu[j], vj = xx[6 + j];
-                            const double qdd = P.cq[j] * (uj - vj);  // prediction_model.py:326
+                            const double uj = uu[j], vj = xx[6 + j], ue = eff_u(j, uj);
+                            const double qdd = P.cq[j] * (ue - vj);  // prediction_model.py:326
                             cu[j] = 2.0 * P.w_u * uj * uj + P.w_qddot * qdd * qdd;
-                            rec[O_BD + j] = (xx[j] + P.a12[j] * vj + P.b1[j] * uj) - xn[j];
-                            rec[O_BD + 6 + j] = (P.a22[j] * vj + P.b2[j] * uj) - xn[6 + j];
+                            rec[O_BD + j] = (xx[j] + P.a12[j] * vj + P.b1[j] * ue) - xn[j];
+                            rec[O_BD + 6 + j] = (P.a22[j] * vj + P.b2[j] * ue) - xn[6 + j];
                         }
                         task_lin<true, double *, REF>(rb, P, xx, xx + 6, rec, rec);
                         double s_ = 0.0;
@@ -744,7 +765,7 @@ struct Engine {
                             if (e < items) {
                                 const int s = e / 6, j = e - s * 6, k = k0 + s;
                                 double *rec = v2 + (size_t)s * LS;
-                                const double uj = v[r][0], qj = v[r][1], vj = v[r][2];
+                                const double uj = v[r][0], qj = v[r][1], vj = v[r][2], ue = eff_u(j, uj);
                                 const double c2 = P.w_qddot * P.cq[j] * P.cq[j];
                                 double as_ = a_s.at(lane), ai_ = a_i.at(lane), ac_ = a_c.at(lane);
                                 auto bound = [&](int ci, double cur, double l_lo, double l_hi, double t_lo, double t_hi, double &val) {
@@ -764,7 +785,7 @@ struct Engine {
                                 // u_j (stat_cls<0>, no step)
                                 double ru = 0.0;
                                 if (k < Nl) {
-                                    ru = P.dt * (2.0 * P.w_u * uj + c2 * (uj - vj));
+                                    ru = P.dt * (2.0 * P.w_u * uj + c2 * (ue - vj));
                                     ru += P.b1[j] * v[r][3] + P.b2[j] * v[r][4];
                                 }
                                 bound(j, uj, v[r][7], v[r][8], v[r][9], v[r][10], ru);
@@ -789,7 +810,7 @@ struct Engine {
                                 double rv = 0.0;
                                 if (k >= 1) {
                                     if (k < Nl) {
-                                        rv = P.dt * (rec[O_GV + j] * rec[O_Y + 4] + c2 * (vj - uj));
+                                        rv = P.dt * (rec[O_GV + j] * rec[O_Y + 4] + c2 * (vj - ue));
                                         rv += P.a12[j] * v[r][3] + P.a22[j] * v[r][4];
                                     }
                                     rv -= v[r][6];
@@ -804,7 +825,7 @@ struct Engine {
                                     // the fast path's right-hand side of the NEXT QP (fast_rhs): the new plant state is in sm.logv[24..35]
                                     // (the plant lane of the linearisation phase above)
                                     const double dxq = k == 0 ? sm.logv[24 + j] - qj : 0.0, dxv = k == 0 ? sm.logv[30 + j] - vj : 0.0;
-                                    RhsItem o = rhs_item(P, j, k < Nl, k >= 1, uj, vj, dxq, dxv, rec[O_GQ + j], rec[O_GQ + 6 + j],
+                                    RhsItem o = rhs_item(P, j, k < Nl, k >= 1, uj, ue, vj, dxq, dxv, rec[O_GQ + j], rec[O_GQ + 6 + j],
                                                          rec[O_GQ + 12 + j], rec[O_GQ + 18 + j], rec[O_GQ + 24 + j], rec[O_Y], rec[O_Y + 1],
                                                          rec[O_Y + 2], rec[O_Y + 3], rec[O_Y + 4], rec[O_GV + j], rec[O_BD + j],
                                                          rec[O_BD + 6 + j]);
@@ -1076,13 +1097,13 @@ struct Engine {
                         if (e < items) {
                             const int k = y0 + e / 6, j = e - (k - y0) * 6;
                             const double du = v[r][2], dvv = v[r][3];
-                            const double uj = v[r][0] + du, vj = v[r][1] + dvv;
+                            const double uj = v[r][0] + du, vj = v[r][1] + dvv, ue = eff_u(j, uj);
                             const double c2 = P.w_qddot * P.cq[j] * P.cq[j];
                             double *g3 = G3 + (size_t)k * W3, *g2 = G2 + (size_t)k * W2;
                             // u_j (stat_cls<0>)
                             double rgu = 0.0;
                             if (k < Nl) {
-                                rgu = dt * (2.0 * P.w_u * uj + c2 * (uj - vj));
+                                rgu = dt * (2.0 * P.w_u * uj + c2 * (ue - vj));
                                 rgu += P.b1[j] * v[r][4] + P.b2[j] * v[r][5];
                                 rgu += dt * lm * du;
                             }
@@ -1092,7 +1113,7 @@ struct Engine {
                             double rgv = 0.0;
                             if (k >= 1) {
                                 if (k < Nl) {
-                                    rgv = dt * (v[r][7] * Y[(k - y0) * 6 + 4] + c2 * (vj - uj));
+                                    rgv = dt * (v[r][7] * Y[(k - y0) * 6 + 4] + c2 * (vj - ue));
                                     rgv += P.a12[j] * v[r][4] + P.a22[j] * v[r][5];
                                 }
                                 rgv += (k < Nl ? dt : 1.0) * lm * dvv;
@@ -2923,7 +2944,7 @@ struct Engine {
                     if (e < items) {
                         const int k = e / 6, j = e - k * 6;
                         const double dxq = k == 0 ? sm.xhat[j] - v[r][2] : 0.0, dxv = k == 0 ? sm.xhat[6 + j] - v[r][1] : 0.0;
-                        RhsItem o = rhs_item(P, j, k < Nl, k >= 1, v[r][0], v[r][1], dxq, dxv, v[r][4], v[r][5], v[r][6], v[r][7], v[r][8],
+                        RhsItem o = rhs_item(P, j, k < Nl, k >= 1, v[r][0], eff_u(j, v[r][0]), v[r][1], dxq, dxv, v[r][4], v[r][5], v[r][6], v[r][7], v[r][8],
                                              v[r][9], v[r][10], v[r][11], v[r][12], v[r][13], v[r][3], v[r][14], v[r][15]);
                         if constexpr (TERM) {
                             // stage N (>= 1: no feedback step there): g_N = P (X_N - x_e)
@@ -3246,7 +3267,9 @@ struct Engine {
         ex.par([&](int lane) {
             if (lane < NX) {
                 const double *r1 = ex.smem().w.G1, *r2 = ex.smem().w.G2;  // stage 0 records in HBM (y holds W(r + G delta))
-                const double a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2));
+                double a;
+                if constexpr (DIST) a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2, gld(ex.uni(this->dist) + (lane >= 6 ? lane - 6 : 0))));
+                else a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2));
                 double *mw = &ex.smem().w.state[ST_X0_MW + lane];
                 *mw = nlp::merit_weight(sqp_iter, *mw, a);
             }
@@ -3565,11 +3588,11 @@ struct Engine {
         shift_group<W1>(sm.w.G1, Nl, [](int col) { return shift_class_g1(col); });
         // (SQP_RTI keeps nothing in G5)
         if (c.pb->solver_type == 0) shift_group<W5>(sm.w.G5, Nl, [](int col) { return shift_class_g5(col); });
-        // x_N <- Ad x_N + Bd u_{N-1}: the old x_N and the held input
+        // x_N <- Ad x_N + Bd u_{N-1}: the old x_N and the held input (DIST: the effective one, with this step's disturbance)
         double *const buf = ex.pool();
         ex.par([&](int lane) {
             if (lane < NX) buf[lane] = gld(sm.w.G1 + (size_t)Nl * W1 + O_X + lane);
-            if (lane >= 16 && lane < 16 + NU) buf[lane] = gld(sm.w.G1 + (size_t)(Nl - 1) * W1 + O_U + lane - 16);
+            if (lane >= 16 && lane < 16 + NU) buf[lane] = eff_u(lane - 16, gld(sm.w.G1 + (size_t)(Nl - 1) * W1 + O_U + lane - 16));
         });
         ex.par([&](int lane) {
             if (lane < NX) gst(sm.w.G1 + (size_t)Nl * W1 + O_X + lane, shift_tail(sm.P, lane, buf, buf + 16));
@@ -3773,13 +3796,17 @@ struct Engine {
     // SENSW (the kernels of mpcb_step_sens_w; with SENS): and its sensitivity to the cost weights through io.du0_dw.
     // TERM (the engine's flag; the kernels of mpcb_step_term): io.term holds this simulation's terminal cost, and with SENS the
     // sensitivity of u0 to its reference leaves through io.du0_dxe.  Not combined with SENSW.
+    // DIST (the engine's flag; the kernels of mpcb_step_dist): io.dist holds this simulation's input disturbance (SQP_RTI; the line
+    // search of full SQP does not know it).  Not combined with SENS, SENSW or TERM.
     template <bool WARM = false, bool SENS = false, bool SENSW = false>
     MPC_HD void control_step(const StepIO &io, int inst, bool reset)
     {
         static_assert(!(TERM && SENSW), "the weight sensitivity is not offered with a terminal cost");
+        static_assert(!(DIST && (TERM || SENS || SENSW)), "the input disturbance is not offered with sensitivities or a terminal cost");
         Smem &sm = ex.smem();
         Ws &w = c.w;
         if constexpr (TERM) term = io.term + (size_t)inst * NTERM;
+        if constexpr (DIST) this->dist = io.dist + (size_t)inst * NU;
         bool lin_valid = false;
         int mode = WARM_CARRY;
         if constexpr (WARM) {

@@ -149,7 +149,7 @@ __global__ void mpc_debug_task_lin_kernel(int n, Robot rb, const InstParams *__r
 
 // ------------------------------------------------------------------------------------ host
 // The variants of the controller step and the kinds of rollout; each is one kernel (family) per engine, see with_kernel below.
-enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS };
+enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS, STEP_DIST };
 enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM };
 
 struct mpcb_handle {
@@ -227,10 +227,12 @@ static int with_kernel(const mpcb_handle *h, StepVariant v, F &&f)
 {
     const int nw = h->waves_per_sim, wpe = h->wpe;
     if (h->engine == 1)
-        return f(v == STEP_TERM_SENS ? stream_step_term_sens_kernel() : v == STEP_TERM ? stream_step_term_kernel()
+        return f(v == STEP_DIST      ? stream_step_dist_kernel()
+                 : v == STEP_TERM_SENS ? stream_step_term_sens_kernel() : v == STEP_TERM ? stream_step_term_kernel()
                  : v == STEP_SENSW   ? stream_step_sensw_kernel()     : v == STEP_SENS ? stream_step_sens_kernel()
                  : v == STEP_WARM    ? stream_step_warm_kernel()      : stream_step_kernel());
-    return f(v == STEP_TERM_SENS ? step_term_sens_kernel(nw, wpe) : v == STEP_TERM ? step_term_kernel(nw, wpe)
+    return f(v == STEP_DIST      ? step_dist_kernel(nw, wpe)
+             : v == STEP_TERM_SENS ? step_term_sens_kernel(nw, wpe) : v == STEP_TERM ? step_term_kernel(nw, wpe)
              : v == STEP_SENSW   ? step_sensw_kernel(nw, wpe)     : v == STEP_SENS ? step_sens_kernel(nw, wpe)
              : v == STEP_WARM    ? step_warm_kernel(nw, wpe)      : step_kernel(nw, wpe));
 }
@@ -706,7 +708,8 @@ int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
 }
 
 static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
-                     const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream);
+                     const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream,
+                     const double *dist = nullptr, int dist_changed = 0);
 
 // (du0_dw == NULL: all of the above; otherwise the kernels that also form the weight sensitivity, supersets of the sens ones)
 int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
@@ -723,8 +726,17 @@ int mpcb_step_term(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
     return step_impl(h, io, yref, ref_changed, warm, reset, sens, nullptr, term, term_changed, du0_dxe, stream);
 }
 
+// (dist == NULL: mpcb_step_warm, after dist_changed from a fresh linearisation; otherwise the kernels built with the input disturbance
+// in the prediction model -- supersets of the warm-start ones)
+int mpcb_step_dist(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const double *dist, int dist_changed, void *stream)
+{
+    return step_impl(h, io, yref, ref_changed, warm, reset, nullptr, nullptr, nullptr, 0, nullptr, stream, dist, dist_changed);
+}
+
 static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
-                     const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream)
+                     const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream,
+                     const double *dist, int dist_changed)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
@@ -741,19 +753,22 @@ static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref,
     if (term && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
         return fail(h, MPCB_EINVAL, "mpcb_step_term: the terminal cost is offered with SQP_RTI; this controller runs full SQP");
     if (du0_dxe && (!sens || !term)) return fail(h, MPCB_EINVAL, "mpcb_step_term: du0_dxe needs sens (du0_dx and valid) and term");
-    const StepVariant variant = term ? (sens ? STEP_TERM_SENS : STEP_TERM) : du0_dw ? STEP_SENSW : sens ? STEP_SENS : warm ? STEP_WARM : STEP_BASE;
+    if (dist && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_step_dist: the input disturbance is offered with SQP_RTI; this controller runs full SQP");
+    const StepVariant variant = dist ? STEP_DIST : term ? (sens ? STEP_TERM_SENS : STEP_TERM) : du0_dw ? STEP_SENSW : sens ? STEP_SENS : warm ? STEP_WARM : STEP_BASE;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     StepArgs args;
     StepIO &sio = args.io;
     std::memcpy(&sio, io, sizeof(mpcb_step_io));
     sio.yref = yref;
-    // (new weights, or a new terminal cost, make the carried linearisation stale exactly as a new reference does)
-    sio.ref_changed = (ref_changed != 0 || term_changed != 0 || h->weights_changed) ? 1 : 0;
+    // (new weights, a new terminal cost or a new input disturbance make the carried linearisation stale exactly as a new reference does)
+    sio.ref_changed = (ref_changed != 0 || term_changed != 0 || dist_changed != 0 || h->weights_changed) ? 1 : 0;
     sio.warm = warm;
     sio.du0_dw = du0_dw;
     sio.term = term;
     sio.du0_dxe = du0_dxe;
+    sio.dist = dist;
     if (sens) { sio.du0_dx = sens->du0_dx; sio.du0_dyref = sens->du0_dyref; sio.sens_valid = sens->valid; }
     args.reset = (reset != 0 || h->reset_next) ? 1 : 0;
     if (int rc = timed_launch(h, variant, s, args)) return rc;

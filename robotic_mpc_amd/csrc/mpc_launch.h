@@ -34,19 +34,21 @@ using StreamRolloutTermFn = void (*)(Problem, const Robot *, const InstParams *,
      : (waves_per_sim) == 2 ? static_cast<Fn>(K<2>)                                                                         \
                             : static_cast<Fn>(K<1>))
 
-// mpc_step*.hip / mpc_stream_step*.hip: mpcb_step, _warm, _sens, _sens_w, _term without and with the sensitivity pass
+// mpc_step*.hip / mpc_stream_step*.hip: mpcb_step, _warm, _sens, _sens_w, _term without and with the sensitivity pass, _dist
 StepFn step_kernel(int waves_per_sim, int wpe);
 StepFn step_warm_kernel(int waves_per_sim, int wpe);
 StepFn step_sens_kernel(int waves_per_sim, int wpe);
 StepFn step_sensw_kernel(int waves_per_sim, int wpe);
 StepFn step_term_kernel(int waves_per_sim, int wpe);
 StepFn step_term_sens_kernel(int waves_per_sim, int wpe);
+StepFn step_dist_kernel(int waves_per_sim, int wpe);
 StreamStepFn stream_step_kernel();
 StreamStepFn stream_step_warm_kernel();
 StreamStepFn stream_step_sens_kernel();
 StreamStepFn stream_step_sensw_kernel();
 StreamStepFn stream_step_term_kernel();
 StreamStepFn stream_step_term_sens_kernel();
+StreamStepFn stream_step_dist_kernel();
 // mpc_rollout_*.hip / mpc_stream_rollout_*.hip: mpcb_rollout_ref, _pert, _term (the kernels of mpcb_rollout are mpc_kernel.hip's own)
 RolloutRefFn rollout_ref_kernel(int waves_per_sim, int wpe);
 RolloutPertFn rollout_pert_kernel(int waves_per_sim, int wpe);

@@ -157,7 +157,7 @@ struct Outputs {
 // solver.get(0,'u') and the step's statistics out, batch-major.  x_pred / u_pred may be null (not written).  The members past
 // u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged", one that stops
 // at ref_changed "every simulation carries its solver memory", one that stops at warm "no sensitivities", one that stops at sens_valid "none to the weights",
-// one that stops at du0_dw "no terminal cost".
+// one that stops at du0_dw "no terminal cost", one that stops at du0_dxe "no input disturbance".
 struct StepIO {
     const double *xhat;  // [batch][12]
     double *u0;          // [batch][6]
@@ -181,6 +181,8 @@ struct StepIO {
     // mpcb_step_term: the joint-wise terminal cost and the sensitivity of u0 to its reference, read by the term kernels only
     const double *term = nullptr;   // [batch][NTERM] pqq 6 | pqv 6 | pvv 6 | x_e 12 (mpc_nlp.h term_*)
     double *du0_dxe = nullptr;      // [batch][6][12] d u0 / d x_e, or null (not written)
+    // mpcb_step_dist: the input disturbance of the prediction model x+ = Ad x + Bd (u + d), read by the dist kernels only
+    const double *dist = nullptr;   // [batch][6] d, rad/s
 };
 
 // How a simulation's solver memory enters a controller step (MPCB_WARM_*); any other value is WARM_CARRY.

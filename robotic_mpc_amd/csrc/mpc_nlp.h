@@ -93,6 +93,19 @@ MPC_HD double x0_stationarity(const InstParams &P, int i, R1 r1, R2 r2)
            P.dt * P.lm * r1[O_QW + 12 + jj];
 }
 
+// The same with the input disturbance d of the model x+ = Ad x + Bd (u + d) (mpcb_step_dist): dj = d_{i-6} enters the qddot term of
+// the qdot rows (i >= 6; not read for i < 6).  Restated, not shared: the function above keeps its code.
+template <class R1, class R2>
+MPC_HD double x0_stationarity(const InstParams &P, int i, R1 r1, R2 r2, double dj)
+{
+    if (i < 6) return x0_stationarity(P, i, r1, r2);
+    const int jj = i - 6;
+    const double uj = (r1[O_U + jj] + r1[O_QW + jj]) + dj, vj = r1[O_X + 6 + jj] + r1[O_QW + 12 + jj];
+    const double c2 = P.w_qddot * P.cq[jj] * P.cq[jj];
+    return P.dt * (r2[O_GV + jj] * r2[O_Y + 4] + c2 * (vj - uj)) + P.a12[jj] * r1[O_QPI + jj] + P.a22[jj] * r1[O_QPI + 6 + jj] +
+           P.dt * P.lm * r1[O_QW + 12 + jj];
+}
+
 // L1 merit function (acados ocp_nlp_evaluate_merit_fun restated), stage k < N at a trial point: stage cost, weighted dynamics
 // defect against the next stage's trial state, weighted bound violations, added to `acc` term by term (a lane that sums several
 // stages keeps one running sum).  xx[12] | uu[6]: trial state and input; res(i): task residual i, any reference subtracted;

@@ -365,6 +365,25 @@ SE_DEV auto term_rec(TermArg<TERM> t)
     else return TermRec{nullptr};
 }
 
+// DIST (the kernel of mpcb_step_dist only, mpc_stream_step_dist.hip): the prediction model carries a constant input disturbance d [6]
+// of the simulation, x+ = Ad x + Bd (u + d).  A compile-time flag of control_step and of every pass it reaches that reads u for the
+// dynamics or for qddot -- the defect, the qddot cost and its gradient rows in rti_items, residual_pass and residual_items, the
+// shift's tail; they read the effective input eff_u = u + d there.  (lin_pass forms the task residual and its Jacobian only: no u.)
+// The pointer travels as an argument -- an empty struct, no register, in every other kernel -- and the lanes that use an entry read
+// it from the step's device buffer, as the terminal record is read.  The input cost row, the bounds and the Hessians stay as they are.
+template <bool DIST>
+struct DistArg {};
+template <>
+struct DistArg<true> {
+    const double *p;
+};
+template <bool DIST>
+SE_DEV double eff_u(DistArg<DIST> da, int j, double u)
+{
+    if constexpr (DIST) return u + ((const MPC_GLOBAL double *)uni_ref(TaskRef{da.p}).y)[j];
+    else return u;
+}
+
 // Stationarity element of class CLS (0: u_j, 1: q_j, 2: v_j) -- mpc_core.h Engine::stat_cls with the records in LDS.
 // r1: G1 row of stage k, r2: [R..GV] of stage k, pk / pm: pi_k / pi_{k-1}.
 template <int CLS>
@@ -416,8 +435,8 @@ struct IpmNorms {
 // multiplier step stored with stage k+1; pi_{k-1} travels in LDS from the previous iteration.
 //   in  : G1 row | G3 [DW..DT] | G2 [R..GV]            (234 doubles)
 //   out : G1 [QW..QT] | G2 [R,Y] | G2 [GAM|GT|RB] | G3 [RG|RD|RM]   (196 doubles)
-template <int MODE, int TERM = 0>
-SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {})
+template <int MODE, int TERM = 0, bool DIST = false>
+SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     static_assert(MODE == 0 || MODE == 1, "warm start or Newton step");
     SSmem &sm = g_ssm;
@@ -594,7 +613,7 @@ SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {})
                 if (cls == 0) {
                     if (k < N) {
                         const double uj = q_a + q_b, vj = q_c + q_d;
-                        rg = k_dt * (k_2wu * uj + k_c2 * (uj - vj));
+                        rg = k_dt * (k_2wu * uj + k_c2 * (eff_u(da, cj, uj) - vj));
                         rg += k_p1 * q_e + k_p2 * q_f;
                         rg += k_dt * k_lm * q_b;
                     }
@@ -612,7 +631,7 @@ SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {})
                 } else {
                     if (k > 0) {
                         if (k < N) {
-                            const double uj = q_a + q_b, vj = q_c + q_d;
+                            const double uj = eff_u(da, cj, q_a + q_b), vj = q_c + q_d;
                             rg = k_dt * (gv * y4 + k_c2 * (vj - uj));
                             rg += k_p1 * q_e + k_p2 * q_f;
                         }
@@ -685,8 +704,8 @@ SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {})
 // three phases U | Y | S,D and the same arithmetic per element).  ~17 batches of loads per pass instead of 101 stages of chain;
 // while a batch is in flight the SIMD's other simulation runs.  y of every stage waits in the (idle) ring between Y and S.
 // (residual_items_ok: beside RING_DOUBLES above)
-template <int TERM = 0>
-SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {})
+template <int TERM = 0, bool DIST = false>
+SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
@@ -870,13 +889,13 @@ SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {})
                 if (e < items) {
                     const int k = e / 6, j = e - k * 6;
                     const double du = v[r][2], dvv = v[r][3];
-                    const double uj = v[r][0] + du, vj = v[r][1] + dvv;
+                    const double uj = v[r][0] + du, vj = v[r][1] + dvv, ue = eff_u(da, j, uj);
                     const double c2 = P.w_qddot * P.cq[j] * P.cq[j];
                     MPC_GLOBAL double *g3 = rec(k, j) + C3, *g2 = rec(k, j) + C2;
                     // u_j
                     double rgu = 0.0;
                     if (k < N) {
-                        rgu = dt * (2.0 * P.w_u * uj + c2 * (uj - vj));
+                        rgu = dt * (2.0 * P.w_u * uj + c2 * (ue - vj));
                         rgu += P.b1[j] * v[r][4] + P.b2[j] * v[r][5];
                         rgu += dt * lm * du;
                     }
@@ -886,7 +905,7 @@ SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {})
                     double rgv = 0.0;
                     if (k >= 1) {
                         if (k < N) {
-                            rgv = dt * (v[r][7] * Y[k * 6 + 4] + c2 * (vj - uj));
+                            rgv = dt * (v[r][7] * Y[k * 6 + 4] + c2 * (vj - ue));
                             rgv += P.a12[j] * v[r][4] + P.a22[j] * v[r][5];
                         }
                         rgv += (k < N ? dt : 1.0) * lm * dvv;
@@ -962,8 +981,9 @@ SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {})
 // (an accepted fast-path candidate that has become the iterate by a flip of the index, fast_commit / ipm_solve).
 // TERM: stage N's joint items take the terminal cost -- its term of the cost, P (X_N - x_e) in the stationarity rows and in the
 // right-hand side's gt (mpc_nlp.h term_*).
-template <bool NORMS, bool RHS, bool SQPM = false, int TERM = 0>
-SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = {})
+// DIST: the defect, the qddot cost, the qddot terms of the stationarity rows and of the right-hand side read the effective input.
+template <bool NORMS, bool RHS, bool SQPM = false, int TERM = 0, bool DIST = false>
+SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     SSmem &sm = g_ssm;
     const InstParams &P = sm.P;
@@ -1015,7 +1035,7 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = 
             const int e = base + r * WAVE + lane;
             if (e < items) {
                 const int k = e / 6, j = e - k * 6;
-                const double uj = x[r][0], qj = x[r][1], vj = x[r][2];
+                const double uj = x[r][0], qj = x[r][1], vj = x[r][2], ue = eff_u(da, j, uj);
                 const double c2 = P.w_qddot * P.cq[j] * P.cq[j];
                 const bool st = k < N;
                 double s_ = 0.0;
@@ -1035,10 +1055,10 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = 
                     // dynamics defect (prediction_model.py:317-320) and this joint's share of the cost
                     bdq = 0.0; bdv = 0.0;
                     if (st) {
-                        bdq = (qj + P.a12[j] * vj + P.b1[j] * uj) - m[r][12];
-                        bdv = (P.a22[j] * vj + P.b2[j] * uj) - m[r][13];
+                        bdq = (qj + P.a12[j] * vj + P.b1[j] * ue) - m[r][12];
+                        bdv = (P.a22[j] * vj + P.b2[j] * ue) - m[r][13];
                         n_e = fmax(n_e, fmax(fabs(bdq), fabs(bdv)));
-                        const double qdd = P.cq[j] * (uj - vj);
+                        const double qdd = P.cq[j] * (ue - vj);
                         csum += 0.5 * dt * (2.0 * P.w_u * uj * uj + P.w_qddot * qdd * qdd);
                         if (j < NTASK) csum += 0.5 * dt * P.w_task[j] * g[r][11] * g[r][11];
                     }
@@ -1060,7 +1080,7 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = 
                     };
                     double ru = 0.0;
                     if (st) {
-                        ru = dt * (2.0 * P.w_u * uj + c2 * (uj - vj));
+                        ru = dt * (2.0 * P.w_u * uj + c2 * (ue - vj));
                         ru += P.b1[j] * m[r][0] + P.b2[j] * m[r][1];
                     }
                     bound(j, st, uj, m[r][4], m[r][5], m[r][6], m[r][7], ru);
@@ -1074,7 +1094,7 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = 
                     double rv = 0.0;
                     if (k > 0) {
                         if (st) {
-                            rv = dt * (g[r][0] * g[r][10] + c2 * (vj - uj));
+                            rv = dt * (g[r][0] * g[r][10] + c2 * (vj - ue));
                             rv += P.a12[j] * m[r][0] + P.a22[j] * m[r][1];
                         }
                         rv -= m[r][3];
@@ -1091,9 +1111,9 @@ SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = 
                 if (RHS) {
                     const double dxq = k == 0 ? xh_q - qj : 0.0, dxv = k == 0 ? xh_v - vj : 0.0;
                     const double vjn = vj + dxv;
-                    const double gtu = st ? dt * (2.0 * P.w_u * uj + c2 * (uj - vjn)) : 0.0;
+                    const double gtu = st ? dt * (2.0 * P.w_u * uj + c2 * (ue - vjn)) : 0.0;
                     double gtq = st && k >= 1 ? dt * s_ : 0.0;
-                    double gtv = st && k >= 1 ? dt * (g[r][0] * g[r][10] + c2 * (vjn - uj)) : 0.0;
+                    double gtv = st && k >= 1 ? dt * (g[r][0] * g[r][10] + c2 * (vjn - ue)) : 0.0;
                     if constexpr (TERM) {
                         if (k == N) { gtq = tgq; gtv = tgv; }       // stage N (>= 1: no feedback step there): g_N = P (X_N - x_e)
                     }
@@ -1768,9 +1788,9 @@ SE_PASS void fast_commit(bool embed_x0)
 // `fast_accepted` (out, optional): whether this QP is the accepted fast-path candidate (mpc_step's hook asks).
 // FULLFACT (the kernel of mpcb_step_sens): the fast path's factor records go out whole, tail [w | R~^-1] included -- sens_pass reads
 // R~_0^-1; the same factorisation, 48 more scalars stored per stage.
-template <class FT, bool FULLFACT = false, int TERM = 0>
+template <class FT, bool FULLFACT = false, int TERM = 0, bool DIST = false>
 SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_prev = nullptr, int *cur = nullptr, bool *fast_accepted = nullptr,
-                     TermArg<TERM> tm = {})
+                     TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     SSmem &sm = g_ssm;
     const double tol = sm.P.qp_tol;
@@ -1781,7 +1801,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         else {
             tried = 1;
             SPROF_T0(t_r);
-            if (nlp_prev) rti_items<true, true, false, TERM>(1, nlp_prev, slot, tm); else rti_items<false, true, false, TERM>(0, nullptr, 0, tm);
+            if (nlp_prev) rti_items<true, true, false, TERM, DIST>(1, nlp_prev, slot, tm, da); else rti_items<false, true, false, TERM, DIST>(0, nullptr, 0, tm, da);
             SPROF_ADD(10, t_r);
             nlp_prev = nullptr;                                    // the previous step's residuals are done, whatever happens next
             SPROF_T0(t_f);
@@ -1808,9 +1828,9 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         }
     }
     // nlp_prev: the NLP residual / cost of the previous step's iterate is still to be evaluated -- by this QP's first pass
-    if (nlp_prev) rti_items<true, false, false, TERM>(1, nlp_prev, slot, tm);     // (the same items as everywhere else: see rti_items)
+    if (nlp_prev) rti_items<true, false, false, TERM, DIST>(1, nlp_prev, slot, tm, da);     // (the same items as everywhere else: see rti_items)
     if (cur && slot == 1) { fast_commit(false); *cur = 0; }      // the interior-point passes expect the iterate in G1 (this also overwrites a rejected candidate there)
-    IpmNorms r = residual_pass<0, TERM>(0.0, tm);
+    IpmNorms r = residual_pass<0, TERM, DIST>(0.0, tm, da);
     const double nc = unid(r.nc);
     double mu = nc > 0 ? unid(r.smu) / nc : 0.0;
     int it = 0, status = 1;
@@ -1843,7 +1863,7 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
         }
         const double a = ipm::step_scale(alpha);
         SPROF_T0(tr);
-        r = residual_items_ok(uni(sm.n_hor)) ? residual_items<TERM>(a, tm) : residual_pass<1, TERM>(a, tm);
+        r = residual_items_ok(uni(sm.n_hor)) ? residual_items<TERM, DIST>(a, tm, da) : residual_pass<1, TERM, DIST>(a, tm, da);
         SPROF_ADD(4, tr);
         mu = nc > 0 ? unid(r.smu) / nc : 0.0;
     }
@@ -2183,9 +2203,10 @@ struct StepStats {
 // while G2 still holds the linearisation the QP was built from; `exact`: the QP was solved by an accepted fast-path attempt.
 struct NoHook {};
 // TERM (SQP_RTI): `tm` is the terminal cost of the QP, the cost and the stationarity rows (TermArg).
-template <class FT, class Lin, class Search, class AfterQp = NoHook, int TERM = 0>
+// DIST (SQP_RTI): `da` is the input disturbance of the model (DistArg); the full-SQP branch does not know it.
+template <class FT, class Lin, class Search, class AfterQp = NoHook, int TERM = 0, bool DIST = false>
 SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer, AfterQp &&after_qp = AfterQp{},
-                          TermArg<TERM> tm = {})
+                          TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     constexpr bool HOOK = !std::is_same<typename std::decay<AfterQp>::type, NoHook>::value;
     SSmem &sm = g_ssm;
@@ -2198,11 +2219,11 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
         if (!c.lin_valid) {
             lin(0.0, false, false, -1); __builtin_amdgcn_s_waitcnt(0); fence();
             double o5[5];
-            rti_items<true, false, false, TERM>(0, o5, c.cur, tm);
+            rti_items<true, false, false, TERM, DIST>(0, o5, c.cur, tm, da);
             c.lin_cost = unid(o5[0]);
         }
         bool fast_accepted = false;
-        const int qs = ipm_solve<FT, HOOK, TERM>(pb.qp_iter_max, &s.qp_iter, c.fast, nlp_prev, &c.cur, HOOK ? &fast_accepted : nullptr, tm);
+        const int qs = ipm_solve<FT, HOOK, TERM, DIST>(pb.qp_iter_max, &s.qp_iter, c.fast, nlp_prev, &c.cur, HOOK ? &fast_accepted : nullptr, tm, da);
         SPROF_ADD(5, tq);
         const bool ok = qs == 0 || qs == 1;
         if (!ok) s.status = 4;                                         // ACADOS_QP_FAILURE, iterate untouched
@@ -2218,7 +2239,7 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
             if (lane < NX) sm.vec[3][lane] = sm.xhat[lane];            // the x_hat this QP was solved for
         } else {
             double o5[5];
-            rti_items<true, false, false, TERM>(0, o5, c.cur, tm);
+            rti_items<true, false, false, TERM, DIST>(0, o5, c.cur, tm, da);
             s.cost = unid(o5[0]); s.res4[0] = o5[1]; s.res4[1] = o5[2]; s.res4[2] = o5[3]; s.res4[3] = o5[4];
         }
         SPROF_ADD(9, tn);
@@ -2417,8 +2438,9 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
 // its stores, a later block loads only rows above everything stored so far, and the row it stores into was loaded by the block
 // before -- no wait between blocks.  The passes that follow fetch these records through the ring: stores drained first.
 constexpr int SH_R = 12;
-template <bool SQP>
-SE_PASS void shift_pass(int N)
+// DIST: the tail is propagated with the effective input, x_N <- Ad x_N + Bd (u_{N-1} + d), this step's disturbance.
+template <bool SQP, bool DIST = false>
+SE_PASS void shift_pass(int N, DistArg<DIST> da = {})
 {
     SSmem &sm = g_ssm;
     const SWs w = sm.w;
@@ -2454,7 +2476,16 @@ SE_PASS void shift_pass(int N)
     double xn = 0.0;
     if (lane < NX) {
         const MPC_GLOBAL double *x = g + (size_t)N * ldd + O_X, *u = g + (size_t)(N - 1) * ldd + O_U;
-        xn = shift_tail(sm.P, lane, x, u);
+        if constexpr (DIST) {
+            const int j = lane < 6 ? lane : lane - 6;
+            struct OneU {                                      // (shift_tail reads the lane's joint alone)
+                double v;
+                SE_DEV double operator[](int) const { return v; }
+            };
+            xn = shift_tail(sm.P, lane, x, OneU{eff_u(da, j, u[j])});
+        } else {
+            xn = shift_tail(sm.P, lane, x, u);
+        }
     }
     if (lane < NX) g[(size_t)N * ldd + O_X + lane] = xn;
     __builtin_amdgcn_s_waitcnt(0);                                // the shifted records are in memory before the first pass reads them
@@ -2642,11 +2673,13 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
 // SENSW (the kernel of mpcb_step_sens_w; with SENS): and its sensitivity to the cost weights through io.du0_dw.
 // TERM (the kernels of mpcb_step_term, SQP_RTI): io.term holds this simulation's terminal cost -- on a ragged batch it acts at the
 // simulation's own horizon end -- and with SENS the sensitivity of u0 to its reference leaves through io.du0_dxe.  Not with SENSW.
-template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false, bool TERM = false>
+// DIST (the kernel of mpcb_step_dist, SQP_RTI): io.dist holds this simulation's input disturbance (DistArg).  Not with SENS, SENSW, TERM.
+template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false, bool TERM = false, bool DIST = false>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
     static_assert(!(TERM && SENSW), "the weight sensitivity is not offered with a terminal cost");
+    static_assert(!(DIST && (TERM || SENS || SENSW)), "the input disturbance is not offered with sensitivities or a terminal cost");
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
     const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), NMAX = pb.N;
@@ -2661,8 +2694,12 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
     if constexpr (WARM) {
         // the linearisation carried with a shifted iterate was formed at the unshifted one: linearise again, like after a new reference
         if (mode == WARM_SHIFT) {
-            if (pb.solver_type == 0) shift_pass<true>(N);
-            else shift_pass<false>(N);
+            if constexpr (DIST) {
+                shift_pass<false, true>(N, DistArg<true>{io.dist + (size_t)inst * NU});     // (SQP_RTI only: mpcb_step_dist refuses full SQP)
+            } else {
+                if (pb.solver_type == 0) shift_pass<true>(N);
+                else shift_pass<false>(N);
+            }
             c.lin_valid = false;
         }
     }
@@ -2695,6 +2732,8 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
         }, TermArg<true>{tp});
     } else if constexpr (TERM) {
         s = mpc_step<FT>(pb, c, lin, search, nullptr, false, NoHook{}, TermArg<true>{io.term + (size_t)inst * NTERM});
+    } else if constexpr (DIST) {
+        s = mpc_step<FT>(pb, c, lin, search, nullptr, false, NoHook{}, TermArg<0>{}, DistArg<true>{io.dist + (size_t)inst * NU});
     } else if constexpr (SENS) {
         s = mpc_step<FT>(pb, c, lin, search, nullptr, false, [&](bool exact) {
             sens_pass(io.du0_dx + (size_t)inst * NU * NX, io.du0_dyref ? io.du0_dyref + (size_t)inst * NMAX * NTASK * NU : nullptr,

@@ -93,6 +93,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
             "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
+            "mpcb_step_dist",
             "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term")
 
 
@@ -151,6 +152,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                      C.c_void_p]
     lib.mpcb_step_term.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.POINTER(MpcbStepSensOut), _dp, C.c_int,
                                    _dp, C.c_void_p]
+    lib.mpcb_step_dist.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -521,6 +523,22 @@ class MpcBatchEngine:
             return
         self._check(self.lib.mpcb_step_sens(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
                                             C.c_void_p(stream)), "mpcb_step_sens")
+
+    def step_dist(self, io, yref=None, ref_changed: bool = False, warm=None, reset: bool = False, dist=None,
+                  dist_changed: bool = False, stream: Optional[int] = None):
+        """mpcb_step_dist: step_warm() whose prediction model carries the input disturbance `dist`, a contiguous float64 device
+        tensor [batch, 6] in rad/s (x+ = Ad x + Bd (u + d)), or None: step_warm().  `dist_changed`: the disturbance differs from the
+        previous step's, or was switched on or off (the step linearises again first)."""
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._step_struct(io)
+        yp = C.cast(C.c_void_p(yref.data_ptr()), _dp) if yref is not None else None
+        wp = C.cast(C.c_void_p(warm.data_ptr()), _ip) if warm is not None else None
+        dp = C.cast(C.c_void_p(dist.data_ptr()), _dp) if dist is not None else None
+        self._check(self.lib.mpcb_step_dist(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), dp,
+                                            int(bool(dist_changed)), C.c_void_p(stream)), "mpcb_step_dist")
 
     def debug_task_lin(self, cfgs: Sequence[Dict], chain, x: np.ndarray) -> np.ndarray:
         """Diagnostic: the device linearisation at points x[i] = [q; qdot] with the parameters of cfgs[i];

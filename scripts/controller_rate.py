@@ -22,10 +22,14 @@ reports the fraction of steps that had them; `--sens-w` asks for the sensitivity
 rest): the kernels of mpcb_step_term; with --sens every step also returns du0_dxe.  Not with --sens-w.  `--terminal zero` puts all-zero
 blocks in force instead: the same kernels on exactly the plain step's trajectory and solver work (a zero terminal cost is none), which
 isolates what the kernels themselves cost; the LQR cost changes the closed loop and with it the QP iterations per step (qp_iter_mean).
+`--dist` gives every step an input disturbance for the prediction model (BatchController.step(dist=...): the kernels of mpcb_step_dist,
+which linearise again at the start of every step as after a new reference): `--dist zero` all zeros, exactly the plain step's
+trajectory, to be held against `--ref packed`, the packed reference rows given again every step (mpcb_step_ref with ref_changed = 1 on
+the same trajectory); `--dist random` alternates two draws of +-0.1 rad/s.  Not with --sens, --sens-w or --terminal.
 
     python scripts/controller_rate.py [--batch 256 ...] [--engine latency|stream ...] [--N 100] [--steps 600] [--solver SQP_RTI]
                                       [--skip-rollout] [--ref none|once|every ...] [--warm carry|shift ...] [--sens] [--sens-w]
-                                      [--terminal [lqr|zero]]
+                                      [--terminal [lqr|zero]] [--dist [zero|random]]
 """
 import argparse
 import json
@@ -73,7 +77,7 @@ def main():
     ap.add_argument("--solver", choices=("SQP_RTI", "SQP"), default="SQP_RTI")
     ap.add_argument("--skip-rollout", action="store_true")
     # task reference: none (the packed one), set once before the loop, or a new one every step (one more linearisation per step)
-    ap.add_argument("--ref", nargs="+", choices=("none", "once", "every"), default=["none"])
+    ap.add_argument("--ref", nargs="+", choices=("none", "once", "every", "packed"), default=["none"])
     # warm start of every step: the previous iterate as it is, or moved one stage (the shift pass + one more linearisation per step)
     ap.add_argument("--warm", nargs="+", choices=("carry", "shift"), default=None)
     # every step also returns du0_dx / du0_dyref / sens_valid (the sensitivity pass)
@@ -82,8 +86,12 @@ def main():
     ap.add_argument("--sens-w", action="store_true")
     # a joint-wise LQR terminal cost in force (the kernels of mpcb_step_term)
     ap.add_argument("--terminal", nargs="?", const="lqr", default=None, choices=("lqr", "zero"))
+    # an input disturbance of the prediction model given every step (the kernels of mpcb_step_dist)
+    ap.add_argument("--dist", nargs="?", const="random", default=None, choices=("zero", "random"))
     args = ap.parse_args()
     args.sens = args.sens or args.sens_w
+    if args.dist and (args.sens or args.terminal):
+        ap.error("--dist is not offered together with --sens, --sens-w or --terminal")
     if args.terminal and args.sens_w:
         ap.error("--sens-w is not offered together with --terminal")
     for B in args.batch:
@@ -150,6 +158,13 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
         blocks = terminal.lqr_terminal(raw[0])["blocks"] if args.terminal == "lqr" else np.zeros((6, 3))
         ctl.set_terminal_cost(np.stack([blocks] * B), x_e)
 
+    dsched = None
+    if args.dist:
+        rng = np.random.default_rng(1)
+        dsched = [torch.tensor(rng.uniform(-0.1, 0.1, (B, 6)) if args.dist == "random" else np.zeros((B, 6)), dtype=torch.float64, device=dev)
+                  for _ in range(2)]
+    packed = base.clone()
+
     nvalid, nqp = [], []
 
     def closed_loop(events=None):
@@ -162,7 +177,9 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
             kw = dict(sens_w=True) if args.sens_w else dict(sens=True) if args.sens else {}
             if warm == "shift":
                 kw.update(shift=True)
-            o = ctl.step(x, yref=sched[k % 2] if ref == "every" else None, **kw)
+            if dsched is not None:
+                kw.update(dist=dsched[k % 2])
+            o = ctl.step(x, yref=sched[k % 2] if ref == "every" else packed if ref == "packed" else None, **kw)
             u = o["u0"]
             if events is not None:
                 events[-1][1].record()
@@ -184,7 +201,7 @@ def measure(args, B, eng, ref="none", warm="carry", sliding=False):
     closed_loop(ev)
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
-    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, sens=bool(args.sens), sens_w=bool(args.sens_w), terminal=args.terminal or False, step_loop_ms=round(loop_ms, 3),
+    out = dict(workload=f"batch {B}, N {args.N}, {args.solver}, {S} steps", engine=eng, reference=ref, warm=warm, sens=bool(args.sens), sens_w=bool(args.sens_w), terminal=args.terminal or False, dist=args.dist or False, step_loop_ms=round(loop_ms, 3),
                step_loop_steps_per_s=round(B * S / (loop_ms * 1e-3)), step_launch_ms_mean=round(float(np.mean(step_ms)), 4),
                step_launch_ms_median=round(float(np.median(step_ms)), 4), step_launch_ms_total=round(float(np.sum(step_ms)), 3),
                launch_info=ctl.launch_info(), kernel_info=ctl.engine.kernel_info(), final_state_finite=bool(torch.isfinite(xf).all()))
