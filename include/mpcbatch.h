@@ -349,7 +349,7 @@ int mpcb_step_term(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
  * mpcb_step_warm from a fresh linearisation (the disturbance switched off).  MPCB_EINVAL: dist != NULL on a full-SQP controller.
  * MPCB_ESTATE on a handle not set up as a controller.  The sensitivities (mpcb_step_sens), the weight sensitivity
  * (mpcb_step_sens_w) and the terminal cost (mpcb_step_term) are not offered together with a disturbance; d u0 / d d is not
- * offered, nor a per-stage disturbance profile, nor a rollout with an on-device observer. */
+ * offered, nor a per-stage disturbance profile.  (A rollout whose steps take the estimate of an on-device observer: mpcb_rollout_obs.) */
 int mpcb_step_dist(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                    const double *dist /* DEVICE [batch][6] or NULL */, int dist_changed, void *stream);
 
@@ -464,7 +464,34 @@ int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o
                       const double *term_blocks /* DEVICE [batch][18] or NULL */,
                       const double *term_xref /* DEVICE [batch][Nsim][12] */, void *stream);
 
-/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term launch of this handle went through the throughput
+/* ---- rollouts with an on-device disturbance observer: offset-free MPC over the perturbed plant ---- */
+/* mpcb_rollout_pert whose step t predicts with the input disturbance of mpcb_step_dist, estimated inside the kernel from the measured
+ * velocities.  Per joint j of simulation i, with a22, b2 of the MODEL (parameters [8..13], dt) and obs_gain[i] = l1[6] | l2[6]:
+ *   v^_0 = y_0,  d^_0 = 0
+ *   for t = 0 .. Nsim - 1:
+ *       xhat_t  = z_t + x_noise[i][t],   y_t = its velocities (what the observer measures is what the controller sees)
+ *       u_t     = u0 of mpcb_step_dist(xhat_t, window t of yref_sched, ref_changed = 1, dist = d^_t, dist_changed = 1);  d_hat[i][t] = d^_t
+ *       z_{t+1} = plant step of mpcb_rollout_pert from z_t with u_t + u_dist[i][t]
+ *       v^_{t+1} = a22 v^_t + b2 (u_t + d^_t) + l1 (y_t - v^_t),   d^_{t+1} = d^_t + l2 (y_t - v^_t)      (u_t: the COMMANDED input)
+ * -- the two-state Luenberger predictor of robotic_mpc_amd/observer.py (DisturbanceObserver.update), whose gains for both error poles
+ * at p are l1 = a22 + 1 - 2 p, l2 = (1 - p)^2 / b2.  Logs, errors, cost and residuals follow mpcb_rollout_pert; cost and residuals
+ * are those of the problem with d^_t.  There is no shift.  obs_gain is a DEVICE array read during the launch; d_hat is a DEVICE array
+ * the launch WRITES (rows [step0, step1)) and never reads: the step's estimate stays on chip, and what carries from one launch (and
+ * one work-queue item) to the next are the twelve doubles (v^, d^) in the simulation's workspace, next to the true state -- no
+ * workspace, pool or mpcb_workspace_bytes change.  l2 = 0 keeps d^ at zero: the perturbed rollout through these kernels.
+ *
+ * obs_gain == NULL is mpcb_rollout_pert exactly (the same kernels, the same bits; d_hat is then ignored).  MPCB_EINVAL: obs_gain
+ * without d_hat or without yref_sched (a run without a schedule passes the packed row on every row), on a full-SQP problem, or with
+ * MPCB_PRECISION_FP32_RICCATI.  MPCB_ESTATE on a controller handle or before mpcb_setup; the step-range rules of mpcb_rollout.
+ * Whichever engine mpcb_setup chose runs it, work queue and ragged horizons included; mpcb_queue_used and mpcb_last_kernel_ms apply,
+ * and after such a launch mpcb_kernel_info reports this rollout's kernel.  Not offered together with the terminal cost
+ * (mpcb_rollout_term) or the sensitivities. */
+int mpcb_rollout_obs(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
+                     const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
+                     const double *obs_gain /* DEVICE [batch][12] = l1[6] | l2[6], or NULL */,
+                     double *d_hat /* DEVICE [batch][Nsim][6], written: row t = the estimate step t used */, void *stream);
+
+/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term / mpcb_rollout_obs launch of this handle went through the throughput
  * engine's work queue, 0: it did not (< 0: error).  Host state only. */
 int mpcb_queue_used(mpcb_handle *h);
 

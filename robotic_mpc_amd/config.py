@@ -47,7 +47,11 @@ EXTENSION_DEFAULTS = {"translation_ee_t": (0.0, 0.0, 0.1), "urdf_path": None, "e
                       # the joint-wise terminal cost that closes every step's horizon in a rollout (terminal.py): None -- no
                       # terminal cost -- or a JSON-serialisable spec {"weight": {"kind": "lqr" | "blocks", ...}, "reference":
                       # {"kind": "constant" | "table", ...}}; SQP_RTI and fp64 only
-                      "terminal_cost": None}
+                      "terminal_cost": None,
+                      # the input-disturbance observer that runs inside the rollout (observer.py): None -- the controller predicts
+                      # without an estimate -- or {"pole": p}, 0 <= p < 1, where both poles of the estimation error sit; SQP_RTI
+                      # and fp64 only, not together with terminal_cost
+                      "disturbance_observer": None}
 # codes of the parameter record (include/mpcbatch.h [7]); RK4 = 0 keeps default records unchanged
 PLANT_INTEGRATORS = {"RK4": 0, "Euler": 1, "RK2": 2, "RK3": 3}
 
@@ -292,8 +296,20 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
         term = copy.deepcopy(dict(term))
         # (the number of rows of a table against this run's Nsim; the LQR design against this model)
         terminal.sample({"terminal_cost": term, "Nsim": Nsim, "dt": dt, "wcv": wcv})
+    obs = cfg["disturbance_observer"]
+    if obs is not None:
+        from . import observer
+
+        if term is not None:
+            raise ValueError("a disturbance_observer is not offered together with a terminal_cost")
+        if so["nlp_solver_type"] != "SQP_RTI":
+            raise ValueError("a disturbance_observer is offered with nlp_solver_type='SQP_RTI' only")
+        if cfg["riccati_precision"] == "fp32":
+            raise ValueError("a disturbance_observer is offered with riccati_precision='fp64' only")
+        observer.validate(obs)
+        obs = {"pole": float(obs["pole"])}
     return {
-        "reference_schedule": schedule, "plant_perturbation": perturbation, "terminal_cost": term,
+        "reference_schedule": schedule, "plant_perturbation": perturbation, "terminal_cost": term, "disturbance_observer": obs,
         "robot_name": cfg["robot_name"], "urdf_path": cfg["urdf_path"], "ee_frame": cfg["ee_frame"],
         "N": N, "Nsim": Nsim, "dt": dt,
         "solver_type": SOLVER_RTI if so["nlp_solver_type"] == "SQP_RTI" else SOLVER_SQP,

@@ -36,8 +36,8 @@ controllers): one 2x2 block per joint, the shape of the discrete LQR cost-to-go 
 ``set_input_disturbance(d)`` / ``step(x, dist=d)`` tell the prediction model about a constant input disturbance (SQP_RTI
 controllers): it becomes ``x+ = Ad x + Bd (u + d)``, and with an estimate of ``d`` (``robotic_mpc_amd.observer.DisturbanceObserver``)
 the controller tracks without the offset a disturbed plant otherwise leaves -- offset-free MPC.  Not offered together with ``sens``,
-``sens_w`` or a terminal cost; rollouts with an on-device observer, ``d u0 / d d``, a per-stage disturbance profile and full SQP are
-not offered either.
+``sens_w`` or a terminal cost; ``d u0 / d d``, a per-stage disturbance profile and full SQP are not offered either.  Rollouts run
+the same observer on the device (configuration key ``disturbance_observer``, mpcb_rollout_obs).
 """
 from __future__ import annotations
 

@@ -177,13 +177,17 @@ MPC_HD void load_constants(Ex &ex, const InstParams *P, const Robot *rb)
 // DistPtr: with DIST this simulation's input disturbance d [6] in the step's device buffer (control_step sets it).  Wavefront-uniform:
 // the lanes that use an entry read it from there (eff_u), as the terminal record is read, never through LDS.  An empty base in every
 // other engine, so that their objects -- and the stack frames of their kernels -- are the ones they were.
-template <bool DIST>
+// DIST = DIST_SHARED (the kernels of mpcb_rollout_obs only, mpc_rollout_obs.hip): the disturbance is the estimate the rollout's own
+// observer formed one step earlier.  It lives in the workgroup's shared block (six slots of Smem::logv that no log row uses,
+// lv_dhat in mpc_layout.h) and eff_u reads it from there: never from a global location this kernel wrote, which a uniform load could
+// serve from a stale scalar-cache line.  No pointer member: the base is empty.  An int, not a bool, for the reason TERM is one.
+template <int DIST>
 struct DistPtr {};
 template <>
-struct DistPtr<true> {
+struct DistPtr<1> {
     const double *dist = nullptr;
 };
-template <class Ex, int TERM = 0, bool DIST = false>
+template <class Ex, int TERM = 0, int DIST = 0>
 struct Engine : DistPtr<DIST> {
     static constexpr int NT = Ex::NT;  // lanes per simulation
     Ex &ex;
@@ -465,10 +469,16 @@ struct Engine : DistPtr<DIST> {
         else return TermRec{nullptr};
     }
 
-    // the input of joint j that the dynamics and qddot see: u_j + d_j with DIST (a uniform global load), u_j itself otherwise
+    // the input of joint j that the dynamics and qddot see: u_j + d_j with DIST (a uniform global load; DIST_SHARED: an LDS read), u_j itself otherwise
+    MPC_HD double dist_of(int j) const
+    {
+        if constexpr (DIST == DIST_SHARED) return ex.smem().logv[lv_dhat(j)];
+        else return gld(ex.uni(this->dist) + j);
+    }
     MPC_HD double eff_u(int j, double u) const
     {
-        if constexpr (DIST) return u + gld(ex.uni(this->dist) + j);
+        if constexpr (DIST == DIST_SHARED) return u + dist_of(j);
+        else if constexpr (DIST) return u + gld(ex.uni(this->dist) + j);
         else return u;
     }
 
@@ -3268,7 +3278,8 @@ struct Engine : DistPtr<DIST> {
             if (lane < NX) {
                 const double *r1 = ex.smem().w.G1, *r2 = ex.smem().w.G2;  // stage 0 records in HBM (y holds W(r + G delta))
                 double a;
-                if constexpr (DIST) a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2, gld(ex.uni(this->dist) + (lane >= 6 ? lane - 6 : 0))));
+                if constexpr (DIST == DIST_SHARED) a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2, dist_of(lane >= 6 ? lane - 6 : 0)));
+                else if constexpr (DIST) a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2, gld(ex.uni(this->dist) + (lane >= 6 ? lane - 6 : 0))));
                 else a = fabs(nlp::x0_stationarity(sm.P, lane, r1, r2));
                 double *mw = &ex.smem().w.state[ST_X0_MW + lane];
                 *mw = nlp::merit_weight(sqp_iter, *mw, a);
@@ -3397,14 +3408,24 @@ struct Engine : DistPtr<DIST> {
     // TERM_TABLE (the engine's flag, with REF and PERT; the kernels of mpcb_rollout_term, mpc_rollout_term.hip): step t's QP is closed by the
     // joint-wise terminal cost of `tt` -- this simulation's constant blocks, and row t of its reference table as x_e.  The step
     // linearises again at its start (REF), so the new row needs nothing else, and nothing of it carries to the next step or launch.
+    // OBS (the engine built with DIST_SHARED, with REF and PERT; the kernels of mpcb_rollout_obs, mpc_rollout_obs.hip): step t's model
+    // carries the input disturbance d^_t that the rollout's own observer -- DisturbanceObserver of observer.py, re-associated in time --
+    // formed at the end of step t - 1 from the innovation y_{t-1} - v^_{t-1} (y: the measured velocities, sm.xhat[6..11], noise
+    // included) and the commanded u_{t-1}, with the MODEL's a22, b2 and the gains l1, l2 of `ob`.  The six plant lanes keep (v^, d^)
+    // of the next step in registers; d^_t is put into the shared block (sm.logv[lv_dhat], what eff_u reads) and into row t of the log
+    // ob.d_hat -- write-only here -- before the solve.  Step 0 takes v^_0 = y_0, d^_0 = 0.  Across a launch boundary the twelve
+    // doubles travel in w.state[ST_OBS], stored and loaded where ST_Z is.
     struct NoSched {};
-    template <bool REF = false, bool PERT = false>
+    template <bool REF = false, bool PERT = false, bool OBS = false>
     MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {},
                         typename std::conditional<PERT, PlantPert, NoSched>::type pert = {},
-                        typename std::conditional<TERM == TERM_TABLE, TermTab, NoSched>::type tt = {})
+                        typename std::conditional<TERM == TERM_TABLE, TermTab, NoSched>::type tt = {},
+                        typename std::conditional<OBS, ObsArg, NoSched>::type ob = {})
     {
         static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
         static_assert(!TERM || (TERM == TERM_TABLE && REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
+        static_assert(OBS == (DIST == DIST_SHARED) && (!OBS || (REF && PERT)), "the rollout with an observer runs the perturbed rollout's step on the engine whose disturbance is in the shared block");
+        static_assert(!DIST || OBS, "a rollout takes its input disturbance from its own observer");
         if constexpr (TERM == TERM_TABLE) term.p = tt.blocks;
         Smem &sm = ex.smem();
         const InstParams &P = sm.P;
@@ -3446,6 +3467,15 @@ struct Engine : DistPtr<DIST> {
         if constexpr (PERT) ex.wpar([&](int lane) {
             wc_plant.at(lane) = lane < 6 ? (pert.wcv ? pert.wcv[lane] : P.wcv[lane]) : 0.0;
         });
+        // (OBS) the plant lanes' observer: gains, and the estimate (v^, d^) of the step about to run
+        typename std::conditional<OBS, typename Ex::template PerLane<double>, NoSched>::type ob_l1, ob_l2, ob_v, ob_d;
+        if constexpr (OBS) ex.wpar([&](int lane) {
+            const bool on = lane < 6;
+            ob_l1.at(lane) = on ? ob.gain[lane] : 0.0;
+            ob_l2.at(lane) = on ? ob.gain[6 + lane] : 0.0;
+            ob_v.at(lane) = on && step0 != 0 ? w.state[ST_OBS + lane] : 0.0;
+            ob_d.at(lane) = on && step0 != 0 ? w.state[ST_OBS + 6 + lane] : 0.0;
+        });
         for (int i = step0; i < step1; i++) {
             int sqp_iter = 0, qp_iter = 0;
             double res4[4] = {0, 0, 0, 0}, cost = 0.0;
@@ -3456,6 +3486,14 @@ struct Engine : DistPtr<DIST> {
                 lin_valid = false;
             }
             if constexpr (TERM == TERM_TABLE) term.x = tt.x_ref + (size_t)i * NX;
+            if constexpr (OBS) ex.par([&](int lane) {
+                // the estimate this step's model takes: into the shared block for eff_u, and row i of the log
+                if (lane < 6) {
+                    if (i == 0) { ob_v.at(lane) = sm.xhat[6 + lane]; ob_d.at(lane) = 0.0; }
+                    sm.logv[lv_dhat(lane)] = ob_d.at(lane);
+                    gst(ob.d_hat + (size_t)i * NU + lane, ob_d.at(lane));
+                }
+            });
             const int status = nlp_step<!PERT>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
             const double t1 = ex.clock();
             PROF_T0(tp);
@@ -3472,6 +3510,10 @@ struct Engine : DistPtr<DIST> {
                         sm.logv[24 + j] = qn;
                         sm.logv[30 + j] = vn;
                         sm.u0[j] = u;
+                        if constexpr (OBS) {
+                            // the estimate of step i + 1, while sm.xhat still holds this step's measurement (mpc_nlp.h observer_next)
+                            nlp::observer_next(P.a22[j], P.b2[j], ob_l1.at(lane), ob_l2.at(lane), sm.xhat[6 + j], u, ob_v.at(lane), ob_d.at(lane));
+                        }
                     }
                 } else
                 if (lane < 6 && !plant_done) {
@@ -3507,6 +3549,9 @@ struct Engine : DistPtr<DIST> {
         }
         if (log_lo <= step1) log_flush(out, inst, log_lo, step1);   // the columns of a partly filled block
         store_carry(lin_valid);
+        if constexpr (OBS) ex.par([&](int lane) {
+            if (lane < 6) { w.state[ST_OBS + lane] = ob_v.at(lane); w.state[ST_OBS + 6 + lane] = ob_d.at(lane); }
+        });
     }
 
     // acados initial guess: x_k = x0, u_k = 0, all multipliers / QP memory 0 (SURVEY A.7 iv); sm.xhat = x0, sm.u0 = qdot_0

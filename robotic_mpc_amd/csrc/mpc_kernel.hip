@@ -150,7 +150,7 @@ __global__ void mpc_debug_task_lin_kernel(int n, Robot rb, const InstParams *__r
 // ------------------------------------------------------------------------------------ host
 // The variants of the controller step and the kinds of rollout; each is one kernel (family) per engine, see with_kernel below.
 enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS, STEP_DIST };
-enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM };
+enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM, ROLLOUT_OBS };
 
 struct mpcb_handle {
     int device = -1;
@@ -241,9 +241,11 @@ static int with_kernel(const mpcb_handle *h, RolloutKind kind, F &&f)
 {
     const int nw = h->waves_per_sim, wpe = h->wpe;
     if (h->engine == 1)
-        return kind == ROLLOUT_TERM ? f(stream_rollout_term_kernel()) : kind == ROLLOUT_PERT ? f(stream_rollout_pert_kernel())
+        return kind == ROLLOUT_OBS  ? f(stream_rollout_obs_kernel())
+             : kind == ROLLOUT_TERM ? f(stream_rollout_term_kernel()) : kind == ROLLOUT_PERT ? f(stream_rollout_pert_kernel())
              : kind == ROLLOUT_REF  ? f(stream_rollout_ref_kernel())  : f(stream_rollout_kernel(h->pb.precision));
-    return kind == ROLLOUT_TERM ? f(rollout_term_kernel(nw, wpe)) : kind == ROLLOUT_PERT ? f(rollout_pert_kernel(nw, wpe))
+    return kind == ROLLOUT_OBS  ? f(rollout_obs_kernel(nw, wpe))
+         : kind == ROLLOUT_TERM ? f(rollout_term_kernel(nw, wpe)) : kind == ROLLOUT_PERT ? f(rollout_pert_kernel(nw, wpe))
          : kind == ROLLOUT_REF  ? f(rollout_ref_kernel(nw, wpe))  : f(rollout_kernel(nw, wpe));
 }
 
@@ -252,7 +254,7 @@ struct StepArgs { StepIO io; int reset; };
 struct RolloutArgs {
     unsigned grid; Outputs out; int step0, step1;
     int *queue; int chunk_steps; long long timeout_ticks;   // throughput engine
-    const double *yref_sched; PlantPert pert; TermTab term;  // ref / pert / term
+    const double *yref_sched; PlantPert pert; TermTab term; ObsArg obs;  // ref / pert / term / obs
 };
 
 // Every kernel starts (pb, robot record, params, ws_base, ws_stride).  Latency engine: the record by value, a workgroup of
@@ -292,6 +294,10 @@ static void launch(RolloutTermFn k, const mpcb_handle *h, hipStream_t s, const R
 {
     latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.term);
 }
+static void launch(RolloutObsFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.obs);
+}
 static void launch(StreamRolloutFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
 {
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks);
@@ -307,6 +313,11 @@ static void launch(StreamRolloutPertFn k, const mpcb_handle *h, hipStream_t s, c
 static void launch(StreamRolloutTermFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
 {
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.term);
+}
+
+static void launch(StreamRolloutObsFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.obs);
 }
 
 // One launch of `variant`'s kernel on stream s, between the two events mpcb_last_kernel_ms reads.  Latency engine: the dynamic-LDS
@@ -328,6 +339,9 @@ static int timed_launch(mpcb_handle *h, V variant, hipStream_t s, const Args &ar
         return MPCB_OK;
     });
 }
+
+static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                       const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream);
 
 extern "C" {
 
@@ -600,6 +614,23 @@ int mpcb_rollout_pert(mpcb_handle *h, int step0, int step1, const mpcb_result *o
 int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
                       const double *term_blocks, const double *term_xref, void *stream)
 {
+    return rollout_any(h, step0, step1, o, yref_sched, pert_, term_blocks, term_xref, nullptr, nullptr, stream);
+}
+
+// (obs_gain == NULL: the kernels of mpcb_rollout_pert, chosen by pert and yref_sched; otherwise those of the rollout with an observer,
+// mpc_rollout_obs.hip / mpc_stream_rollout_obs.hip, through the same launch path -- a null pert is the nominal plant inside them)
+int mpcb_rollout_obs(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                     const double *obs_gain, double *d_hat, void *stream)
+{
+    return rollout_any(h, step0, step1, o, yref_sched, pert_, nullptr, nullptr, obs_gain, d_hat, stream);
+}
+
+}  // extern "C"
+
+// The one launch path of every rollout: at most one of term_blocks and obs_gain is given.
+static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                       const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream)
+{
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
     if (h->controller) return fail(h, MPCB_ESTATE, "mpcb_rollout on a controller handle (mpcb_setup_controller): use mpcb_step");
@@ -617,6 +648,14 @@ int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o
         return fail(h, MPCB_EINVAL, "mpcb_rollout_term: a rollout with a terminal cost needs a reference schedule (the packed rows when there is none)");
     if (term_blocks && !term_xref)
         return fail(h, MPCB_EINVAL, "mpcb_rollout_term: term_blocks needs term_xref, the table of terminal references");
+    if (obs_gain && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_obs: a disturbance observer is offered in fp64 only (no fp32 Riccati leg)");
+    if (obs_gain && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_obs: a disturbance observer is offered with SQP_RTI only");
+    if (obs_gain && !yref_sched)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_obs: a rollout with an observer needs a reference schedule (the packed rows when there is none)");
+    if (obs_gain && !d_hat)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_obs: obs_gain needs d_hat, the log of the estimates");
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -626,11 +665,12 @@ int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o
         return fail(h, MPCB_EINVAL, "every result array must be provided");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const RolloutKind kind = term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
+    const RolloutKind kind = obs_gain ? ROLLOUT_OBS : term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
     RolloutArgs args{};
     args.yref_sched = yref_sched;
     if (pert_) args.pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
     args.term = TermTab{term_blocks, term_xref};
+    args.obs = ObsArg{obs_gain, d_hat};
     std::memcpy(&args.out, o, sizeof args.out);
     args.step0 = step0;
     args.step1 = step1;
@@ -670,6 +710,8 @@ int mpcb_rollout_term(mpcb_handle *h, int step0, int step1, const mpcb_result *o
     h->next_step = step1;
     return MPCB_OK;
 }
+
+extern "C" {
 
 int mpcb_set_weights(mpcb_handle *h, const double *weights, void *stream)
 {

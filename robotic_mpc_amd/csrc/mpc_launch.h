@@ -15,6 +15,8 @@ using RolloutRefFn = void (*)(Problem, Robot, const InstParams *, double *, size
 using RolloutPertFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert);
 using RolloutTermFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
                                TermTab);
+using RolloutObsFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
+                              ObsArg);
 // throughput engine (mpc_stream.h): the robot record in device memory, no pool; rollouts take (queue, chunk_steps, timeout_ticks)
 using StreamStepFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, StepIO, int);
 using StreamRolloutFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long);
@@ -24,6 +26,8 @@ using StreamRolloutPertFn = void (*)(Problem, const Robot *, const InstParams *,
                                      const double *, PlantPert);
 using StreamRolloutTermFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
                                      const double *, PlantPert, TermTab);
+using StreamRolloutObsFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
+                                    const double *, PlantPert, ObsArg);
 
 // The kernel of the latency engine's template K<NWV, WPE = 1> for a launch geometry (mpcb_setup picks it; <2> and <1> are reached
 // through MPCB_WAVES_PER_SIM), as a pointer of type Fn.  The module holds its kernels in the order they are instantiated in, which is
@@ -49,12 +53,14 @@ StreamStepFn stream_step_sensw_kernel();
 StreamStepFn stream_step_term_kernel();
 StreamStepFn stream_step_term_sens_kernel();
 StreamStepFn stream_step_dist_kernel();
-// mpc_rollout_*.hip / mpc_stream_rollout_*.hip: mpcb_rollout_ref, _pert, _term (the kernels of mpcb_rollout are mpc_kernel.hip's own)
+// mpc_rollout_*.hip / mpc_stream_rollout_*.hip: mpcb_rollout_ref, _pert, _term, _obs (the kernels of mpcb_rollout are mpc_kernel.hip's own)
 RolloutRefFn rollout_ref_kernel(int waves_per_sim, int wpe);
 RolloutPertFn rollout_pert_kernel(int waves_per_sim, int wpe);
 RolloutTermFn rollout_term_kernel(int waves_per_sim, int wpe);
+RolloutObsFn rollout_obs_kernel(int waves_per_sim, int wpe);
 StreamRolloutRefFn stream_rollout_ref_kernel();
 StreamRolloutPertFn stream_rollout_pert_kernel();
 StreamRolloutTermFn stream_rollout_term_kernel();
+StreamRolloutObsFn stream_rollout_obs_kernel();
 
 }  // namespace mpcb

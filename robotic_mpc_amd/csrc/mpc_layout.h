@@ -85,6 +85,7 @@ constexpr int ST_FAST = 26;        // [2] fast path: QPs left before the next at
 constexpr int ST_CUR = 28;         // throughput engine, SQP_RTI: the slot of the stage records that holds the QP iterate (0: G1, 1: G3)
 constexpr int ST_PROF = 32;        // [NPROF] profile counters (diagnostic build)
 constexpr int NPROF = 16;
+constexpr int ST_OBS = 48;         // [12] the rollout's disturbance observer (mpcb_rollout_obs): v^ [6] | d^ [6] of the next step
 constexpr int STATE_DOUBLES = 64;
 
 // Kinematic constants (robots.py KinematicChain.packed): 105 doubles
@@ -249,6 +250,25 @@ MPC_HD TermTab term_tab_of(const TermTab &a, int inst, int Nsim)
     return TermTab{a.blocks + (size_t)inst * 18, a.x_ref + (size_t)inst * Nsim * 12};
 }
 
+// Value of the engines' DIST flag in the kernels of mpcb_rollout_obs: the model's input disturbance is the estimate of the rollout's own
+// observer, kept in the engine's shared block (1, or true: the caller's device buffer of mpcb_step_dist).
+constexpr int DIST_SHARED = 2;
+// ... where entry j of that estimate lives in Smem::logv (and in the throughput engine's logv, same layout): the slots no log row
+// uses, [21..23] and [43..45].  No kernel's shared block grows.
+MPC_HD int lv_dhat(int j) { return j < 3 ? 21 + j : 40 + j; }
+// The disturbance observer of ONE simulation in a rollout (mpcb_rollout_obs; the simulation's offsets applied): its gains, read once,
+// and the log of its estimates, row t = the d^ that step t's model took -- written by the kernel, never read by it.
+struct ObsArg {
+    const double *gain;     // [12] l1 [6] | l2 [6]
+    double *d_hat;          // [Nsim][6]
+};
+// ... of simulation `inst` of a launch (`a`: the two [batch][...] arrays)
+MPC_HD ObsArg obs_arg_of(const ObsArg &a, int inst, int Nsim)
+{
+    return ObsArg{a.gain + (size_t)inst * 12, a.d_hat + (size_t)inst * Nsim * 6};
+}
+static_assert(ST_OBS >= ST_PROF + NPROF && ST_OBS + 12 <= STATE_DOUBLES, "the observer's slots lie past the profile counters, inside the state block");
+
 // One instance's workspace: five stage-major group arrays + persistent scalars.
 struct Ws {
     double *G1, *G2, *G3, *G4, *G5, *PH, *state;
@@ -324,7 +344,7 @@ struct Smem {
     alignas(16) double red[8][NWV_MAX];   // one partial per wavefront (Ex::put_* / get_*)
     alignas(16) double xhat[12];    // current plant state (feedback, simulator.py:206)
     alignas(16) double u0[6];
-    alignas(16) double logv[48];    // [0..20] pose, rpy, J qdot | [24..35] next plant state | [36..42] task errors
+    alignas(16) double logv[48];    // [0..20] pose, rpy, J qdot | [24..35] next plant state | [36..42] task errors | lv_dhat: d^ (mpcb_rollout_obs)
     // log columns wait here until LOGB of them leave as contiguous runs (one 64-byte run per row and flush
     // instead of one 8-byte store per row and step)
     alignas(16) double logbuf[LOG_ROWS][LOGB];

@@ -66,6 +66,17 @@ MPC_HD void plant_rk(const InstParams &P, double wc, double q, double v, double 
     }
 }
 
+// One joint of the rollout's disturbance observer (mpcb_rollout_obs; robotic_mpc_amd/observer.py DisturbanceObserver.update, one step
+// earlier in time): from the estimate (v, d) that step t used, its measured velocity y and its commanded input u, the estimate of
+// step t + 1 -- v+ = a22 v + b2 (u + d) + l1 (y - v), d+ = d + l2 (y - v).  Two chains of fused multiply-adds, written out so that
+// both engines and the host emulation round alike.
+MPC_HD void observer_next(double a22, double b2, double l1, double l2, double y, double u, double &v, double &d)
+{
+    const double e = y - v;
+    v = fma(a22, v, fma(b2, u + d, l1 * e));
+    d = fma(l2, e, d);
+}
+
 // ---- SQP line search: MERIT_BACKTRACKING (trajectory_optimizer.py:68; acados alpha_reduction, alpha_min) -------------------------
 // trial steps 1, 0.7, 0.49, ... while >= 0.05
 constexpr double LS_REDUCTION = 0.7, LS_ALPHA_MIN = 0.05;

@@ -371,16 +371,21 @@ SE_DEV auto term_rec(TermArg<TERM> t)
 // shift's tail; they read the effective input eff_u = u + d there.  (lin_pass forms the task residual and its Jacobian only: no u.)
 // The pointer travels as an argument -- an empty struct, no register, in every other kernel -- and the lanes that use an entry read
 // it from the step's device buffer, as the terminal record is read.  The input cost row, the bounds and the Hessians stay as they are.
-template <bool DIST>
+// DIST = DIST_SHARED (the kernel of mpcb_rollout_obs only, mpc_stream_rollout_obs.hip): the disturbance is the estimate the rollout's own
+// observer formed one step earlier; it lives in g_ssm (six slots of logv that no log row uses, lv_dhat in mpc_layout.h) and eff_u reads
+// it there -- never from a global location this kernel wrote, which a uniform load could serve from a stale scalar-cache line.  No
+// pointer: the argument is empty.  An int, not a bool, for the reason TERM is one.
+template <int DIST>
 struct DistArg {};
 template <>
-struct DistArg<true> {
+struct DistArg<1> {
     const double *p;
 };
-template <bool DIST>
+template <int DIST>
 SE_DEV double eff_u(DistArg<DIST> da, int j, double u)
 {
-    if constexpr (DIST) return u + ((const MPC_GLOBAL double *)uni_ref(TaskRef{da.p}).y)[j];
+    if constexpr (DIST == DIST_SHARED) return u + g_ssm.logv[lv_dhat(j)];
+    else if constexpr (DIST) return u + ((const MPC_GLOBAL double *)uni_ref(TaskRef{da.p}).y)[j];
     else return u;
 }
 
@@ -435,7 +440,7 @@ struct IpmNorms {
 // multiplier step stored with stage k+1; pi_{k-1} travels in LDS from the previous iteration.
 //   in  : G1 row | G3 [DW..DT] | G2 [R..GV]            (234 doubles)
 //   out : G1 [QW..QT] | G2 [R,Y] | G2 [GAM|GT|RB] | G3 [RG|RD|RM]   (196 doubles)
-template <int MODE, int TERM = 0, bool DIST = false>
+template <int MODE, int TERM = 0, int DIST = 0>
 SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     static_assert(MODE == 0 || MODE == 1, "warm start or Newton step");
@@ -704,7 +709,7 @@ SE_PASS IpmNorms residual_pass(double a, TermArg<TERM> tm = {}, DistArg<DIST> da
 // three phases U | Y | S,D and the same arithmetic per element).  ~17 batches of loads per pass instead of 101 stages of chain;
 // while a batch is in flight the SIMD's other simulation runs.  y of every stage waits in the (idle) ring between Y and S.
 // (residual_items_ok: beside RING_DOUBLES above)
-template <int TERM = 0, bool DIST = false>
+template <int TERM = 0, int DIST = 0>
 SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     SSmem &sm = g_ssm;
@@ -982,7 +987,7 @@ SE_PASS IpmNorms residual_items(double a, TermArg<TERM> tm = {}, DistArg<DIST> d
 // TERM: stage N's joint items take the terminal cost -- its term of the cost, P (X_N - x_e) in the stationarity rows and in the
 // right-hand side's gt (mpc_nlp.h term_*).
 // DIST: the defect, the qddot cost, the qddot terms of the stationarity rows and of the right-hand side read the effective input.
-template <bool NORMS, bool RHS, bool SQPM = false, int TERM = 0, bool DIST = false>
+template <bool NORMS, bool RHS, bool SQPM = false, int TERM = 0, int DIST = 0>
 SE_PASS void rti_items(int xsel, double *out5, int slot = 0, TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
     SSmem &sm = g_ssm;
@@ -1788,7 +1793,7 @@ SE_PASS void fast_commit(bool embed_x0)
 // `fast_accepted` (out, optional): whether this QP is the accepted fast-path candidate (mpc_step's hook asks).
 // FULLFACT (the kernel of mpcb_step_sens): the fast path's factor records go out whole, tail [w | R~^-1] included -- sens_pass reads
 // R~_0^-1; the same factorisation, 48 more scalars stored per stage.
-template <class FT, bool FULLFACT = false, int TERM = 0, bool DIST = false>
+template <class FT, bool FULLFACT = false, int TERM = 0, int DIST = 0>
 SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_prev = nullptr, int *cur = nullptr, bool *fast_accepted = nullptr,
                      TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
@@ -2204,7 +2209,7 @@ struct StepStats {
 struct NoHook {};
 // TERM (SQP_RTI): `tm` is the terminal cost of the QP, the cost and the stationarity rows (TermArg).
 // DIST (SQP_RTI): `da` is the input disturbance of the model (DistArg); the full-SQP branch does not know it.
-template <class FT, class Lin, class Search, class AfterQp = NoHook, int TERM = 0, bool DIST = false>
+template <class FT, class Lin, class Search, class AfterQp = NoHook, int TERM = 0, int DIST = 0>
 SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&search, double *nlp_prev, bool defer, AfterQp &&after_qp = AfterQp{},
                           TermArg<TERM> tm = {}, DistArg<DIST> da = {})
 {
@@ -2309,14 +2314,23 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 // cost of `tt_` -- this simulation's constant blocks, and row t of its reference table as x_e -- at the simulation's own last stage.
 // The step linearises again at its start (REF), so the new row needs nothing else, and nothing of it carries to the next step, launch
 // or work item.
-template <class FT, bool REF = false, bool PERT = false, bool TERM = false>
+// OBS (with REF and PERT, not with TERM; the kernel of mpcb_rollout_obs, mpc_stream_rollout_obs.hip): step t's model carries the input
+// disturbance d^_t that the rollout's own observer (observer.py DisturbanceObserver, re-associated in time: mpc_nlp.h observer_next)
+// formed at the end of step t - 1 from the innovation y_{t-1} - v^_{t-1} (y: the measured velocities, sm.xhat[6..11], noise included)
+// and the commanded u_{t-1}, with the MODEL's a22, b2 and the gains of `ob_`.  The six plant lanes keep (v^, d^) of the next step in
+// registers; d^_t goes into sm.logv[lv_dhat] (what eff_u reads, DIST_SHARED) and into row t of the log ob_.d_hat -- write-only here -- before
+// the solve.  Step 0 takes v^_0 = y_0, d^_0 = 0; across a launch boundary and a work-queue hand-off the twelve doubles travel in
+// w.state[ST_OBS], stored and loaded where ST_Z is.
+template <class FT, bool REF = false, bool PERT = false, bool TERM = false, bool OBS = false>
 SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                     const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched_ = {},
                     typename std::conditional<PERT, PlantPert, NoSched>::type pert_ = {},
-                    typename std::conditional<TERM, TermTab, NoSched>::type tt_ = {})
+                    typename std::conditional<TERM, TermTab, NoSched>::type tt_ = {},
+                    typename std::conditional<OBS, ObsArg, NoSched>::type ob_ = {})
 {
     static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
     static_assert(!TERM || (REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
+    static_assert(!OBS || (REF && PERT && !TERM), "the rollout with an observer runs the perturbed rollout's step, without a terminal cost");
     const double *sched = nullptr;
     if constexpr (REF) sched = uni_ref(TaskRef{sched_}).y;
     const double *p_wcv = nullptr, *p_ud = nullptr, *p_xn = nullptr;
@@ -2355,6 +2369,16 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if (lane < 6) wc_plant = p_wcv ? p_wcv[lane] : P.wcv[lane];
         fence();
     }
+    double ob_l1 = 0.0, ob_l2 = 0.0, ob_v = 0.0, ob_d = 0.0;   // (OBS) the plant lanes' observer: gains, (v^, d^) of the step about to run
+    double *p_dh = nullptr;
+    if constexpr (OBS) {
+        const double *p_gain = uni_ref(TaskRef{ob_.gain}).y;
+        p_dh = const_cast<double *>(uni_ref(TaskRef{ob_.d_hat}).y);
+        if (lane < 6) {
+            ob_l1 = p_gain[lane]; ob_l2 = p_gain[6 + lane];
+            if (step0 != 0) { ob_v = w.state[ST_OBS + lane]; ob_d = w.state[ST_OBS + 6 + lane]; }
+        }
+    }
     const auto lin = [](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass(alpha, do_update, sqp_mult, slot); };
     const auto search = [](int sqp_iter) { return line_search(sqp_iter); };
     for (int i = step0; i < step1; i++) {
@@ -2367,10 +2391,24 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if constexpr (REF) {
             const TaskRef ref{sched + (size_t)i * NTASK};
             c.lin_valid = false;
+            if constexpr (OBS) {
+                // the estimate this step's model takes: into LDS for eff_u, and row i of the log
+                fence();
+                if (lane < 6) {
+                    if (i == 0) { ob_v = sm.xhat[6 + lane]; ob_d = 0.0; }
+                    sm.logv[lv_dhat(lane)] = ob_d;
+                    *(MPC_GLOBAL double *)(p_dh + (size_t)i * NU + lane) = ob_d;
+                }
+                fence();
+            }
             if constexpr (TERM)
                 s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
                                  [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false, NoHook{},
                                  TermArg<TERM_TABLE>{tt_.blocks, tt_.x_ref + (size_t)i * NX});
+            else if constexpr (OBS)
+                s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
+                                 [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false, NoHook{},
+                                 TermArg<0>{}, DistArg<DIST_SHARED>{});
             else
             s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
                              [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false);
@@ -2396,6 +2434,8 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
                 sm.logv[24 + j] = qn;
                 sm.logv[30 + j] = vn;
                 sm.u0[j] = u;
+                // (OBS) the estimate of step i + 1, while sm.xhat still holds this step's measurement
+                if constexpr (OBS) nlp::observer_next(P.a22[j], P.b2[j], ob_l1, ob_l2, sm.xhat[6 + j], u, ob_v, ob_d);
             }
         } else
         if (lane < 6) {
@@ -2428,6 +2468,9 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
     }
     if (log_lo <= step1) log_flush(out, inst, T1, log_lo, step1);
     c.store(w.state);
+    if constexpr (OBS) {
+        if (lane < 6) { w.state[ST_OBS + lane] = ob_v; w.state[ST_OBS + 6 + lane] = ob_d; }
+    }
 }
 
 // WARM_SHIFT (mpc_layout.h, shift_class_*): this simulation's carried records of stages 1..N move to stages 0..N-1 of its own horizon,
@@ -2439,7 +2482,7 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
 // before -- no wait between blocks.  The passes that follow fetch these records through the ring: stores drained first.
 constexpr int SH_R = 12;
 // DIST: the tail is propagated with the effective input, x_N <- Ad x_N + Bd (u_{N-1} + d), this step's disturbance.
-template <bool SQP, bool DIST = false>
+template <bool SQP, int DIST = 0>
 SE_PASS void shift_pass(int N, DistArg<DIST> da = {})
 {
     SSmem &sm = g_ssm;

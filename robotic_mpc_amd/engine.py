@@ -94,7 +94,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
             "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
             "mpcb_step_dist",
-            "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term")
+            "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term", "mpcb_rollout_obs")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -132,6 +132,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_rollout_pert.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), C.c_void_p]
     lib.mpcb_rollout_term.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, _dp,
                                       C.c_void_p]
+    lib.mpcb_rollout_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, _dp,
+                                     C.c_void_p]
     lib.mpcb_queue_used.argtypes = [C.c_void_p]
     lib.mpcb_sync.argtypes = [C.c_void_p]
     lib.mpcb_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
@@ -273,7 +275,7 @@ class MpcBatchEngine:
             setattr(r, name, C.cast(C.c_void_p(ptr), _dp if ty == "f8" else _ip))
         return r
 
-    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None, term=None):
+    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None, term=None, obs=None):
         """Asynchronous launch of closed-loop steps [step0, step1) into device buffers.  `yref`: the task reference schedules of
         the batch, a contiguous float64 device tensor [batch, Nsim + N, 5] (N the longest horizon; schedule_tensor) -- the same one
         for every launch of a run -- or None for the packed references (mpcb_rollout).  `pert`: the plant perturbation of the
@@ -282,7 +284,15 @@ class MpcBatchEngine:
         needs `yref` (schedule_tensor supplies the packed rows when the configurations carry no schedule).  `term`: the joint-wise
         terminal cost of the batch (mpcb_rollout_term; terminal_tensors), a dict of contiguous float64 device tensors "blocks"
         [batch, 18] (pqq 6 | pqv 6 | pvv 6) and "x_ref" [batch, Nsim, 12] (row t: the terminal reference of step t), both
-        required -- the same ones for every launch of a run; it needs `yref` likewise, and takes `pert` or the nominal plant."""
+        required -- the same ones for every launch of a run; it needs `yref` likewise, and takes `pert` or the nominal plant.
+        `obs`: the on-device disturbance observer of the batch (mpcb_rollout_obs; observer_tensors), a dict of contiguous float64
+        device tensors "gain" [batch, 12] (l1 6 | l2 6; read) and "d_hat" [batch, Nsim, 6] (written: row t = the estimate step t
+        used) -- the same ones for every launch of a run; it needs `yref` likewise, takes `pert` or the nominal plant, and is not
+        offered together with `term`."""
+        if obs is not None:
+            if term is not None:
+                raise ValueError("a disturbance observer (obs) is not offered together with a terminal cost (term)")
+            return self._rollout_pert(bufs, step0, step1, yref, pert, stream, obs=obs)
         if term is not None:
             return self._rollout_pert(bufs, step0, step1, yref, pert, stream, term)
         if pert is not None:
@@ -304,10 +314,26 @@ class MpcBatchEngine:
         if tuple(yref.shape) != (pb.batch, pb.Nsim + pb.N, 5) or not yref.is_contiguous() or str(yref.dtype) != "torch.float64":
             raise ValueError(f"yref must be a contiguous float64 tensor [{pb.batch}, {pb.Nsim + pb.N}, 5], got {tuple(yref.shape)} {yref.dtype}")
 
-    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None):
-        """rollout(pert=, term=): every shape is checked before the library is called."""
+    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None, obs=None):
+        """rollout(pert=, term=, obs=): every shape is checked before the library is called."""
         pb = self._pb
         tp = {}
+        if obs is not None:
+            oshapes = {"gain": (pb.batch, 12), "d_hat": (pb.batch, pb.Nsim, 6)}
+            if not isinstance(obs, dict) or set(obs) != set(oshapes):
+                raise ValueError(f"obs has the keys {tuple(oshapes)} (got {sorted(obs) if isinstance(obs, dict) else type(obs).__name__})")
+            if yref is None:
+                raise ValueError("a rollout with a disturbance observer needs yref: schedule_tensor(cfgs) supplies the packed rows when "
+                                 "there is no schedule")
+            for name, shape in oshapes.items():
+                t = obs[name]
+                if t is None or not hasattr(t, "data_ptr") or tuple(t.shape) != shape or not t.is_contiguous() \
+                        or str(t.dtype) != "torch.float64" or not t.is_cuda or t.device.index != self.device:
+                    raise ValueError(f"obs[{name!r}] must be a contiguous float64 tensor {list(shape)} on cuda:{self.device}, got "
+                                     f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t).__name__)} "
+                                     f"{getattr(t, 'device', '')}".rstrip())
+                tp[name] = C.cast(C.c_void_p(t.data_ptr()), _dp)
+            pert = {} if pert is None else pert
         if term is not None:
             tshapes = {"blocks": (pb.batch, 18), "x_ref": (pb.batch, pb.Nsim, 12)}
             if not isinstance(term, dict) or set(term) != set(tshapes):
@@ -344,6 +370,10 @@ class MpcBatchEngine:
 
             stream = torch.cuda.current_stream(self.device).cuda_stream
         r = self._result_struct(bufs)
+        if obs is not None:
+            self._check(self.lib.mpcb_rollout_obs(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
+                                                  tp["gain"], tp["d_hat"], C.c_void_p(stream)), "mpcb_rollout_obs")
+            return
         if term is not None:
             self._check(self.lib.mpcb_rollout_term(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
                                                    tp["blocks"], tp["x_ref"], C.c_void_p(stream)), "mpcb_rollout_term")
@@ -363,6 +393,20 @@ class MpcBatchEngine:
         dev = torch.device("cuda", self.device)
         blocks, x_ref = terminal.stack(cfgs)
         return {"blocks": torch.from_numpy(blocks).to(dev), "x_ref": torch.from_numpy(x_ref).to(dev)}
+
+    def observer_tensors(self, cfgs: Sequence[Dict]):
+        """The disturbance observers of a bucket on this engine's device -- {"gain": observer.stack(cfgs), "d_hat": zeros
+        [batch, Nsim, 6], which the rollout fills} -- or None when the configurations carry none (a bucket is all or nothing:
+        packing.bucket_key)."""
+        if not any(c.get("disturbance_observer") is not None for c in cfgs):
+            return None
+        import torch
+
+        from . import observer
+
+        dev = torch.device("cuda", self.device)
+        return {"gain": torch.from_numpy(observer.stack(cfgs)).to(dev),
+                "d_hat": torch.zeros((len(cfgs), int(cfgs[0]["Nsim"]), 6), dtype=torch.float64, device=dev)}
 
     def perturbation_tensors(self, cfgs: Sequence[Dict]):
         """The plant perturbations of a bucket (plant.stack) on this engine's device -- {"wcv", "u_dist", "x_noise"} -- or None when
@@ -385,12 +429,13 @@ class MpcBatchEngine:
 
     def schedule_tensor(self, cfgs: Sequence[Dict]):
         """The reference schedules of a bucket (reference.stack) on this engine's device, or None when the configurations carry
-        none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation or a terminal cost: those
-        rollouts always track a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
+        none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation, a terminal cost or a
+        disturbance observer: those rollouts always track a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
         from . import reference
 
         if not any(c.get("reference_schedule") is not None for c in cfgs):
-            if not any(c.get("plant_perturbation") is not None or c.get("terminal_cost") is not None for c in cfgs):
+            if not any(c.get("plant_perturbation") is not None or c.get("terminal_cost") is not None
+                       or c.get("disturbance_observer") is not None for c in cfgs):
                 return None
             import torch
 
@@ -564,12 +609,15 @@ class MpcBatchEngine:
         yref = self.schedule_tensor(cfgs)      # sampled and stacked once; every chunk gets the same array
         pert = self.perturbation_tensors(cfgs)
         term = self.terminal_tensors(cfgs)
+        obs = self.observer_tensors(cfgs)
         chunk = step_chunk if step_chunk and step_chunk > 0 else pb.Nsim
         self.last_kernel_ms = []
         for s0 in range(0, pb.Nsim, chunk):
-            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert, term=term)
+            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert, term=term, obs=obs)
             self.sync()
             self.last_kernel_ms.append(self.kernel_ms())
+        if obs is not None:
+            bufs["d_hat"] = obs["d_hat"]       # [batch, Nsim, 6]: the estimate every step used, beside the result logs
         return pb, bufs
 
     def run(self, cfgs: Sequence[Dict], chain, step_chunk: int = 0) -> Dict[str, np.ndarray]:
@@ -580,13 +628,17 @@ class MpcBatchEngine:
     # ------------------------------------------------------------------ host-buffer path
     def run_host_buffers(self, cfgs: Sequence[Dict], chain) -> Dict[str, np.ndarray]:
         """Same through mpcb_run (library-owned device buffers, numpy in/out, no torch).  mpcb_run takes no reference schedule:
-        configurations that carry one are refused, and so are configurations with a plant perturbation or a terminal cost."""
+        configurations that carry one are refused, and so are configurations with a plant perturbation, a terminal cost or a
+        disturbance observer."""
         if any(c.get("reference_schedule") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no reference schedule: run configurations with a reference_schedule through run() / run_device()")
         if any(c.get("plant_perturbation") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no plant perturbation: run configurations with a plant_perturbation through run() / run_device()")
         if any(c.get("terminal_cost") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no terminal cost: run configurations with a terminal_cost through run() / run_device()")
+        if any(c.get("disturbance_observer") is not None for c in cfgs):
+            raise ValueError("mpcb_run takes no disturbance observer: run configurations with a disturbance_observer through run() / "
+                             "run_device()")
         pb = make_problem(cfgs)
         params = packing.pack_batch(cfgs)
         robot = np.ascontiguousarray(chain.packed(cfgs[0]["t_ee"]), dtype=np.float64)

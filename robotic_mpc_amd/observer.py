@@ -21,12 +21,55 @@ work the same.
         u_prev = ctl.step(x, dist=d_hat)["u0"].clone()
         x = my_plant(x, u_prev)
 
-Not offered: an observer inside the rollout kernels (rollouts over a disturbed plant, ``plant_perturbation``, run the controller
-without an estimate), measurement-noise tuning beyond the choice of ``pole``, a disturbance that varies over the horizon.
+Rollouts run the same observer on the device (configuration key ``disturbance_observer``: ``{"pole": p}``, mpcb_rollout_obs), with
+the gains of ``observer_gains``: the closed loop above in one launch, over the plant of ``plant_perturbation``.
+
+Not offered: measurement-noise tuning beyond the choice of ``pole``, a disturbance that varies over the horizon.
 """
 from __future__ import annotations
 
 import numpy as np
+
+
+KEY = "disturbance_observer"
+
+
+def observer_gains(wcv, dt: float, pole: float):
+    """The gains that place both error poles of the per-joint predictor at ``pole``: ``l1 = a22 + 1 - 2 pole``,
+    ``l2 = (1 - pole)^2 / b2`` with ``a22 = exp(-wcv dt)``, ``b2 = 1 - a22``.  ``wcv`` [..., 6] a sequence, numpy array or torch
+    tensor; returns ``(l1, l2)`` of its kind and shape (float64)."""
+    if not (0.0 <= float(pole) < 1.0):
+        raise ValueError(f"pole must lie in [0, 1), got {pole!r}")
+    if not float(dt) > 0.0:
+        raise ValueError(f"dt must be > 0, got {dt!r}")
+    if hasattr(wcv, "exp") and hasattr(wcv, "dim"):      # a torch tensor
+        a22 = (-wcv.double() * float(dt)).exp()
+    else:
+        a22 = np.exp(-np.asarray(wcv, dtype=np.float64) * float(dt))
+    b2 = 1.0 - a22                                        # (as the engines pack it: mpc_pack.h)
+    return a22 + 1.0 - 2.0 * float(pole), (1.0 - float(pole)) ** 2 / b2
+
+
+def validate(spec) -> None:
+    """The configuration key ``disturbance_observer``: ``{"pole": p}``, 0 <= p < 1 (ValueError otherwise)."""
+    if not isinstance(spec, dict) or set(spec) != {"pole"}:
+        raise ValueError(f"{KEY} must be {{'pole': p}} or None, got {spec!r}")
+    try:
+        p = float(spec["pole"])
+    except (TypeError, ValueError):
+        raise ValueError(f"{KEY}.pole must be a number in [0, 1), got {spec['pole']!r}") from None
+    if not (0.0 <= p < 1.0):
+        raise ValueError(f"{KEY}.pole must lie in [0, 1), got {spec['pole']!r}")
+
+
+def stack(cfgs) -> np.ndarray:
+    """The gain array of a bucket of resolved configurations as mpcb_rollout_obs takes it: [B, 12] = l1 [6] | l2 [6], from each
+    simulation's MODEL bandwidths, dt and pole."""
+    out = np.zeros((len(cfgs), 12))
+    for i, c in enumerate(cfgs):
+        l1, l2 = observer_gains(c["wcv"], c["dt"], c[KEY]["pole"])
+        out[i, :6], out[i, 6:] = l1, l2
+    return out
 
 
 class DisturbanceObserver:
@@ -49,8 +92,7 @@ class DisturbanceObserver:
         self.dt, self.pole = float(dt), float(pole)
         self.a22 = torch.exp(-w * self.dt)
         self.b2 = 1.0 - self.a22                          # (as the engines pack it: mpc_pack.h)
-        self.l1 = self.a22 + 1.0 - 2.0 * self.pole
-        self.l2 = (1.0 - self.pole) ** 2 / self.b2
+        self.l1, self.l2 = observer_gains(w, self.dt, self.pole)
         self.reset()
 
     def reset(self):

@@ -9,6 +9,7 @@ simulator.py:668-674).  One ``.npz`` archive holds a whole run, batch-major:
     z [K,12,T1] u [K,6,T1] ee_pose [K,12,T1] ee_rpy [K,3,T1] ee_vel [K,6,T1] errors [K,7,T1]   (padded to the longest run)
     status/sqp_iter/qp_iter [K,T] residuals [K,T,4] cost/solver_time/plant_time [K,T]
     nsim             [K]  int          closed-loop steps of each simulation (its arrays use [:nsim(+1)])
+    d_hat [K,T,6], has_d_hat [K]       only when a simulation ran with a disturbance_observer: the estimates, and who has them
 
 Everything is plain numpy (no pickle), so the archive is readable without this package.
 """
@@ -52,7 +53,7 @@ def records_of(sim) -> Dict[str, np.ndarray]:
     return {"z": sm.z, "u": sm.u, "ee_pose": sm._ee_pose_log, "ee_rpy": sm._ee_rpy_log, "ee_vel": sm._ee_velocity_log,
             "status": sim.solver_status, "sqp_iter": sim.sqp_iter, "qp_iter": sim.qp_iter, "residuals": sim.residuals,
             "cost": sim.cost_history, "solver_time": sim.solver_time, "plant_time": sim.integration_time,
-            "errors": analysis_rows(sim)}
+            "errors": analysis_rows(sim), **({"d_hat": sim._d_hat} if getattr(sim, "_d_hat", None) is not None else {})}
 
 
 def analysis_rows(sim) -> np.ndarray:
@@ -85,6 +86,12 @@ def save_results(path: str, names: Sequence[str], configs: Sequence[Dict], recor
     for i, r in enumerate(records):
         a[i, :nsim[i]] = r["residuals"]
     out["residuals"] = a
+    if any(r.get("d_hat") is not None for r in records):
+        a, has = np.zeros((K, T, 6)), np.zeros(K, dtype=np.int64)
+        for i, r in enumerate(records):
+            if r.get("d_hat") is not None:
+                a[i, :nsim[i]], has[i] = r["d_hat"], 1
+        out["d_hat"], out["has_d_hat"] = a, has
     tmp = path + ".tmp.npz"
     np.savez_compressed(tmp, **out)
     os.replace(tmp, path)
@@ -124,6 +131,8 @@ def record_at(arch: Dict[str, np.ndarray], i: int) -> Dict[str, np.ndarray]:
     rec = {k: arch[k][i][:, :n + 1].copy() for k in LOG_KEYS_T1}
     rec.update({k: arch[k][i][:n].copy() for k in LOG_KEYS_T})
     rec["residuals"] = arch["residuals"][i][:n].copy()
+    if "d_hat" in arch and int(arch["has_d_hat"][i]):
+        rec["d_hat"] = arch["d_hat"][i][:n].copy()
     return rec
 
 

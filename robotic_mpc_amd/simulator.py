@@ -156,6 +156,7 @@ class Simulator:
         self.integration_time = rec["plant_time"] if "plant_time" in rec else np.zeros(self.Nsim)
         self._errors_rows = rec.get("errors")
         self._summary_row = rec.get("summary")
+        self._d_hat = rec.get("d_hat")     # [Nsim, 6] with a disturbance_observer: the estimate every step used
         self._data_computed = True
 
     def _invalidate_cache(self):
@@ -212,6 +213,8 @@ class Simulator:
             data["reference_schedule"] = rows      # [Nsim + 1, 5]: the targets in force at every logged column
         data.update(plant.realised(self.resolved))  # "input_disturbance" [Nsim, 6] / "measurement_noise" [Nsim, 12] when configured
         data.update(terminal.realised(self.resolved))  # "terminal_reference" [Nsim, 12] / "terminal_blocks" [6, 3] likewise
+        if getattr(self, "_d_hat", None) is not None:
+            data["d_hat"] = np.asarray(self._d_hat).T   # [6, Nsim]: the disturbance estimate step t predicted with (disturbance_observer)
         return data
 
     def get_analysis(self):
@@ -322,9 +325,12 @@ class _EngineRunner:
             yref = eng.schedule_tensor(cfgs)   # the bucket's reference schedules, or None (kept alive by the ticket)
             pert = eng.perturbation_tensors(cfgs)   # ... and its plant perturbations, or None (likewise)
             term = eng.terminal_tensors(cfgs)       # ... and its terminal costs, or None (likewise)
-            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert, term=term)
+            obs = eng.observer_tensors(cfgs)        # ... and its disturbance observers, or None (likewise)
+            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert, term=term, obs=obs)
             summary = eng.summary(bufs, stream=stream.cuda_stream)
-        return eng, stream, bufs, summary, (yref, pert, term)
+            if obs is not None:
+                bufs["d_hat"] = obs["d_hat"]        # the estimates travel with the logs: gathered, checkpointed, get_data()["d_hat"]
+        return eng, stream, bufs, summary, (yref, pert, term, obs)
 
     def collect(self, ticket):
         eng, stream, bufs, summary, _yref = ticket

@@ -28,8 +28,12 @@ STREAM_ROLLOUT_PERT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_str
 # built with its TERM flag, under budgets of their own below
 ROLLOUT_TERM_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_term.hip")
 STREAM_ROLLOUT_TERM_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_term.hip")
+# the kernels of the rollout with an on-device disturbance observer (mpcb_rollout_obs; modules of their own): the perturbed rollout's
+# on the engine built with its DIST flag (the estimate in the shared block), under budgets of their own below
+ROLLOUT_OBS_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_obs.hip")
+STREAM_ROLLOUT_OBS_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_obs.hip")
 SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC, ROLLOUT_PERT_SRC, STREAM_ROLLOUT_PERT_SRC,
-           ROLLOUT_TERM_SRC, STREAM_ROLLOUT_TERM_SRC)
+           ROLLOUT_TERM_SRC, STREAM_ROLLOUT_TERM_SRC, ROLLOUT_OBS_SRC, STREAM_ROLLOUT_OBS_SRC)
 
 
 def scan(asm_text):
@@ -90,6 +94,12 @@ BUDGET = {
     "22mpc_stream_term_kernelId": 157,
     "DevExecILi8ELi1EELi2EE10nlp_directILb1ELb1E": 55, "DevExecILi4ELi2EELi2EE10nlp_directILb1ELb1E": 54,
     "DevExecILi4ELi1EELi2EE10nlp_directILb1ELb1E": 8,
+    # the rollout with a disturbance observer (recorded: 265 / 328 / 61 for the kernel bodies -- the observer's gains and estimate
+    # live across the step in the six plant lanes -- 164 for the throughput engine's; its NLP pass with the effective input 35 / 36 / 2)
+    "22mpc_rollout_obs_kernelILi8ELi1E": 292, "22mpc_rollout_obs_kernelILi4ELi2E": 361, "22mpc_rollout_obs_kernelILi4ELi1E": 68,
+    "21mpc_stream_obs_kernelId": 180,
+    "DevExecILi8ELi1EELi0ELi2EE10nlp_directILb1ELb1E": 39, "DevExecILi4ELi2EELi0ELi2EE10nlp_directILb1ELb1E": 40,
+    "DevExecILi4ELi1EELi0ELi2EE10nlp_directILb1ELb1E": 8,
 }
 
 
