@@ -353,6 +353,25 @@ int mpcb_step_term(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
 int mpcb_step_dist(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                    const double *dist /* DEVICE [batch][6] or NULL */, int dist_changed, void *stream);
 
+/* ---- a scheduled, stage-varying surface in the controller step ---- */
+#define MPCB_NSURF 6 /* a row of a surface table: a b c d e f of S(x, y) = a x^2 + b y^2 + c x y + d x + e y + f (parameters [50..55]) */
+/* mpcb_step_warm whose task functions are evaluated on a surface that differs from stage to stage (SQP_RTI controllers): surf[i][k] =
+ * the six coefficients of simulation i at stage k = 0 .. N_i - 1, a DEVICE array [batch][N][MPCB_NSURF], N = mpcb_problem.N (the
+ * longest horizon of the batch; rows past a simulation's own horizon are never read), read during the launch only, like yref.  At
+ * stage k the row replaces parameters [50..55] wherever the task functions use them: S, its gradient (Sx, Sy), the unit normal n
+ * and the derivatives of n in g1 = S(X, Y) - Z and g2 = n . z_task, in the residual r_k, in the Jacobian of the Gauss-Newton QP
+ * (H_k, g_k) and in the cost.  g3, g4 and g5 do not depend on the surface.  Stage N has no task residual.  The reset guess, the
+ * warm-start modes and everything that carries are those of mpcb_step_warm.  Both engines run it, ragged horizons included on the
+ * throughput engine.  A window whose every row equals the packed coefficients is the arithmetic of mpcb_step_warm.
+ * surf_changed != 0 (the window differs from the previous step's -- a window that slides along a table does at every step -- or it
+ * was switched on or off) makes every simulation linearise again at the start of the step, exactly as ref_changed does.
+ * surf == NULL && surf_changed == 0 is mpcb_step_warm exactly (same kernels, same bits); surf == NULL with surf_changed != 0 is
+ * mpcb_step_warm from a fresh linearisation (the window switched off: the packed surface again).  MPCB_EINVAL: surf != NULL on a
+ * full-SQP controller.  MPCB_ESTATE on a handle not set up as a controller.  The sensitivities (mpcb_step_sens, mpcb_step_sens_w),
+ * the terminal cost (mpcb_step_term) and the input disturbance (mpcb_step_dist) are not offered together with a surface window. */
+int mpcb_step_surf(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const double *surf /* DEVICE [batch][N][MPCB_NSURF] or NULL */, int surf_changed, void *stream);
+
 /* ---- the controller step on either kernel family ---- */
 #define MPCB_ENGINE_AUTO (-1)    /* mpcb_controller_engine_for decides                                  */
 #define MPCB_ENGINE_LATENCY 0    /* one workgroup of 4-8 wavefronts per simulation (mpc_step_kernel)     */
@@ -491,7 +510,35 @@ int mpcb_rollout_obs(mpcb_handle *h, int step0, int step1, const mpcb_result *ou
                      const double *obs_gain /* DEVICE [batch][12] = l1[6] | l2[6], or NULL */,
                      double *d_hat /* DEVICE [batch][Nsim][6], written: row t = the estimate step t used */, void *stream);
 
-/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term / mpcb_rollout_obs launch of this handle went through the throughput
+/* ---- rollouts over a scheduled, stage-varying surface ---- */
+/* mpcb_rollout_pert whose surface moves with time: `surf_sched` is a DEVICE pointer [batch][Nsim + N][MPCB_NSURF], N =
+ * mpcb_problem.N (the longest horizon of the batch); row r of a simulation is a, b, c, d, e, f at time r * dt.  Closed-loop step t
+ * (0 <= t < Nsim) of simulation i, of own horizon N_i, uses surf_sched[i][t + k] at stage k = 0 .. N_i - 1 (stage N_i has no task
+ * residual), and column t of the `errors` log, t = 0 .. Nsim, is measured against surface row t and reference row t.  It is the
+ * closed loop
+ *   u_t = u0 of mpcb_step_surf(xhat_t, window t of yref_sched, ref_changed = 1, surf = window t of surf_sched, surf_changed = 1)
+ * over the plant of mpcb_rollout_pert (pert == NULL: the nominal plant; the same kernels serve both); cost and residuals are those
+ * of the returned iterate against window t.  Everything that carries in mpcb_rollout_pert carries, and nothing more: a step
+ * linearises again at its start, the row index is the absolute step number, and there is no shift.  The array is read during the
+ * launch only, by the lanes that linearise a stage (six doubles each) and by uniform loads for the error log: no workspace, LDS or
+ * mpcb_workspace_bytes change; pass the same array to every launch of one run.
+ *
+ * surf_sched == NULL is mpcb_rollout_pert exactly (the same kernels, the same bits).  A schedule whose every row equals the packed
+ * coefficients gives the perturbed rollout's results through these kernels.  MPCB_EINVAL: surf_sched on a full-SQP problem, with
+ * MPCB_PRECISION_FP32_RICCATI or without yref_sched (a run without a reference schedule passes the packed row on every row).
+ * MPCB_ESTATE on a controller handle or before mpcb_setup; the step-range rules of mpcb_rollout.  Whichever engine mpcb_setup chose
+ * runs it, work queue and ragged horizons included; mpcb_queue_used and mpcb_last_kernel_ms apply, and after such a launch
+ * mpcb_kernel_info reports this rollout's kernel.  Not offered together with the terminal cost (mpcb_rollout_term), the disturbance
+ * observer (mpcb_rollout_obs) or the sensitivities.  Measured at 600 steps (profiles/rollout_surf_rate.txt, device time, an all-equal
+ * schedule against mpcb_rollout_pert on the same closed loop): 1.018x at 256 simulations on the latency engine and 1.008x at 4096 on
+ * the throughput engine (queued) at N = 100, 1.011x and 1.018x at N = 20; the loop of mpcb_step_surf launches it replaces takes
+ * 1.17x - 1.73x.  The 256-register latency kernels hold 40 - 48 bytes more scratch per lane than the perturbed rollout's (the row is
+ * live from the end of the kinematics through the Jacobian loop); the throughput engine's kernel holds what it held. */
+int mpcb_rollout_surf(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
+                      const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
+                      const double *surf_sched /* DEVICE [batch][Nsim + N][MPCB_NSURF] or NULL */, void *stream);
+
+/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term / mpcb_rollout_obs / mpcb_rollout_surf launch of this handle went through the throughput
  * engine's work queue, 0: it did not (< 0: error).  Host state only. */
 int mpcb_queue_used(mpcb_handle *h);
 

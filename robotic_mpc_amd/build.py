@@ -26,7 +26,8 @@ SOURCES = ("mpc_kernel.hip", "mpc_step.hip", "mpc_stream_step.hip", "mpc_step_wa
            "mpc_step_term.hip", "mpc_stream_step_term.hip", "mpc_step_term_sens.hip", "mpc_stream_step_term_sens.hip",
            "mpc_rollout_ref.hip", "mpc_stream_rollout_ref.hip", "mpc_rollout_pert.hip", "mpc_stream_rollout_pert.hip",
            "mpc_rollout_term.hip", "mpc_stream_rollout_term.hip", "mpc_step_dist.hip", "mpc_stream_step_dist.hip",
-           "mpc_rollout_obs.hip", "mpc_stream_rollout_obs.hip")
+           "mpc_rollout_obs.hip", "mpc_stream_rollout_obs.hip", "mpc_step_surf.hip", "mpc_stream_step_surf.hip",
+           "mpc_rollout_surf.hip", "mpc_stream_rollout_surf.hip")
 
 
 def _stale(target: str) -> bool:

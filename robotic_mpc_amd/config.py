@@ -51,7 +51,11 @@ EXTENSION_DEFAULTS = {"translation_ee_t": (0.0, 0.0, 0.1), "urdf_path": None, "e
                       # the input-disturbance observer that runs inside the rollout (observer.py): None -- the controller predicts
                       # without an estimate -- or {"pole": p}, 0 <= p < 1, where both poles of the estimation error sit; SQP_RTI
                       # and fp64 only, not together with terminal_cost
-                      "disturbance_observer": None}
+                      "disturbance_observer": None,
+                      # a surface that moves or changes along the run (surface.py): None -- the constant surface_coeffs -- or a
+                      # JSON-serialisable spec {"kind": "table" | "moving", ...}; SQP_RTI and fp64 only, not together with
+                      # terminal_cost or disturbance_observer
+                      "surface_schedule": None}
 # codes of the parameter record (include/mpcbatch.h [7]); RK4 = 0 keeps default records unchanged
 PLANT_INTEGRATORS = {"RK4": 0, "Euler": 1, "RK2": 2, "RK3": 3}
 
@@ -308,8 +312,26 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
             raise ValueError("a disturbance_observer is offered with riccati_precision='fp64' only")
         observer.validate(obs)
         obs = {"pole": float(obs["pole"])}
+    surf = cfg["surface_schedule"]
+    if surf is not None:
+        from . import surface
+
+        if term is not None:
+            raise ValueError("a surface_schedule is not offered together with a terminal_cost")
+        if obs is not None:
+            raise ValueError("a surface_schedule is not offered together with a disturbance_observer")
+        if so["nlp_solver_type"] != "SQP_RTI":
+            raise ValueError("a surface_schedule is offered with nlp_solver_type='SQP_RTI' only")
+        if cfg["riccati_precision"] == "fp32":
+            raise ValueError("a surface_schedule is offered with riccati_precision='fp64' only")
+        surface.validate(surf)
+        surf = copy.deepcopy(dict(surf))
+        # (the number of rows of a table against this run's Nsim + N)
+        surface.sample({"surface_schedule": surf, "Nsim": Nsim, "N": N, "dt": dt,
+                        "coeffs": np.array([coeffs[k] for k in "abcdef"], dtype=np.float64)})
     return {
         "reference_schedule": schedule, "plant_perturbation": perturbation, "terminal_cost": term, "disturbance_observer": obs,
+        "surface_schedule": surf,
         "robot_name": cfg["robot_name"], "urdf_path": cfg["urdf_path"], "ee_frame": cfg["ee_frame"],
         "N": N, "Nsim": Nsim, "dt": dt,
         "solver_type": SOLVER_RTI if so["nlp_solver_type"] == "SQP_RTI" else SOLVER_SQP,

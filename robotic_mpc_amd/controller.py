@@ -38,6 +38,12 @@ controllers): it becomes ``x+ = Ad x + Bd (u + d)``, and with an estimate of ``d
 the controller tracks without the offset a disturbed plant otherwise leaves -- offset-free MPC.  Not offered together with ``sens``,
 ``sens_w`` or a terminal cost; ``d u0 / d d``, a per-stage disturbance profile and full SQP are not offered either.  Rollouts run
 the same observer on the device (configuration key ``disturbance_observer``, mpcb_rollout_obs).
+
+``set_surface(coeffs)`` / ``step(x, surface=coeffs)`` put a stage-varying surface under the horizon (SQP_RTI controllers): stage
+``k`` evaluates the task functions on the quadric ``coeffs[:, k]`` = a..f instead of the packed ``surface_coeffs`` -- a workpiece
+that moves, or a free-form surface handed over patch by patch (``robotic_mpc_amd.surface``).  Not offered together with ``sens``,
+``sens_w``, a terminal cost or an input disturbance.  Rollouts take the whole table (configuration key ``surface_schedule``,
+mpcb_rollout_surf).
 """
 from __future__ import annotations
 
@@ -94,6 +100,12 @@ class BatchController:
     _dist_on = False
     _dist_changed = False
     _dist_stream = None
+    # surface window (set_surface): the controller's own [B, N, 6] device buffer, whether it is in force, whether the next step must
+    # linearise again because of it, the stream of the last copy into it
+    _surf = None
+    _surf_on = False
+    _surf_changed = False
+    _surf_stream = None
 
     def __init__(self, configs: Sequence[Mapping], device: int = 0, engine: str = "latency"):
         if engine not in CONTROLLER_ENGINES:
@@ -393,6 +405,8 @@ class BatchController:
             return
         if x_ref is None:
             raise ValueError("set_terminal_cost needs the terminal reference x_ref with P")
+        if self._surf_on:
+            raise ValueError("a terminal cost is not offered while a surface window is in force (set_surface(None) switches it off)")
         if self._dist_on:
             raise ValueError("a terminal cost is not offered while an input disturbance is in force (set_input_disturbance(None) "
                              "switches it off)")
@@ -434,6 +448,8 @@ class BatchController:
         if self._term_on:
             raise ValueError("an input disturbance is not offered while a terminal cost is in force (set_terminal_cost(None) "
                              "switches it off)")
+        if self._surf_on:
+            raise ValueError("an input disturbance is not offered while a surface window is in force (set_surface(None) switches it off)")
         if isinstance(d, np.ndarray):
             shape, dtype_ok = tuple(d.shape), d.dtype == np.float64
         elif isinstance(d, torch.Tensor):
@@ -489,7 +505,76 @@ class BatchController:
             cur.wait_stream(self._dist_stream)
         return self._dist.clone()
 
-    def step(self, xhat, predict: bool = False, yref=None, shift=False, sens: bool = False, sens_w: bool = False, dist=None) -> Dict:
+    def _check_surface(self, coeffs):
+        """Validates a surface window ([B, N, 6] or [N, 6], float64, a numpy array or a tensor on the controller's device) without
+        touching the device; returns it as a [B, N, 6] or [1, N, 6] array / tensor."""
+        import torch
+
+        B, N = self.batch, self.N
+        if self.configs[0]["solver_type"] != packing.SOLVER_RTI:
+            raise ValueError("set_surface needs an SQP_RTI controller: the scheduled surface is not offered with full SQP")
+        if self._term_on:
+            raise ValueError("a surface window is not offered while a terminal cost is in force (set_terminal_cost(None) "
+                             "switches it off)")
+        if self._dist_on:
+            raise ValueError("a surface window is not offered while an input disturbance is in force (set_input_disturbance(None) "
+                             "switches it off)")
+        if isinstance(coeffs, np.ndarray):
+            shape, dtype_ok = tuple(coeffs.shape), coeffs.dtype == np.float64
+        elif isinstance(coeffs, torch.Tensor):
+            shape, dtype_ok = tuple(coeffs.shape), coeffs.dtype == torch.float64
+            if coeffs.device.type != "cuda" or coeffs.device.index != self.device:
+                raise ValueError(f"the surface window must live on cuda:{self.device}, got {coeffs.device}")
+        else:
+            raise ValueError(f"the surface window must be a torch tensor, a numpy array or None, got {type(coeffs).__name__}")
+        if shape not in ((B, N, 6), (N, 6)):
+            raise ValueError(f"the surface window must have shape ({B}, {N}, 6) or ({N}, 6), got {shape}")
+        if not dtype_ok:
+            raise ValueError(f"the surface window must be float64, got {coeffs.dtype}")
+        if isinstance(coeffs, np.ndarray) and not np.isfinite(coeffs).all():
+            raise ValueError("the surface window has non-finite entries")
+        return coeffs[None] if len(shape) == 2 else coeffs
+
+    def set_surface(self, coeffs):
+        """Puts a stage-varying surface under the following steps (SQP_RTI controllers; ``ValueError`` on a full-SQP one, and while
+        a terminal cost or an input disturbance is in force): ``coeffs[i, k]`` = the six quadric coefficients a..f that stage ``k``
+        of simulation ``i`` evaluates g1, g2 and their Jacobians on, [B, N, 6] float64 or [N, 6] for the whole batch (N the longest
+        horizon; rows past ``horizons[i]`` are not read); a numpy array or a tensor on the controller's device
+        (include/mpcbatch.h, mpcb_step_surf).  The values are copied into the controller's own device buffer and stay in force
+        across steps and ``reset()`` until they are set again; ``None`` switches back to the packed ``surface_coeffs``.  The next
+        step linearises again first, as after a new reference; everything else carries.  ``robotic_mpc_amd.surface`` builds such
+        windows: rows ``[t, t + N)`` of ``surface.sample(cfg)`` are the window of closed-loop step ``t``."""
+        import torch
+
+        if coeffs is None:
+            if self._surf_on:
+                self._surf_on, self._surf_changed = False, True
+            return
+        arr = self._check_surface(coeffs)
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(self.device)
+        if self._surf is None:
+            self._surf = torch.empty((self.batch, self.N, 6), dtype=torch.float64, device=dev)
+        if self._step_stream is not None and self._step_stream != cur:
+            cur.wait_stream(self._step_stream)        # a step still reading the buffer on another stream finishes first
+        src = torch.from_numpy(np.ascontiguousarray(arr)).to(dev) if isinstance(arr, np.ndarray) else arr
+        self._surf.copy_(src.expand(self.batch, self.N, 6))
+        self._surf_stream = cur
+        self._surf_on, self._surf_changed = True, True
+
+    def surface(self):
+        """The surface window in force: ``None``, or a new [B, N, 6] float64 tensor on the controller's device."""
+        import torch
+
+        if not self._surf_on:
+            return None
+        cur = torch.cuda.current_stream(self.device)
+        if self._surf_stream is not None and self._surf_stream != cur:
+            cur.wait_stream(self._surf_stream)
+        return self._surf.clone()
+
+    def step(self, xhat, predict: bool = False, yref=None, shift=False, sens: bool = False, sens_w: bool = False, dist=None,
+             surface=None) -> Dict:
         """One MPC step of every controller from the feedback states ``xhat`` ([B, 12] q; qdot, float64: a tensor on the
         controller's device, or a numpy array that is copied there).
 
@@ -536,9 +621,22 @@ class BatchController:
         ``dist`` (optional) is ``set_input_disturbance(dist)`` before the step: the disturbance then stays in force for later
         steps.  While one is in force the step's QP, ``cost`` and ``residuals`` are those of the model ``x+ = Ad x + Bd (u + d)``,
         ``x_pred`` is that model's prediction, and ``shift`` propagates the tail with it; ``sens=True`` and ``sens_w=True`` then
-        raise ``ValueError``.  The step costs what a step with a new reference costs (``profiles/controller_step_rate_dist.txt``)."""
+        raise ``ValueError``.  The step costs what a step with a new reference costs (``profiles/controller_step_rate_dist.txt``).
+
+        ``surface`` (optional) is ``set_surface(surface)`` before the step: the window then stays in force for later steps.  While
+        one is in force stage ``k`` works on the quadric of its row ``k``; ``cost`` and ``residuals`` are those of that problem;
+        ``sens=True``, ``sens_w=True`` and ``dist`` then raise ``ValueError``."""
         import torch
 
+        if surface is not None:
+            if dist is not None:
+                raise ValueError("a surface window is not offered together with an input disturbance (dist)")
+            self._check_surface(surface)
+        if (sens or sens_w) and (self._surf_on or surface is not None):
+            raise ValueError("step(sens=True) / step(sens_w=True) are not offered while a surface window is in force "
+                             "(set_surface(None) switches it off)")
+        if dist is not None and self._surf_on:
+            raise ValueError("an input disturbance is not offered while a surface window is in force (set_surface(None) switches it off)")
         if dist is not None:
             self._check_disturbance(dist)
         if (sens or sens_w) and (self._dist_on or dist is not None):
@@ -560,6 +658,8 @@ class BatchController:
             self.set_reference(yref)
         if dist is not None:
             self.set_input_disturbance(dist)
+        if surface is not None:
+            self.set_surface(surface)
         stream = torch.cuda.current_stream(self.device)
         warm = None
         if self._reset_mask is not None or not shift_all or bool(shift):
@@ -572,8 +672,12 @@ class BatchController:
             stream.wait_stream(self._term_stream)     # the copy of the terminal cost lands before the step reads it
         if self._dist_on and self._dist_stream is not None and self._dist_stream != stream:
             stream.wait_stream(self._dist_stream)     # the copy of the disturbance lands before the step reads it
-        # (a terminal cost or a disturbance that was switched off leaves a stale linearisation behind, exactly as a changed reference does)
-        ref_changed = self._ref_changed or (self._term_changed and not self._term_on) or (self._dist_changed and not self._dist_on)
+        if self._surf_on and self._surf_stream is not None and self._surf_stream != stream:
+            stream.wait_stream(self._surf_stream)     # the copy of the surface window lands before the step reads it
+        # (a terminal cost, a disturbance or a surface window that was switched off leaves a stale linearisation behind, exactly as a
+        # changed reference does)
+        ref_changed = self._ref_changed or (self._term_changed and not self._term_on) or (self._dist_changed and not self._dist_on) \
+            or (self._surf_changed and not self._surf_on)
         term = dict(term=self._term, term_changed=self._term_changed) if self._term_on else {}
         if sens:
             if self._sens is None:
@@ -598,6 +702,9 @@ class BatchController:
         elif self._dist_on:
             self.engine.step_dist(io, self._yref if self._ref_on else None, ref_changed=ref_changed, warm=warm, reset=self._reset,
                                   dist=self._dist, dist_changed=self._dist_changed, stream=stream.cuda_stream)
+        elif self._surf_on:
+            self.engine.step_surf(io, self._yref if self._ref_on else None, ref_changed=ref_changed, warm=warm, reset=self._reset,
+                                  surf=self._surf, surf_changed=self._surf_changed, stream=stream.cuda_stream)
         elif warm is not None:
             self.engine.step_warm(io, self._yref if self._ref_on else None, ref_changed=ref_changed, warm=warm,
                                   reset=self._reset, stream=stream.cuda_stream)
@@ -611,6 +718,7 @@ class BatchController:
         self._ref_changed = False
         self._term_changed = False
         self._dist_changed = False
+        self._surf_changed = False
         self._reset_mask = None
         out = {k: v for k, v in io.items() if k != "xhat"}
         if sens:

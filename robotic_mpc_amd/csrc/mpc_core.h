@@ -187,8 +187,20 @@ template <>
 struct DistPtr<1> {
     const double *dist = nullptr;
 };
-template <class Ex, int TERM = 0, int DIST = 0>
-struct Engine : DistPtr<DIST> {
+// SURF (the kernels of mpcb_step_surf and mpcb_rollout_surf only, mpc_step_surf.hip / mpc_rollout_surf.hip): the surface is scheduled and
+// stage-varying -- every evaluation of the task functions at stage k of the step under way reads the six coefficients a..f from row k
+// of that step's window of a surface table (SurfPtr::surf; control_step and rollout set it), in place of InstParams::coeffs: the
+// linearisation and the residual-only pass (task_lin's overload with coefficients), and the logged task errors with the row of the
+// logged column.  The row is lane-varying (lane <-> stage): six vector loads, issued past the kinematics where the targets are.
+// Nothing else changes: the cost and residual passes read r, Y and the Jacobian from the stage records.  An empty base otherwise.
+template <int SURF>
+struct SurfPtr {};
+template <>
+struct SurfPtr<1> {
+    const double *surf = nullptr;
+};
+template <class Ex, int TERM = 0, int DIST = 0, int SURF = 0>
+struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
     static constexpr int NT = Ex::NT;  // lanes per simulation
     Ex &ex;
     Ctx c;
@@ -482,6 +494,13 @@ struct Engine : DistPtr<DIST> {
         else return u;
     }
 
+    // (SURF) row k of the step's surface window, as task_lin / task_errors read it: cf[i], i < NSURF
+    struct SurfRow {
+        const double *p;
+        MPC_HD double operator[](int i) const { return gld(p + i); }
+    };
+    MPC_HD SurfRow surf_row(int k) const { return SurfRow{ex.uni(this->surf) + (size_t)k * NSURF}; }
+
     // The fast path's right-hand side of joint j at one stage (Gamma = 0): condensed gradient gt = g at (dw, pi, lam) = 0 with the
     // feedback step dx_0 = x_hat - x_0 embedded, and rb = b + A dx_0.  ONE function with explicit fused multiply-adds for its two
     // callers -- fast_rhs (a pass of its own: first attempt of a launch, SQP) and the residual-norm items of nlp_direct (SQP_RTI) -- so
@@ -694,7 +713,8 @@ struct Engine : DistPtr<DIST> {
                             rec[O_BD + j] = (xx[j] + P.a12[j] * vj + P.b1[j] * ue) - xn[j];
                             rec[O_BD + 6 + j] = (P.a22[j] * vj + P.b2[j] * ue) - xn[6 + j];
                         }
-                        task_lin<true, double *, REF>(rb, P, xx, xx + 6, rec, rec);
+                        if constexpr (SURF) task_lin<true, double *, REF>(rb, P, surf_row(k), xx, xx + 6, rec, rec);
+                        else task_lin<true, double *, REF>(rb, P, xx, xx + 6, rec, rec);
                         double s_ = 0.0;
                         if constexpr (REF) {
                             double t[NTASK];    // (loaded here, past the kinematics: the linearisation is register-bound)
@@ -739,7 +759,8 @@ struct Engine : DistPtr<DIST> {
                         sm.logv[24 + j] = zn[j]; sm.logv[30 + j] = zn[6 + j];
                     }
                     plant_log(rb, zn, sm.logv);
-                    if constexpr (REF && RLOG) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, ref.y + NTASK);
+                    if constexpr (REF && RLOG && SURF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, ref.y + NTASK, surf_row(1));
+                    else if constexpr (REF && RLOG) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, ref.y + NTASK);
                     else task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
                     sm.ret[6] = ex.clock() - tp0;
                 }
@@ -3244,7 +3265,8 @@ struct Engine : DistPtr<DIST> {
                     if (k < Nl) {
 #pragma unroll
                         for (int i = 0; i < 6; i++) uu[i] = r1[O_U + i] + alpha * r1[O_QW + i];
-                        task_lin<false, double *, REF>(rb, P, xx, xx + 6, rec, rec);
+                        if constexpr (SURF) task_lin<false, double *, REF>(rb, P, surf_row(k), xx, xx + 6, rec, rec);
+                        else task_lin<false, double *, REF>(rb, P, xx, xx + 6, rec, rec);
                         const auto xnext = [&](int i) { return rn[O_X + i] + alpha * rn[O_QW + 6 + i]; };
                         if constexpr (REF) {
                             double t[NTASK];
@@ -3415,14 +3437,20 @@ struct Engine : DistPtr<DIST> {
     // of the next step in registers; d^_t is put into the shared block (sm.logv[lv_dhat], what eff_u reads) and into row t of the log
     // ob.d_hat -- write-only here -- before the solve.  Step 0 takes v^_0 = y_0, d^_0 = 0.  Across a launch boundary the twelve
     // doubles travel in w.state[ST_OBS], stored and loaded where ST_Z is.
+    // SURF (the engine's flag, with REF and PERT; the kernels of mpcb_rollout_surf, mpc_rollout_surf.hip): `ssched` [Nsim + N][NSURF] is
+    // this simulation's surface table.  Step t's window is ssched + t * NSURF -- stage k reads row t + k -- and log column t measures
+    // the task errors against row t, as the reference schedule's.  The step linearises again at its start (REF), so nothing of a
+    // window carries; the row index is the absolute step number, in every launch.
     struct NoSched {};
     template <bool REF = false, bool PERT = false, bool OBS = false>
     MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {},
                         typename std::conditional<PERT, PlantPert, NoSched>::type pert = {},
                         typename std::conditional<TERM == TERM_TABLE, TermTab, NoSched>::type tt = {},
-                        typename std::conditional<OBS, ObsArg, NoSched>::type ob = {})
+                        typename std::conditional<OBS, ObsArg, NoSched>::type ob = {},
+                        typename std::conditional<SURF != 0, const double *, NoSched>::type ssched = {})
     {
         static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
+        static_assert(!SURF || (REF && PERT && !TERM && !DIST), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
         static_assert(!TERM || (TERM == TERM_TABLE && REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
         static_assert(OBS == (DIST == DIST_SHARED) && (!OBS || (REF && PERT)), "the rollout with an observer runs the perturbed rollout's step on the engine whose disturbance is in the shared block");
         static_assert(!DIST || OBS, "a rollout takes its input disturbance from its own observer");
@@ -3436,7 +3464,8 @@ struct Engine : DistPtr<DIST> {
         int log_lo = step0 == 0 ? 0 : step0 + 1;   // first log column this launch produces
         if (step0 == 0) {
             initial_guess();
-            if constexpr (REF) log_lo = ex.uni(log_state<true>(out, inst, 0, log_lo, false, sched));
+            if constexpr (REF && SURF) log_lo = ex.uni(log_state<true>(out, inst, 0, log_lo, false, sched, ssched));
+            else if constexpr (REF) log_lo = ex.uni(log_state<true>(out, inst, 0, log_lo, false, sched));
             else log_lo = ex.uni(log_state(out, inst, 0, log_lo, false));
         } else {
             ex.par([&](int lane) {
@@ -3486,6 +3515,7 @@ struct Engine : DistPtr<DIST> {
                 lin_valid = false;
             }
             if constexpr (TERM == TERM_TABLE) term.x = tt.x_ref + (size_t)i * NX;
+            if constexpr (SURF) this->surf = ssched + (size_t)i * NSURF;
             if constexpr (OBS) ex.par([&](int lane) {
                 // the estimate this step's model takes: into the shared block for eff_u, and row i of the log
                 if (lane < 6) {
@@ -3534,7 +3564,8 @@ struct Engine : DistPtr<DIST> {
             ex.par([&](int lane) {
                 if (lane < NX) sm.xhat[lane] = sm.logv[24 + lane];
             });
-            if constexpr (REF) log_lo = ex.uni(log_state<true>(out, inst, i + 1, log_lo, plant_done, sched + (size_t)(i + 1) * NTASK));
+            if constexpr (REF && SURF) log_lo = ex.uni(log_state<true>(out, inst, i + 1, log_lo, plant_done, sched + (size_t)(i + 1) * NTASK, ssched + (size_t)(i + 1) * NSURF));
+            else if constexpr (REF) log_lo = ex.uni(log_state<true>(out, inst, i + 1, log_lo, plant_done, sched + (size_t)(i + 1) * NTASK));
             else log_lo = ex.uni(log_state(out, inst, i + 1, log_lo, plant_done));
             if constexpr (PERT) {
                 // the feedback state of step i + 1, when this launch runs it (no row Nsim exists; the next launch forms its own)
@@ -3843,6 +3874,8 @@ struct Engine : DistPtr<DIST> {
     // sensitivity of u0 to its reference leaves through io.du0_dxe.  Not combined with SENSW.
     // DIST (the engine's flag; the kernels of mpcb_step_dist): io.dist holds this simulation's input disturbance (SQP_RTI; the line
     // search of full SQP does not know it).  Not combined with SENS, SENSW or TERM.
+    // SURF (the engine's flag; the kernels of mpcb_step_surf): io.surf holds this simulation's surface window, row k = stage k's a..f.
+    // Not combined with SENS, SENSW, TERM or DIST.
     template <bool WARM = false, bool SENS = false, bool SENSW = false>
     MPC_HD void control_step(const StepIO &io, int inst, bool reset)
     {
@@ -3852,6 +3885,8 @@ struct Engine : DistPtr<DIST> {
         Ws &w = c.w;
         if constexpr (TERM) term = io.term + (size_t)inst * NTERM;
         if constexpr (DIST) this->dist = io.dist + (size_t)inst * NU;
+        static_assert(!(SURF && (TERM || DIST || SENS || SENSW)), "the scheduled surface is not offered with sensitivities, a terminal cost or an input disturbance");
+        if constexpr (SURF) this->surf = io.surf + (size_t)inst * N * NSURF;
         bool lin_valid = false;
         int mode = WARM_CARRY;
         if constexpr (WARM) {
@@ -3913,9 +3948,11 @@ struct Engine : DistPtr<DIST> {
     // contiguous runs of up to LOGB columns per row: `log_lo` = first column of the current block still in LDS.
     // `computed`: sm.logv already holds the pose / rpy / J qdot / task errors of sm.xhat (done inside the last NLP pass)
     // REF (rollout<true>): the task errors are measured against `yrow`, the reference schedule's row of this column
+    // SURF (with REF): and against `srow`, the surface table's row of this column (uniform loads: the table is read-only in a launch)
     template <bool REF = false>
     MPC_PASS int log_state(const Outputs &out, int inst, int col, int log_lo, bool computed,
-                           typename std::conditional<REF, const double *, NoSched>::type yrow = {})
+                           typename std::conditional<REF, const double *, NoSched>::type yrow = {},
+                           typename std::conditional<SURF != 0, const double *, NoSched>::type srow = {})
     {
         Smem &sm = ex.smem();
         const Robot &rb = sm.rb;
@@ -3925,7 +3962,8 @@ struct Engine : DistPtr<DIST> {
 #pragma unroll
                 for (int i = 0; i < 12; i++) z[i] = sm.xhat[i];
                 plant_log(rb, z, sm.logv);
-                if constexpr (REF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow);
+                if constexpr (REF && SURF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow, SurfRow{srow});
+                else if constexpr (REF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow);
                 else task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
             }
         });

@@ -149,8 +149,8 @@ __global__ void mpc_debug_task_lin_kernel(int n, Robot rb, const InstParams *__r
 
 // ------------------------------------------------------------------------------------ host
 // The variants of the controller step and the kinds of rollout; each is one kernel (family) per engine, see with_kernel below.
-enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS, STEP_DIST };
-enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM, ROLLOUT_OBS };
+enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS, STEP_DIST, STEP_SURF };
+enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM, ROLLOUT_OBS, ROLLOUT_SURF };
 
 struct mpcb_handle {
     int device = -1;
@@ -227,11 +227,13 @@ static int with_kernel(const mpcb_handle *h, StepVariant v, F &&f)
 {
     const int nw = h->waves_per_sim, wpe = h->wpe;
     if (h->engine == 1)
-        return f(v == STEP_DIST      ? stream_step_dist_kernel()
+        return f(v == STEP_SURF      ? stream_step_surf_kernel()
+                 : v == STEP_DIST    ? stream_step_dist_kernel()
                  : v == STEP_TERM_SENS ? stream_step_term_sens_kernel() : v == STEP_TERM ? stream_step_term_kernel()
                  : v == STEP_SENSW   ? stream_step_sensw_kernel()     : v == STEP_SENS ? stream_step_sens_kernel()
                  : v == STEP_WARM    ? stream_step_warm_kernel()      : stream_step_kernel());
-    return f(v == STEP_DIST      ? step_dist_kernel(nw, wpe)
+    return f(v == STEP_SURF      ? step_surf_kernel(nw, wpe)
+             : v == STEP_DIST    ? step_dist_kernel(nw, wpe)
              : v == STEP_TERM_SENS ? step_term_sens_kernel(nw, wpe) : v == STEP_TERM ? step_term_kernel(nw, wpe)
              : v == STEP_SENSW   ? step_sensw_kernel(nw, wpe)     : v == STEP_SENS ? step_sens_kernel(nw, wpe)
              : v == STEP_WARM    ? step_warm_kernel(nw, wpe)      : step_kernel(nw, wpe));
@@ -241,10 +243,12 @@ static int with_kernel(const mpcb_handle *h, RolloutKind kind, F &&f)
 {
     const int nw = h->waves_per_sim, wpe = h->wpe;
     if (h->engine == 1)
-        return kind == ROLLOUT_OBS  ? f(stream_rollout_obs_kernel())
+        return kind == ROLLOUT_SURF ? f(stream_rollout_surf_kernel())
+             : kind == ROLLOUT_OBS  ? f(stream_rollout_obs_kernel())
              : kind == ROLLOUT_TERM ? f(stream_rollout_term_kernel()) : kind == ROLLOUT_PERT ? f(stream_rollout_pert_kernel())
              : kind == ROLLOUT_REF  ? f(stream_rollout_ref_kernel())  : f(stream_rollout_kernel(h->pb.precision));
-    return kind == ROLLOUT_OBS  ? f(rollout_obs_kernel(nw, wpe))
+    return kind == ROLLOUT_SURF ? f(rollout_surf_kernel(nw, wpe))
+         : kind == ROLLOUT_OBS  ? f(rollout_obs_kernel(nw, wpe))
          : kind == ROLLOUT_TERM ? f(rollout_term_kernel(nw, wpe)) : kind == ROLLOUT_PERT ? f(rollout_pert_kernel(nw, wpe))
          : kind == ROLLOUT_REF  ? f(rollout_ref_kernel(nw, wpe))  : f(rollout_kernel(nw, wpe));
 }
@@ -255,6 +259,7 @@ struct RolloutArgs {
     unsigned grid; Outputs out; int step0, step1;
     int *queue; int chunk_steps; long long timeout_ticks;   // throughput engine
     const double *yref_sched; PlantPert pert; TermTab term; ObsArg obs;  // ref / pert / term / obs
+    const double *surf_sched;                                            // surf
 };
 
 // Every kernel starts (pb, robot record, params, ws_base, ws_stride).  Latency engine: the record by value, a workgroup of
@@ -298,6 +303,10 @@ static void launch(RolloutObsFn k, const mpcb_handle *h, hipStream_t s, const Ro
 {
     latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.obs);
 }
+static void launch(RolloutSurfFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.surf_sched);
+}
 static void launch(StreamRolloutFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
 {
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks);
@@ -318,6 +327,11 @@ static void launch(StreamRolloutTermFn k, const mpcb_handle *h, hipStream_t s, c
 static void launch(StreamRolloutObsFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
 {
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.obs);
+}
+
+static void launch(StreamRolloutSurfFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.surf_sched);
 }
 
 // One launch of `variant`'s kernel on stream s, between the two events mpcb_last_kernel_ms reads.  Latency engine: the dynamic-LDS
@@ -341,7 +355,8 @@ static int timed_launch(mpcb_handle *h, V variant, hipStream_t s, const Args &ar
 }
 
 static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
-                       const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream);
+                       const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream,
+                       const double *surf_sched = nullptr);
 
 extern "C" {
 
@@ -625,11 +640,20 @@ int mpcb_rollout_obs(mpcb_handle *h, int step0, int step1, const mpcb_result *o,
     return rollout_any(h, step0, step1, o, yref_sched, pert_, nullptr, nullptr, obs_gain, d_hat, stream);
 }
 
+// (surf_sched == NULL: the kernels of mpcb_rollout_pert, chosen by pert and yref_sched; otherwise those of the rollout over a scheduled
+// surface, mpc_rollout_surf.hip / mpc_stream_rollout_surf.hip, through the same launch path -- a null pert is the nominal plant inside them)
+int mpcb_rollout_surf(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                      const double *surf_sched, void *stream)
+{
+    return rollout_any(h, step0, step1, o, yref_sched, pert_, nullptr, nullptr, nullptr, nullptr, stream, surf_sched);
+}
+
 }  // extern "C"
 
-// The one launch path of every rollout: at most one of term_blocks and obs_gain is given.
+// The one launch path of every rollout: at most one of term_blocks, obs_gain and surf_sched is given.
 static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
-                       const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream)
+                       const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream,
+                       const double *surf_sched)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
@@ -656,6 +680,12 @@ static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *
         return fail(h, MPCB_EINVAL, "mpcb_rollout_obs: a rollout with an observer needs a reference schedule (the packed rows when there is none)");
     if (obs_gain && !d_hat)
         return fail(h, MPCB_EINVAL, "mpcb_rollout_obs: obs_gain needs d_hat, the log of the estimates");
+    if (surf_sched && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_surf: a surface schedule is offered in fp64 only (no fp32 Riccati leg)");
+    if (surf_sched && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_surf: a surface schedule is offered with SQP_RTI only");
+    if (surf_sched && !yref_sched)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_surf: a rollout over a scheduled surface needs a reference schedule (the packed rows when there is none)");
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -665,12 +695,13 @@ static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *
         return fail(h, MPCB_EINVAL, "every result array must be provided");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const RolloutKind kind = obs_gain ? ROLLOUT_OBS : term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
+    const RolloutKind kind = surf_sched ? ROLLOUT_SURF : obs_gain ? ROLLOUT_OBS : term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
     RolloutArgs args{};
     args.yref_sched = yref_sched;
     if (pert_) args.pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
     args.term = TermTab{term_blocks, term_xref};
     args.obs = ObsArg{obs_gain, d_hat};
+    args.surf_sched = surf_sched;
     std::memcpy(&args.out, o, sizeof args.out);
     args.step0 = step0;
     args.step1 = step1;
@@ -751,7 +782,7 @@ int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
 
 static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                      const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream,
-                     const double *dist = nullptr, int dist_changed = 0);
+                     const double *dist = nullptr, int dist_changed = 0, const double *surf = nullptr, int surf_changed = 0);
 
 // (du0_dw == NULL: all of the above; otherwise the kernels that also form the weight sensitivity, supersets of the sens ones)
 int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
@@ -776,9 +807,17 @@ int mpcb_step_dist(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
     return step_impl(h, io, yref, ref_changed, warm, reset, nullptr, nullptr, nullptr, 0, nullptr, stream, dist, dist_changed);
 }
 
+// (surf == NULL: mpcb_step_warm, after surf_changed from a fresh linearisation; otherwise the kernels built with the scheduled surface --
+// supersets of the warm-start ones)
+int mpcb_step_surf(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                   const double *surf, int surf_changed, void *stream)
+{
+    return step_impl(h, io, yref, ref_changed, warm, reset, nullptr, nullptr, nullptr, 0, nullptr, stream, nullptr, 0, surf, surf_changed);
+}
+
 static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                      const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream,
-                     const double *dist, int dist_changed)
+                     const double *dist, int dist_changed, const double *surf, int surf_changed)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
@@ -797,20 +836,26 @@ static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref,
     if (du0_dxe && (!sens || !term)) return fail(h, MPCB_EINVAL, "mpcb_step_term: du0_dxe needs sens (du0_dx and valid) and term");
     if (dist && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
         return fail(h, MPCB_EINVAL, "mpcb_step_dist: the input disturbance is offered with SQP_RTI; this controller runs full SQP");
-    const StepVariant variant = dist ? STEP_DIST : term ? (sens ? STEP_TERM_SENS : STEP_TERM) : du0_dw ? STEP_SENSW : sens ? STEP_SENS : warm ? STEP_WARM : STEP_BASE;
+    if (surf && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_step_surf: the scheduled surface is offered with SQP_RTI; this controller runs full SQP");
+    if (surf && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_step_surf: the scheduled surface is offered in fp64 only (no fp32 Riccati leg)");
+    const StepVariant variant = surf ? STEP_SURF : dist ? STEP_DIST : term ? (sens ? STEP_TERM_SENS : STEP_TERM) : du0_dw ? STEP_SENSW : sens ? STEP_SENS : warm ? STEP_WARM : STEP_BASE;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     StepArgs args;
     StepIO &sio = args.io;
     std::memcpy(&sio, io, sizeof(mpcb_step_io));
     sio.yref = yref;
-    // (new weights, a new terminal cost or a new input disturbance make the carried linearisation stale exactly as a new reference does)
-    sio.ref_changed = (ref_changed != 0 || term_changed != 0 || dist_changed != 0 || h->weights_changed) ? 1 : 0;
+    // (new weights, a new terminal cost, a new input disturbance or a new surface window make the carried linearisation stale exactly
+    // as a new reference does)
+    sio.ref_changed = (ref_changed != 0 || term_changed != 0 || dist_changed != 0 || surf_changed != 0 || h->weights_changed) ? 1 : 0;
     sio.warm = warm;
     sio.du0_dw = du0_dw;
     sio.term = term;
     sio.du0_dxe = du0_dxe;
     sio.dist = dist;
+    sio.surf = surf;
     if (sens) { sio.du0_dx = sens->du0_dx; sio.du0_dyref = sens->du0_dyref; sio.sens_valid = sens->valid; }
     args.reset = (reset != 0 || h->reset_next) ? 1 : 0;
     if (int rc = timed_launch(h, variant, s, args)) return rc;

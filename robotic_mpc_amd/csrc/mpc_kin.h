@@ -180,6 +180,72 @@ MPC_HD void task_lin(const Robot &rb, const InstParams &P, const double *q, cons
     }
 }
 
+// The same on a scheduled surface (SURF: mpcb_step_surf / mpcb_rollout_surf): the six coefficients a..f of THIS stage come from `cf`
+// (cf[i], i < 6: a row of the surface table, lane-varying) and replace P.coeffs in S, Sx, Sy, the normal and its derivatives; P still
+// gives px_ref / vy_ref where !RAW.  Restated, not shared: the function above keeps its code.
+template <bool JAC, class PG, bool RAW, class CF>
+MPC_HD void task_lin(const Robot &rb, const InstParams &P, CF cf, const double *q, const double *qd, double *rec_r, PG rec_g)
+{
+    Kin k;
+    kin_eval(rb, q, k);
+    const V3 yh = col(k.R, 1), zh = col(k.R, 2);
+    const V3 tw = mul(k.R, v3(rb.t_ee[0], rb.t_ee[1], rb.t_ee[2]));
+    const V3 pt = k.p + tw;
+    const double a = cf[0], b = cf[1], c = cf[2], d = cf[3], e = cf[4], f = cf[5];   // (read here, past the kinematics)
+    const double X = pt.x, Y = pt.y;
+    const double S = a * X * X + b * Y * Y + c * X * Y + d * X + e * Y + f;          // surface.py:21
+    const double Sx = 2 * a * X + c * Y + d, Sy = 2 * b * Y + c * X + e;             // surface.py:246-247
+    const double nn = sqrt(Sx * Sx + Sy * Sy + 1.0);                                // surface.py:255
+    const double inn = 1.0 / nn;
+    const V3 n = v3(Sx * inn, Sy * inn, -inn);
+    V3 vl = v3(0, 0, 0), om = v3(0, 0, 0);
+    V3 cj[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        cj[j] = cross(k.o[j], k.z[j]);  // WORLD spatial Jacobian, linear rows (prediction_model.py:163-164)
+        vl = vl + qd[j] * cj[j];
+        om = om + qd[j] * k.z[j];
+    }
+    const V3 s = vl + cross(om, tw);
+    rec_r[O_R + 0] = (S - pt.z) - 0.0;
+    rec_r[O_R + 1] = dot(n, zh) - (RAW ? 0.0 : 1.0);
+    rec_r[O_R + 2] = yh.x - 0.0;
+    rec_r[O_R + 3] = pt.x - (RAW ? 0.0 : P.px_ref);
+    rec_r[O_R + 4] = dot(yh, s) - (RAW ? 0.0 : P.vy_ref);  // v_task,y = (R^T (v + w x t_w))_y, prediction_model.py:313
+    if (!JAC) return;
+    const V3 mX = v3(2 * a, c, 0), mY = v3(c, 2 * b, 0);
+    const double pX = dot(n, mX), pY = dot(n, mY);
+    const V3 nX = inn * (mX - pX * n), nY = inn * (mY - pY * n);
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        const V3 zi = k.z[i];
+        const V3 dpt = cross(zi, pt - k.o[i]);
+        const V3 dzh = cross(zi, zh), dyh = cross(zi, yh), dtw = cross(zi, tw);
+        rec_g[O_GQ + 0 * 6 + i] = Sx * dpt.x + Sy * dpt.y - dpt.z;
+        const V3 dn = dpt.x * nX + dpt.y * nY;
+        rec_g[O_GQ + 1 * 6 + i] = dot(dn, zh) + dot(n, dzh);
+        rec_g[O_GQ + 2 * 6 + i] = dyh.x;
+        rec_g[O_GQ + 3 * 6 + i] = dpt.x;
+        V3 dvl = v3(0, 0, 0), otail = v3(0, 0, 0);
+#pragma unroll
+        for (int j = i + 1; j < 6; j++) {
+            const V3 doj = cross(zi, k.o[j] - k.o[i]);
+            const V3 dzj = cross(zi, k.z[j]);
+            dvl = dvl + qd[j] * (cross(doj, k.z[j]) + cross(k.o[j], dzj));
+            otail = otail + qd[j] * k.z[j];
+        }
+        const V3 dom = cross(zi, otail);
+        const V3 ds = dvl + cross(dom, tw) + cross(om, dtw);
+        rec_g[O_GQ + 4 * 6 + i] = dot(dyh, s) + dot(yh, ds);
+        rec_g[O_GV + i] = dot(yh, cj[i] + cross(zi, tw));
+#if defined(__HIP_DEVICE_COMPILE__)
+        // one Jacobian column at a time: left alone, the scheduler interleaves all six (each ~100 independent operations) and the
+        // 256-register builds spill ~60 values around this loop
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+    }
+}
+
 template <bool JAC>
 MPC_HD void task_lin(const Robot &rb, const InstParams &P, const double *q, const double *qd, double *rec)
 {
@@ -279,5 +345,31 @@ MPC_HD void task_errors(const InstParams &P, const Robot &rb, const double *pose
     out7[5] = Z;
     out7[6] = pose12[1];
 }
+
+// The same against a row of a surface table as well (mpcb_rollout_surf): cf[0..5] = a..f of the logged column replace P.coeffs.
+// Restated, not shared.
+template <class CF>
+MPC_HD void task_errors(const InstParams &P, const Robot &rb, const double *pose12, const double *vel6, double *out7, const double *y, CF cf)
+{
+    const double r00 = pose12[3], r01 = pose12[4], r02 = pose12[5], r10 = pose12[6], r11 = pose12[7], r12 = pose12[8],
+                 r20 = pose12[9], r21 = pose12[10], r22 = pose12[11];
+    const double tx = rb.t_ee[0], ty = rb.t_ee[1], tz = rb.t_ee[2];
+    const double twx = r00 * tx + r01 * ty + r02 * tz, twy = r10 * tx + r11 * ty + r12 * tz, twz = r20 * tx + r21 * ty + r22 * tz;
+    const double X = pose12[0] + twx, Y = pose12[1] + twy, Z = pose12[2] + twz;
+    const double dotw = vel6[3] * twx + vel6[4] * twy + vel6[5] * twz;
+    const double vty = r10 * (vel6[0] + dotw) + r11 * (vel6[1] + dotw) + r12 * (vel6[2] + dotw);
+    const double a = cf[0], b = cf[1], c = cf[2], d = cf[3], e = cf[4], f = cf[5];
+    const double nx = 2 * a * X + c * Y + d, ny = 2 * b * Y + c * X + e;
+    const double nn = sqrt(nx * nx + ny * ny + 1.0);
+    const double S = a * X * X + b * Y * Y + c * X * Y + d * X + e * Y + f;
+    out7[0] = (S - Z) - y[0];
+    out7[1] = y[1] - (nx / nn * r02 + ny / nn * r12 + (-1.0 / nn) * r22);
+    out7[2] = r01 - y[2];
+    out7[3] = y[3] - X;
+    out7[4] = y[4] - vty;
+    out7[5] = Z;
+    out7[6] = pose12[1];
+}
+
 
 }  // namespace mpcb

@@ -17,6 +17,8 @@ using RolloutTermFn = void (*)(Problem, Robot, const InstParams *, double *, siz
                                TermTab);
 using RolloutObsFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
                               ObsArg);
+using RolloutSurfFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
+                               const double *);
 // throughput engine (mpc_stream.h): the robot record in device memory, no pool; rollouts take (queue, chunk_steps, timeout_ticks)
 using StreamStepFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, StepIO, int);
 using StreamRolloutFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long);
@@ -28,6 +30,8 @@ using StreamRolloutTermFn = void (*)(Problem, const Robot *, const InstParams *,
                                      const double *, PlantPert, TermTab);
 using StreamRolloutObsFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
                                     const double *, PlantPert, ObsArg);
+using StreamRolloutSurfFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
+                                     const double *, PlantPert, const double *);
 
 // The kernel of the latency engine's template K<NWV, WPE = 1> for a launch geometry (mpcb_setup picks it; <2> and <1> are reached
 // through MPCB_WAVES_PER_SIM), as a pointer of type Fn.  The module holds its kernels in the order they are instantiated in, which is
@@ -38,7 +42,7 @@ using StreamRolloutObsFn = void (*)(Problem, const Robot *, const InstParams *, 
      : (waves_per_sim) == 2 ? static_cast<Fn>(K<2>)                                                                         \
                             : static_cast<Fn>(K<1>))
 
-// mpc_step*.hip / mpc_stream_step*.hip: mpcb_step, _warm, _sens, _sens_w, _term without and with the sensitivity pass, _dist
+// mpc_step*.hip / mpc_stream_step*.hip: mpcb_step, _warm, _sens, _sens_w, _term without and with the sensitivity pass, _dist, _surf
 StepFn step_kernel(int waves_per_sim, int wpe);
 StepFn step_warm_kernel(int waves_per_sim, int wpe);
 StepFn step_sens_kernel(int waves_per_sim, int wpe);
@@ -46,6 +50,7 @@ StepFn step_sensw_kernel(int waves_per_sim, int wpe);
 StepFn step_term_kernel(int waves_per_sim, int wpe);
 StepFn step_term_sens_kernel(int waves_per_sim, int wpe);
 StepFn step_dist_kernel(int waves_per_sim, int wpe);
+StepFn step_surf_kernel(int waves_per_sim, int wpe);
 StreamStepFn stream_step_kernel();
 StreamStepFn stream_step_warm_kernel();
 StreamStepFn stream_step_sens_kernel();
@@ -53,14 +58,17 @@ StreamStepFn stream_step_sensw_kernel();
 StreamStepFn stream_step_term_kernel();
 StreamStepFn stream_step_term_sens_kernel();
 StreamStepFn stream_step_dist_kernel();
-// mpc_rollout_*.hip / mpc_stream_rollout_*.hip: mpcb_rollout_ref, _pert, _term, _obs (the kernels of mpcb_rollout are mpc_kernel.hip's own)
+StreamStepFn stream_step_surf_kernel();
+// mpc_rollout_*.hip / mpc_stream_rollout_*.hip: mpcb_rollout_ref, _pert, _term, _obs, _surf (the kernels of mpcb_rollout are mpc_kernel.hip's own)
 RolloutRefFn rollout_ref_kernel(int waves_per_sim, int wpe);
 RolloutPertFn rollout_pert_kernel(int waves_per_sim, int wpe);
 RolloutTermFn rollout_term_kernel(int waves_per_sim, int wpe);
 RolloutObsFn rollout_obs_kernel(int waves_per_sim, int wpe);
+RolloutSurfFn rollout_surf_kernel(int waves_per_sim, int wpe);
 StreamRolloutRefFn stream_rollout_ref_kernel();
 StreamRolloutPertFn stream_rollout_pert_kernel();
 StreamRolloutTermFn stream_rollout_term_kernel();
 StreamRolloutObsFn stream_rollout_obs_kernel();
+StreamRolloutSurfFn stream_rollout_surf_kernel();
 
 }  // namespace mpcb

@@ -158,7 +158,7 @@ struct Outputs {
 // solver.get(0,'u') and the step's statistics out, batch-major.  x_pred / u_pred may be null (not written).  The members past
 // u_pred are not part of mpcb_step_io; an initialiser that stops at u_pred means "the packed references, unchanged", one that stops
 // at ref_changed "every simulation carries its solver memory", one that stops at warm "no sensitivities", one that stops at sens_valid "none to the weights",
-// one that stops at du0_dw "no terminal cost", one that stops at du0_dxe "no input disturbance".
+// one that stops at du0_dw "no terminal cost", one that stops at du0_dxe "no input disturbance", one that stops at dist "the packed surface".
 struct StepIO {
     const double *xhat;  // [batch][12]
     double *u0;          // [batch][6]
@@ -184,6 +184,8 @@ struct StepIO {
     double *du0_dxe = nullptr;      // [batch][6][12] d u0 / d x_e, or null (not written)
     // mpcb_step_dist: the input disturbance of the prediction model x+ = Ad x + Bd (u + d), read by the dist kernels only
     const double *dist = nullptr;   // [batch][6] d, rad/s
+    // mpcb_step_surf: the surface window, row k = a..f at stage k, read by the surf kernels only
+    const double *surf = nullptr;   // [batch][N][NSURF]
 };
 
 // How a simulation's solver memory enters a controller step (MPCB_WARM_*); any other value is WARM_CARRY.
@@ -267,6 +269,8 @@ MPC_HD ObsArg obs_arg_of(const ObsArg &a, int inst, int Nsim)
 {
     return ObsArg{a.gain + (size_t)inst * 12, a.d_hat + (size_t)inst * Nsim * 6};
 }
+// A row of a surface table (mpcb_step_surf, mpcb_rollout_surf): the quadric's coefficients a b c d e f, as InstParams::coeffs.
+constexpr int NSURF = 6;
 static_assert(ST_OBS >= ST_PROF + NPROF && ST_OBS + 12 <= STATE_DOUBLES, "the observer's slots lie past the profile counters, inside the state block");
 
 // One instance's workspace: five stage-major group arrays + persistent scalars.

@@ -389,6 +389,24 @@ SE_DEV double eff_u(DistArg<DIST> da, int j, double u)
     else return u;
 }
 
+// SURF (the kernels of mpcb_step_surf and mpcb_rollout_surf only, mpc_stream_step_surf.hip / mpc_stream_rollout_surf.hip): the surface is
+// scheduled and stage-varying.  A compile-time flag of the three passes that evaluate the task functions -- lin_pass, merit_pass and
+// log_state -- which read the six coefficients a..f of stage k from row k of the step's window of a surface table (task_lin's and
+// task_errors' overloads with coefficients) in place of InstParams::coeffs.  lane <-> stage: six vector loads per lane, issued past the
+// kinematics where the targets are.  The window's pointer travels as an argument -- an empty struct, no register, in every other
+// kernel.  The cost and residual passes read r, Y and the Jacobian from the stage records: nothing of them changes.
+template <int SURF>
+struct SurfArg {};
+template <>
+struct SurfArg<1> {
+    const double *p;
+};
+struct SurfRow {
+    const MPC_GLOBAL double *p;
+    SE_DEV double operator[](int i) const { return p[i]; }
+};
+SE_DEV SurfRow surf_row(SurfArg<1> sa, int k) { return SurfRow{(const MPC_GLOBAL double *)uni_ref(TaskRef{sa.p}).y + (size_t)k * NSURF}; }
+
 // Stationarity element of class CLS (0: u_j, 1: q_j, 2: v_j) -- mpc_core.h Engine::stat_cls with the records in LDS.
 // r1: G1 row of stage k, r2: [R..GV] of stage k, pk / pm: pi_k / pi_{k-1}.
 template <int CLS>
@@ -1887,8 +1905,9 @@ SE_DEV int ipm_solve(int qp_iter_max, int *iters_out, int *fast, double *nlp_pre
 // `slot` (SQP_RTI: 0 / 1, full SQP: -1): where the QP iterate -- the step to apply -- sits (rti_items); in SQP_RTI stage 0's x part of it,
 // x_hat - x_0 (lbx_0 = ubx_0: the sweeps' dx_0 is 0), is formed AND written here, the only pass that has the x_0 it refers to.
 // REF (the controller step's instantiation only): the task residuals are formed against the task reference `ref` (non-null, task_targets).
-template <bool REF = false>
-SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int slot = -1, TaskRef ref = TaskRef{nullptr})
+// SURF: stage k's task functions are those of row k of the surface window `sa`.
+template <bool REF = false, int SURF = 0>
+SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int slot = -1, TaskRef ref = TaskRef{nullptr}, SurfArg<SURF> sa = {})
 {
     if constexpr (REF) ref = uni_ref(ref);
     SSmem &sm = g_ssm;
@@ -1964,7 +1983,8 @@ SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int s
 #endif
         if (k < N) {
             double rl[10];                                             // r | Y; the Jacobian goes straight to the record
-            task_lin<true, decltype(r2), REF>(rb, P, xx, xx + 6, rl, r2);
+            if constexpr (SURF) task_lin<true, decltype(r2), REF>(rb, P, surf_row(sa, k), xx, xx + 6, rl, r2);
+            else task_lin<true, decltype(r2), REF>(rb, P, xx, xx + 6, rl, r2);
             if constexpr (REF) {
                 double t[NTASK];    // (loaded here, past the kinematics)
                 task_targets(ref, k, t);
@@ -1994,8 +2014,8 @@ SE_PASS void lin_pass(double alpha, bool do_update, bool sqp_mult = false, int s
 // L1 merit function at the trial point (X,U) + alpha (dX,dU) (the stage terms: mpc_nlp.h merit_stage / merit_x0, shared with
 // mpc_core.h merit_pass).  lane <-> stage, straight from HBM.  With `update_weights` the merit weights (G5 MW) are
 // first refreshed from the QP multipliers by Leineweber's rule.
-template <bool REF = false>
-SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskRef ref = TaskRef{nullptr})
+template <bool REF = false, int SURF = 0>
+SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskRef ref = TaskRef{nullptr}, SurfArg<SURF> sa = {})
 {
     if constexpr (REF) ref = uni_ref(ref);
     SSmem &sm = g_ssm;
@@ -2039,7 +2059,8 @@ SE_PASS double merit_pass(double alpha, bool update_weights, int sqp_iter, TaskR
         if (k < N) {
 #pragma unroll
             for (int i = 0; i < 6; i++) uu[i] = r1[O_U + i] + alpha * r1[O_QW + i];
-            task_lin<false, double *, REF>(rb, P, xx, xx + 6, rec, rec);
+            if constexpr (SURF) task_lin<false, double *, REF>(rb, P, surf_row(sa, k), xx, xx + 6, rec, rec);
+            else task_lin<false, double *, REF>(rb, P, xx, xx + 6, rec, rec);
             if constexpr (REF) {
                 double t[NTASK];
                 task_targets(ref, k, t);
@@ -2072,12 +2093,14 @@ SE_PASS void update_x0_weights(int sqp_iter)
 }
 
 // MERIT_BACKTRACKING (nlp::LS_REDUCTION, LS_ALPHA_MIN).  REF: against the task reference `ref`.
-template <bool REF = false>
-SE_DEV double line_search(int sqp_iter, TaskRef ref = TaskRef{nullptr})
+template <bool REF = false, int SURF = 0>
+SE_DEV double line_search(int sqp_iter, TaskRef ref = TaskRef{nullptr}, SurfArg<SURF> sa = {})
 {
     update_x0_weights(sqp_iter);
     const auto merit = [&](double a, bool upd) {
-        if constexpr (REF) return merit_pass<true>(a, upd, sqp_iter, ref);
+        if constexpr (REF && SURF) return merit_pass<true, SURF>(a, upd, sqp_iter, ref, sa);
+        else if constexpr (SURF != 0) return merit_pass<false, SURF>(a, upd, sqp_iter, TaskRef{nullptr}, sa);
+        else if constexpr (REF) return merit_pass<true>(a, upd, sqp_iter, ref);
         else return merit_pass(a, upd, sqp_iter);
     };
     const double m0 = unid(merit(0.0, true));
@@ -2106,8 +2129,10 @@ SE_DEV void log_flush(const Outputs &out, int inst, int T1, int c_lo, int c_hi)
 
 // REF (rollout<FT, true>): the task errors are measured against `yrow`, the reference schedule's row of this column
 struct NoSched {};
-template <bool REF = false>
-SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo, typename std::conditional<REF, const double *, NoSched>::type yrow = {})
+// SURF (with REF): and against row 0 of `sa`, the surface table's row of this column (uniform loads: the table is read-only in a launch)
+template <bool REF = false, int SURF = 0>
+SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo, typename std::conditional<REF, const double *, NoSched>::type yrow = {},
+                      SurfArg<SURF> sa = {})
 {
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
@@ -2117,7 +2142,8 @@ SE_PASS int log_state(const Outputs &out, int inst, int T1, int col, int log_lo,
 #pragma unroll
         for (int i = 0; i < 12; i++) z[i] = sm.xhat[i];
         plant_log(rb, z, sm.logv);
-        if constexpr (REF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow);
+        if constexpr (REF && SURF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow, surf_row(sa, 0));
+        else if constexpr (REF) task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36, yrow);
         else task_errors(sm.P, rb, sm.logv, sm.logv + 15, sm.logv + 36);
     }
     fence();
@@ -2321,13 +2347,21 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 // registers; d^_t goes into sm.logv[lv_dhat] (what eff_u reads, DIST_SHARED) and into row t of the log ob_.d_hat -- write-only here -- before
 // the solve.  Step 0 takes v^_0 = y_0, d^_0 = 0; across a launch boundary and a work-queue hand-off the twelve doubles travel in
 // w.state[ST_OBS], stored and loaded where ST_Z is.
-template <class FT, bool REF = false, bool PERT = false, bool TERM = false, bool OBS = false>
+// SURF (with REF and PERT, not with TERM or OBS; the kernel of mpcb_rollout_surf, mpc_stream_rollout_surf.hip): `ss_` [Nsim + NMAX][NSURF]
+// is this simulation's surface table.  Step t's window is ss_ + t * NSURF -- stage k < N reads row t + k -- and log column t measures
+// the task errors against row t.  Nothing of a window carries to the next step, launch or work item: the row index is the absolute
+// step number.
+template <class FT, bool REF = false, bool PERT = false, bool TERM = false, bool OBS = false, bool SURF = false>
 SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                     const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched_ = {},
                     typename std::conditional<PERT, PlantPert, NoSched>::type pert_ = {},
                     typename std::conditional<TERM, TermTab, NoSched>::type tt_ = {},
-                    typename std::conditional<OBS, ObsArg, NoSched>::type ob_ = {})
+                    typename std::conditional<OBS, ObsArg, NoSched>::type ob_ = {},
+                    typename std::conditional<SURF, const double *, NoSched>::type ss_ = {})
 {
+    static_assert(!SURF || (REF && PERT && !TERM && !OBS), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
+    const double *ssched = nullptr;
+    if constexpr (SURF) ssched = uni_ref(TaskRef{ss_}).y;
     static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
     static_assert(!TERM || (REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
     static_assert(!OBS || (REF && PERT && !TERM), "the rollout with an observer runs the perturbed rollout's step, without a terminal cost");
@@ -2350,7 +2384,8 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if (lane < NX) sm.xhat[lane] = lane < 6 ? P.q0[lane] : P.qdot0[lane - 6];
         if (lane < NU) sm.u0[lane] = P.qdot0[lane];                   // u[:,0] = qdot_0 (simulator.py:81)
         initial_guess<FT>(pb, N);
-        if constexpr (REF) log_lo = uni(log_state<true>(out, inst, T1, 0, log_lo, sched));
+        if constexpr (REF && SURF) log_lo = uni(log_state<true, 1>(out, inst, T1, 0, log_lo, sched, SurfArg<1>{ssched}));
+        else if constexpr (REF) log_lo = uni(log_state<true>(out, inst, T1, 0, log_lo, sched));
         else log_lo = uni(log_state(out, inst, T1, 0, log_lo));
     } else {
         if (lane < NX) sm.xhat[lane] = w.state[ST_Z + lane];
@@ -2409,6 +2444,11 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
                 s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
                                  [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false, NoHook{},
                                  TermArg<0>{}, DistArg<DIST_SHARED>{});
+            else if constexpr (SURF) {
+                const SurfArg<1> sa{ssched + (size_t)i * NSURF};
+                s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true, 1>(alpha, do_update, sqp_mult, slot, ref, sa); },
+                                 [&](int sqp_iter) { return line_search<true, 1>(sqp_iter, ref, sa); }, nullptr, false);
+            }
             else
             s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
                              [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false);
@@ -2452,7 +2492,8 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         fence();
         if (lane < NX) sm.xhat[lane] = sm.logv[24 + lane];
         fence();
-        if constexpr (REF) log_lo = uni(log_state<true>(out, inst, T1, i + 1, log_lo, sched + (size_t)(i + 1) * NTASK));
+        if constexpr (REF && SURF) log_lo = uni(log_state<true, 1>(out, inst, T1, i + 1, log_lo, sched + (size_t)(i + 1) * NTASK, SurfArg<1>{ssched + (size_t)(i + 1) * NSURF}));
+        else if constexpr (REF) log_lo = uni(log_state<true>(out, inst, T1, i + 1, log_lo, sched + (size_t)(i + 1) * NTASK));
         else log_lo = uni(log_state(out, inst, T1, i + 1, log_lo));
         if constexpr (PERT) {
             // the feedback state of step i + 1, when this launch / work item runs it (no row Nsim exists; the next one forms its own)
@@ -2717,12 +2758,15 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
 // TERM (the kernels of mpcb_step_term, SQP_RTI): io.term holds this simulation's terminal cost -- on a ragged batch it acts at the
 // simulation's own horizon end -- and with SENS the sensitivity of u0 to its reference leaves through io.du0_dxe.  Not with SENSW.
 // DIST (the kernel of mpcb_step_dist, SQP_RTI): io.dist holds this simulation's input disturbance (DistArg).  Not with SENS, SENSW, TERM.
-template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false, bool TERM = false, bool DIST = false>
+// SURF (the kernel of mpcb_step_surf): io.surf holds this simulation's surface window, row k = stage k's a..f, rows strided by the
+// batch's longest horizon as the reference's are (SurfArg).  Not with SENS, SENSW, TERM, DIST.
+template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false, bool TERM = false, bool DIST = false, bool SURF = false>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
     static_assert(!(TERM && SENSW), "the weight sensitivity is not offered with a terminal cost");
     static_assert(!(DIST && (TERM || SENS || SENSW)), "the input disturbance is not offered with sensitivities or a terminal cost");
+    static_assert(!(SURF && (TERM || SENS || SENSW || DIST)), "the scheduled surface is not offered with sensitivities, a terminal cost or an input disturbance");
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
     const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), NMAX = pb.N;
@@ -2751,11 +2795,23 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
     if (io.ref_changed) c.lin_valid = false;
     const TaskRef ref{io.yref ? io.yref + (size_t)inst * NMAX * NTASK : nullptr};
     // (without a reference the passes of the packed g_ref: the rollout's)
+    const SurfArg<SURF ? 1 : 0> sa = [&] {
+        if constexpr (SURF) return SurfArg<1>{io.surf + (size_t)inst * NMAX * NSURF};
+        else return SurfArg<0>{};
+    }();
     const auto lin = [&](double alpha, bool do_update, bool sqp_mult, int slot) {
+        if constexpr (SURF) {
+            if (ref.y) lin_pass<true, 1>(alpha, do_update, sqp_mult, slot, ref, sa);
+            else lin_pass<false, 1>(alpha, do_update, sqp_mult, slot, TaskRef{nullptr}, sa);
+        } else {
         if (ref.y) lin_pass<true>(alpha, do_update, sqp_mult, slot, ref);
         else lin_pass(alpha, do_update, sqp_mult, slot);
+        }
     };
-    const auto search = [&](int sqp_iter) { return ref.y ? line_search<true>(sqp_iter, ref) : line_search(sqp_iter); };
+    const auto search = [&](int sqp_iter) {
+        if constexpr (SURF) return ref.y ? line_search<true, 1>(sqp_iter, ref, sa) : line_search<false, 1>(sqp_iter, TaskRef{nullptr}, sa);
+        else return ref.y ? line_search<true>(sqp_iter, ref) : line_search(sqp_iter);
+    };
     if (lane < NX) sm.xhat[lane] = io.xhat[(size_t)inst * NX + lane];
     fence();
     const double t0 = wclock();

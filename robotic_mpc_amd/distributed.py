@@ -222,9 +222,9 @@ def complete_runner_output(local: Dict[str, object], cfgs: Sequence[Dict]) -> Di
         out["plant_time"] = np.zeros(np.shape(to_host(local["solver_time"])))
     if "errors" in missing:
         pose, vel = to_host(local["ee_pose"]), to_host(local["ee_vel"])
-        from . import reference
+        from . import reference, surface
 
-        out["errors"] = np.stack([analysis.errors_rows(analysis.compute_errors(pose[i], vel[i], c["coeffs"], c["t_ee"], c["px_ref"],
+        out["errors"] = np.stack([analysis.errors_rows(analysis.compute_errors(pose[i], vel[i], surface.error_coeffs(c), c["t_ee"], c["px_ref"],
                                                                                c["vy_ref"], yref=reference.log_rows(c)))
                                   for i, c in enumerate(cfgs)]) \
             if len(cfgs) else np.zeros((0, 7, pose.shape[-1]))

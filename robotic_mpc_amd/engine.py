@@ -94,7 +94,8 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_run", "mpcb_setup_controller", "mpcb_step", "mpcb_setup_controller_on", "mpcb_controller_engine_for",
             "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
             "mpcb_step_dist",
-            "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term", "mpcb_rollout_obs")
+            "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term", "mpcb_rollout_obs",
+            "mpcb_step_surf", "mpcb_rollout_surf")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -155,6 +156,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_step_term.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, C.POINTER(MpcbStepSensOut), _dp, C.c_int,
                                    _dp, C.c_void_p]
     lib.mpcb_step_dist.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_void_p]
+    lib.mpcb_step_surf.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_void_p]
+    lib.mpcb_rollout_surf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -275,7 +278,8 @@ class MpcBatchEngine:
             setattr(r, name, C.cast(C.c_void_p(ptr), _dp if ty == "f8" else _ip))
         return r
 
-    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None, term=None, obs=None):
+    def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None, term=None, obs=None,
+                surf=None):
         """Asynchronous launch of closed-loop steps [step0, step1) into device buffers.  `yref`: the task reference schedules of
         the batch, a contiguous float64 device tensor [batch, Nsim + N, 5] (N the longest horizon; schedule_tensor) -- the same one
         for every launch of a run -- or None for the packed references (mpcb_rollout).  `pert`: the plant perturbation of the
@@ -288,7 +292,16 @@ class MpcBatchEngine:
         `obs`: the on-device disturbance observer of the batch (mpcb_rollout_obs; observer_tensors), a dict of contiguous float64
         device tensors "gain" [batch, 12] (l1 6 | l2 6; read) and "d_hat" [batch, Nsim, 6] (written: row t = the estimate step t
         used) -- the same ones for every launch of a run; it needs `yref` likewise, takes `pert` or the nominal plant, and is not
-        offered together with `term`."""
+        offered together with `term`.
+        `surf`: the surface schedules of the batch (mpcb_rollout_surf; surface_tensor), a contiguous float64 device tensor
+        [batch, Nsim + N, 6] (row r: a..f at time r dt) -- the same one for every launch of a run; it needs `yref` likewise, takes
+        `pert` or the nominal plant, and is not offered together with `term` or `obs`."""
+        if surf is not None:
+            if term is not None:
+                raise ValueError("a surface schedule (surf) is not offered together with a terminal cost (term)")
+            if obs is not None:
+                raise ValueError("a surface schedule (surf) is not offered together with a disturbance observer (obs)")
+            return self._rollout_pert(bufs, step0, step1, yref, pert, stream, surf=surf)
         if obs is not None:
             if term is not None:
                 raise ValueError("a disturbance observer (obs) is not offered together with a terminal cost (term)")
@@ -314,10 +327,21 @@ class MpcBatchEngine:
         if tuple(yref.shape) != (pb.batch, pb.Nsim + pb.N, 5) or not yref.is_contiguous() or str(yref.dtype) != "torch.float64":
             raise ValueError(f"yref must be a contiguous float64 tensor [{pb.batch}, {pb.Nsim + pb.N}, 5], got {tuple(yref.shape)} {yref.dtype}")
 
-    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None, obs=None):
-        """rollout(pert=, term=, obs=): every shape is checked before the library is called."""
+    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None, obs=None, surf=None):
+        """rollout(pert=, term=, obs=, surf=): every shape is checked before the library is called."""
         pb = self._pb
         tp = {}
+        if surf is not None:
+            if yref is None:
+                raise ValueError("a rollout over a surface schedule needs yref: schedule_tensor(cfgs) supplies the packed rows when "
+                                 "there is no schedule")
+            shape = (pb.batch, pb.Nsim + pb.N, 6)
+            if not hasattr(surf, "data_ptr") or tuple(surf.shape) != shape or not surf.is_contiguous() \
+                    or str(surf.dtype) != "torch.float64" or not surf.is_cuda or surf.device.index != self.device:
+                raise ValueError(f"surf must be a contiguous float64 tensor {list(shape)} on cuda:{self.device}, got "
+                                 f"{tuple(getattr(surf, 'shape', ()))} {getattr(surf, 'dtype', type(surf).__name__)} "
+                                 f"{getattr(surf, 'device', '')}".rstrip())
+            pert = {} if pert is None else pert
         if obs is not None:
             oshapes = {"gain": (pb.batch, 12), "d_hat": (pb.batch, pb.Nsim, 6)}
             if not isinstance(obs, dict) or set(obs) != set(oshapes):
@@ -370,6 +394,10 @@ class MpcBatchEngine:
 
             stream = torch.cuda.current_stream(self.device).cuda_stream
         r = self._result_struct(bufs)
+        if surf is not None:
+            self._check(self.lib.mpcb_rollout_surf(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
+                                                   C.cast(C.c_void_p(surf.data_ptr()), _dp), C.c_void_p(stream)), "mpcb_rollout_surf")
+            return
         if obs is not None:
             self._check(self.lib.mpcb_rollout_obs(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
                                                   tp["gain"], tp["d_hat"], C.c_void_p(stream)), "mpcb_rollout_obs")
@@ -408,6 +436,17 @@ class MpcBatchEngine:
         return {"gain": torch.from_numpy(observer.stack(cfgs)).to(dev),
                 "d_hat": torch.zeros((len(cfgs), int(cfgs[0]["Nsim"]), 6), dtype=torch.float64, device=dev)}
 
+    def surface_tensor(self, cfgs: Sequence[Dict]):
+        """The surface schedules of a bucket (surface.stack) on this engine's device, [batch, Nsim + N, 6], or None when the
+        configurations carry none (a bucket is all or nothing: packing.bucket_key)."""
+        if not any(c.get("surface_schedule") is not None for c in cfgs):
+            return None
+        import torch
+
+        from . import surface
+
+        return torch.from_numpy(surface.stack(cfgs)).to(torch.device("cuda", self.device))
+
     def perturbation_tensors(self, cfgs: Sequence[Dict]):
         """The plant perturbations of a bucket (plant.stack) on this engine's device -- {"wcv", "u_dist", "x_noise"} -- or None when
         the configurations carry none (a bucket is all or nothing: packing.bucket_key)."""
@@ -429,13 +468,13 @@ class MpcBatchEngine:
 
     def schedule_tensor(self, cfgs: Sequence[Dict]):
         """The reference schedules of a bucket (reference.stack) on this engine's device, or None when the configurations carry
-        none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation, a terminal cost or a
-        disturbance observer: those rollouts always track a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
+        none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation, a terminal cost, a
+        disturbance observer or a surface schedule: those rollouts always track a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
         from . import reference
 
         if not any(c.get("reference_schedule") is not None for c in cfgs):
             if not any(c.get("plant_perturbation") is not None or c.get("terminal_cost") is not None
-                       or c.get("disturbance_observer") is not None for c in cfgs):
+                       or c.get("disturbance_observer") is not None or c.get("surface_schedule") is not None for c in cfgs):
                 return None
             import torch
 
@@ -585,6 +624,28 @@ class MpcBatchEngine:
         self._check(self.lib.mpcb_step_dist(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), dp,
                                             int(bool(dist_changed)), C.c_void_p(stream)), "mpcb_step_dist")
 
+    def step_surf(self, io, yref=None, ref_changed: bool = False, warm=None, reset: bool = False, surf=None,
+                  surf_changed: bool = False, stream: Optional[int] = None):
+        """mpcb_step_surf: step_warm() whose stage k evaluates the task functions on the quadric of row k of `surf`, a contiguous
+        float64 device tensor [batch, N, 6] (a..f per stage; N the longest horizon), or None: step_warm().  `surf_changed`: the
+        window differs from the previous step's, or was switched on or off (the step linearises again first)."""
+        if surf is not None:
+            pb = self._pb
+            if not hasattr(surf, "data_ptr") or tuple(surf.shape) != (pb.batch, pb.N, 6) or not surf.is_contiguous() \
+                    or str(surf.dtype) != "torch.float64" or not surf.is_cuda:
+                raise ValueError(f"surf must be a contiguous float64 device tensor [{pb.batch}, {pb.N}, 6], got "
+                                 f"{tuple(getattr(surf, 'shape', ()))} {getattr(surf, 'dtype', type(surf).__name__)}")
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._step_struct(io)
+        yp = C.cast(C.c_void_p(yref.data_ptr()), _dp) if yref is not None else None
+        wp = C.cast(C.c_void_p(warm.data_ptr()), _ip) if warm is not None else None
+        sp = C.cast(C.c_void_p(surf.data_ptr()), _dp) if surf is not None else None
+        self._check(self.lib.mpcb_step_surf(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
+                                            int(bool(surf_changed)), C.c_void_p(stream)), "mpcb_step_surf")
+
     def debug_task_lin(self, cfgs: Sequence[Dict], chain, x: np.ndarray) -> np.ndarray:
         """Diagnostic: the device linearisation at points x[i] = [q; qdot] with the parameters of cfgs[i];
         returns [n, 60] records laid out like a G2 stage record (r 0..4, dg/dq 24..53, dg5/dqdot 54..59)."""
@@ -610,10 +671,11 @@ class MpcBatchEngine:
         pert = self.perturbation_tensors(cfgs)
         term = self.terminal_tensors(cfgs)
         obs = self.observer_tensors(cfgs)
+        surf = self.surface_tensor(cfgs)
         chunk = step_chunk if step_chunk and step_chunk > 0 else pb.Nsim
         self.last_kernel_ms = []
         for s0 in range(0, pb.Nsim, chunk):
-            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert, term=term, obs=obs)
+            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert, term=term, obs=obs, surf=surf)
             self.sync()
             self.last_kernel_ms.append(self.kernel_ms())
         if obs is not None:
@@ -639,6 +701,8 @@ class MpcBatchEngine:
         if any(c.get("disturbance_observer") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no disturbance observer: run configurations with a disturbance_observer through run() / "
                              "run_device()")
+        if any(c.get("surface_schedule") is not None for c in cfgs):
+            raise ValueError("mpcb_run takes no surface schedule: run configurations with a surface_schedule through run() / run_device()")
         pb = make_problem(cfgs)
         params = packing.pack_batch(cfgs)
         robot = np.ascontiguousarray(chain.packed(cfgs[0]["t_ee"]), dtype=np.float64)

@@ -108,7 +108,7 @@ def load_archive(path: str) -> Dict[str, np.ndarray]:
             raise ValueError(f"{path}: unsupported format version {ver}")
         arch = {k: f[k] for k in f.files}
     if ver == 1:
-        from . import analysis, reference
+        from . import analysis, reference, surface
         from .config import resolve_config
 
         K = len(arch["names"])
@@ -117,7 +117,7 @@ def load_archive(path: str) -> Dict[str, np.ndarray]:
         for i in range(K):
             c = resolve_config(json.loads(str(arch["configs"][i])))
             n = int(arch["nsim"][i])
-            e = analysis.compute_errors(arch["ee_pose"][i][:, :n + 1], arch["ee_vel"][i][:, :n + 1], c["coeffs"], c["t_ee"],
+            e = analysis.compute_errors(arch["ee_pose"][i][:, :n + 1], arch["ee_vel"][i][:, :n + 1], surface.error_coeffs(c), c["t_ee"],
                                         c["px_ref"], c["vy_ref"], yref=reference.log_rows(c))
             err[i, :, :n + 1] = analysis.errors_rows(e)
         arch["errors"] = err

@@ -33,7 +33,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import analysis, config as cfgmod, packing, plant, reference, robots, terminal
+from . import analysis, config as cfgmod, packing, plant, reference, robots, surface, terminal
 
 
 def chain_for(cfg: Dict) -> robots.KinematicChain:
@@ -179,7 +179,7 @@ class Simulator:
         if getattr(self, "_errors_rows", None) is not None:
             return analysis.errors_dict(self._errors_rows)
         sm = self.simulation_model
-        return analysis.compute_errors(sm._ee_pose_log, sm._ee_velocity_log, self.resolved["coeffs"], self.translation,
+        return analysis.compute_errors(sm._ee_pose_log, sm._ee_velocity_log, surface.error_coeffs(self.resolved), self.translation,
                                        self.px_ref, self.vy_ref, yref=reference.log_rows(self.resolved))
 
     @cached_property
@@ -211,6 +211,9 @@ class Simulator:
         rows = reference.log_rows(self.resolved)
         if rows is not None:
             data["reference_schedule"] = rows      # [Nsim + 1, 5]: the targets in force at every logged column
+        srows = surface.log_rows(self.resolved)
+        if srows is not None:
+            data["surface_coeffs"] = np.ascontiguousarray(srows.T)   # [6, Nsim + 1]: a..f every logged column was measured against
         data.update(plant.realised(self.resolved))  # "input_disturbance" [Nsim, 6] / "measurement_noise" [Nsim, 12] when configured
         data.update(terminal.realised(self.resolved))  # "terminal_reference" [Nsim, 12] / "terminal_blocks" [6, 3] likewise
         if getattr(self, "_d_hat", None) is not None:
@@ -326,11 +329,12 @@ class _EngineRunner:
             pert = eng.perturbation_tensors(cfgs)   # ... and its plant perturbations, or None (likewise)
             term = eng.terminal_tensors(cfgs)       # ... and its terminal costs, or None (likewise)
             obs = eng.observer_tensors(cfgs)        # ... and its disturbance observers, or None (likewise)
-            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert, term=term, obs=obs)
+            surf = eng.surface_tensor(cfgs)         # ... and its surface schedules, or None (likewise)
+            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert, term=term, obs=obs, surf=surf)
             summary = eng.summary(bufs, stream=stream.cuda_stream)
             if obs is not None:
                 bufs["d_hat"] = obs["d_hat"]        # the estimates travel with the logs: gathered, checkpointed, get_data()["d_hat"]
-        return eng, stream, bufs, summary, (yref, pert, term, obs)
+        return eng, stream, bufs, summary, (yref, pert, term, obs, surf)
 
     def collect(self, ticket):
         eng, stream, bufs, summary, _yref = ticket

@@ -32,8 +32,13 @@ STREAM_ROLLOUT_TERM_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_str
 # on the engine built with its DIST flag (the estimate in the shared block), under budgets of their own below
 ROLLOUT_OBS_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_obs.hip")
 STREAM_ROLLOUT_OBS_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_obs.hip")
+# the kernels of the rollout over a scheduled, stage-varying surface (mpcb_rollout_surf; modules of their own): the perturbed rollout's
+# on the engine built with its SURF flag (the stage's coefficients loaded by the lane that linearises it), under budgets of their own
+ROLLOUT_SURF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_surf.hip")
+STREAM_ROLLOUT_SURF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_surf.hip")
 SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC, ROLLOUT_PERT_SRC, STREAM_ROLLOUT_PERT_SRC,
-           ROLLOUT_TERM_SRC, STREAM_ROLLOUT_TERM_SRC, ROLLOUT_OBS_SRC, STREAM_ROLLOUT_OBS_SRC)
+           ROLLOUT_TERM_SRC, STREAM_ROLLOUT_TERM_SRC, ROLLOUT_OBS_SRC, STREAM_ROLLOUT_OBS_SRC, ROLLOUT_SURF_SRC,
+           STREAM_ROLLOUT_SURF_SRC)
 
 
 def scan(asm_text):
@@ -100,6 +105,12 @@ BUDGET = {
     "21mpc_stream_obs_kernelId": 180,
     "DevExecILi8ELi1EELi0ELi2EE10nlp_directILb1ELb1E": 39, "DevExecILi4ELi2EELi0ELi2EE10nlp_directILb1ELb1E": 40,
     "DevExecILi4ELi1EELi0ELi2EE10nlp_directILb1ELb1E": 8,
+    # the rollout over a scheduled surface (recorded: 229 / 301 / 63 for the kernel bodies, 144 for the throughput engine's; its NLP
+    # pass, with the row's coefficients live across the Jacobian loop, 41 / 40 / 4 against the perturbed rollout's 33 / 36 / 2)
+    "23mpc_rollout_surf_kernelILi8ELi1E": 252, "23mpc_rollout_surf_kernelILi4ELi2E": 331, "23mpc_rollout_surf_kernelILi4ELi1E": 70,
+    "22mpc_stream_surf_kernelId": 158,
+    "DevExecILi8ELi1EELi0ELi0ELi1EE10nlp_directILb1ELb1E": 45, "DevExecILi4ELi2EELi0ELi0ELi1EE10nlp_directILb1ELb1E": 44,
+    "DevExecILi4ELi1EELi0ELi0ELi1EE10nlp_directILb1ELb1E": 8,
 }
 
 
