@@ -538,7 +538,35 @@ int mpcb_rollout_surf(mpcb_handle *h, int step0, int step1, const mpcb_result *o
                       const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
                       const double *surf_sched /* DEVICE [batch][Nsim + N][MPCB_NSURF] or NULL */, void *stream);
 
-/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term / mpcb_rollout_obs / mpcb_rollout_surf launch of this handle went through the throughput
+/* ---- rollouts with the shift warm start ---- */
+/* mpcb_rollout_surf in which every simulation chooses how its solver memory enters a step: `warm` is a DEVICE array [batch] of
+ * MPCB_WARM_CARRY | MPCB_WARM_SHIFT, the mode of simulation i, constant over the run (any value other than MPCB_WARM_SHIFT counts
+ * as carry, as in mpcb_step_warm; one uniform load per simulation and launch or work item).  It is the closed loop
+ *   u_t = u0 of mpcb_step_warm(xhat_t, window t of yref_sched, ref_changed = 1, warm[i] = (t >= 1 ? mode_i : MPCB_WARM_CARRY))
+ * over the plant of mpcb_rollout_pert (pert == NULL: the nominal plant); with a surface table, mpcb_step_surf with window t of
+ * surf_sched takes the place of mpcb_step_warm.  t is the absolute step number: the first step of a run starts from the initial
+ * guess and does not shift; the first step of a later launch and the first step of a later work-queue item do.  The windows of
+ * mpcb_rollout_ref, _pert and _surf slide one row per step, so stage k + 1 of step t - 1 and stage k of step t read the same rows
+ * of the tables: the shifted iterate is linearised where the previous step left the solution of those rows, the carried one a stage
+ * late.  Everything MPCB_WARM_SHIFT moves or keeps is as stated for mpcb_step_warm: the tail x_N <- Ad x_N + Bd u_{N-1} at each
+ * simulation's own horizon end on a ragged batch, zeros for what arrives at stage 0 from stage 1's state bounds, N = 1 legal.
+ * Nothing new carries between steps, launches or work-queue items: no workspace, LDS or mpcb_workspace_bytes change.
+ *
+ * warm == NULL is mpcb_rollout_surf exactly (the same kernels, the same bits); with surf_sched == NULL as well that is
+ * mpcb_rollout_pert.  MPCB_EINVAL: warm on a full-SQP problem (there the shift costs iterations in the start-up transient and the
+ * loops converge to the same point), with MPCB_PRECISION_FP32_RICCATI or without yref_sched (a run without a reference schedule
+ * passes the packed row on every row).  MPCB_ESTATE on a controller handle or before mpcb_setup; the step-range rules of
+ * mpcb_rollout.  Whichever engine mpcb_setup chose runs it, work queue and ragged horizons included; mpcb_queue_used and
+ * mpcb_last_kernel_ms apply, and after such a launch mpcb_kernel_info reports this rollout's kernel.  Not offered together with the
+ * terminal cost (mpcb_rollout_term) or the disturbance observer (mpcb_rollout_obs).  Device time against mpcb_rollout_pert, the
+ * share of the shift pass and the loop of mpcb_step_warm launches it replaces: profiles/rollout_shift_rate.txt; what the shift does
+ * to the closed loop: profiles/rollout_shift_closed_loop.txt. */
+int mpcb_rollout_warm(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
+                      const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
+                      const double *surf_sched /* DEVICE [batch][Nsim + N][MPCB_NSURF] or NULL */,
+                      const int *warm /* DEVICE [batch] of MPCB_WARM_CARRY | MPCB_WARM_SHIFT, or NULL */, void *stream);
+
+/* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term / mpcb_rollout_obs / mpcb_rollout_surf / mpcb_rollout_warm launch of this handle went through the throughput
  * engine's work queue, 0: it did not (< 0: error).  Host state only. */
 int mpcb_queue_used(mpcb_handle *h);
 

@@ -20,14 +20,15 @@ ARCH = "gfx950"
 # and the rollout kernels of each engine that track a task reference schedule (mpcb_rollout_ref; modules of their own too), and those
 # of the rollout over a perturbed plant (mpcb_rollout_pert; likewise) and of the rollout with a terminal cost (mpcb_rollout_term),
 # and the steps with an input disturbance in the prediction model (mpcb_step_dist), and the rollout kernels whose steps take that
-# disturbance from an on-device observer (mpcb_rollout_obs)
+# disturbance from an on-device observer (mpcb_rollout_obs), the steps and rollouts over a scheduled surface (mpcb_step_surf,
+# mpcb_rollout_surf), and the rollout kernels with the per-simulation shift warm start (mpcb_rollout_warm)
 SOURCES = ("mpc_kernel.hip", "mpc_step.hip", "mpc_stream_step.hip", "mpc_step_warm.hip", "mpc_stream_step_warm.hip",
            "mpc_step_sens.hip", "mpc_stream_step_sens.hip", "mpc_step_sensw.hip", "mpc_stream_step_sensw.hip",
            "mpc_step_term.hip", "mpc_stream_step_term.hip", "mpc_step_term_sens.hip", "mpc_stream_step_term_sens.hip",
            "mpc_rollout_ref.hip", "mpc_stream_rollout_ref.hip", "mpc_rollout_pert.hip", "mpc_stream_rollout_pert.hip",
            "mpc_rollout_term.hip", "mpc_stream_rollout_term.hip", "mpc_step_dist.hip", "mpc_stream_step_dist.hip",
            "mpc_rollout_obs.hip", "mpc_stream_rollout_obs.hip", "mpc_step_surf.hip", "mpc_stream_step_surf.hip",
-           "mpc_rollout_surf.hip", "mpc_stream_rollout_surf.hip")
+           "mpc_rollout_surf.hip", "mpc_stream_rollout_surf.hip", "mpc_rollout_shift.hip", "mpc_stream_rollout_shift.hip")
 
 
 def _stale(target: str) -> bool:

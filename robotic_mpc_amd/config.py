@@ -55,7 +55,13 @@ EXTENSION_DEFAULTS = {"translation_ee_t": (0.0, 0.0, 0.1), "urdf_path": None, "e
                       # a surface that moves or changes along the run (surface.py): None -- the constant surface_coeffs -- or a
                       # JSON-serialisable spec {"kind": "table" | "moving", ...}; SQP_RTI and fp64 only, not together with
                       # terminal_cost or disturbance_observer
-                      "surface_schedule": None}
+                      "surface_schedule": None,
+                      # how a simulation's solver memory enters a closed-loop step: "carry" -- as it was left -- or "shift" -- moved
+                      # one stage towards stage 0 first, from the run's second step on (MPCB_WARM_SHIFT, mpcb_rollout_warm); per
+                      # simulation, so a grid over it is one bucket; "shift": SQP_RTI and fp64 only, not together with
+                      # terminal_cost or disturbance_observer
+                      "warm_start": "carry"}
+WARM_STARTS = ("carry", "shift")
 # codes of the parameter record (include/mpcbatch.h [7]); RK4 = 0 keeps default records unchanged
 PLANT_INTEGRATORS = {"RK4": 0, "Euler": 1, "RK2": 2, "RK3": 3}
 
@@ -329,9 +335,21 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
         # (the number of rows of a table against this run's Nsim + N)
         surface.sample({"surface_schedule": surf, "Nsim": Nsim, "N": N, "dt": dt,
                         "coeffs": np.array([coeffs[k] for k in "abcdef"], dtype=np.float64)})
+    warm = cfg["warm_start"]
+    if not isinstance(warm, str) or warm not in WARM_STARTS:
+        raise ValueError(f"warm_start must be one of {WARM_STARTS}, got {warm!r}")
+    if warm == "shift":
+        if term is not None:
+            raise ValueError("warm_start='shift' is not offered together with a terminal_cost")
+        if obs is not None:
+            raise ValueError("warm_start='shift' is not offered together with a disturbance_observer")
+        if so["nlp_solver_type"] != "SQP_RTI":
+            raise ValueError("warm_start='shift' is offered with nlp_solver_type='SQP_RTI' only")
+        if cfg["riccati_precision"] == "fp32":
+            raise ValueError("warm_start='shift' is offered with riccati_precision='fp64' only")
     return {
         "reference_schedule": schedule, "plant_perturbation": perturbation, "terminal_cost": term, "disturbance_observer": obs,
-        "surface_schedule": surf,
+        "surface_schedule": surf, "warm_start": warm,
         "robot_name": cfg["robot_name"], "urdf_path": cfg["urdf_path"], "ee_frame": cfg["ee_frame"],
         "N": N, "Nsim": Nsim, "dt": dt,
         "solver_type": SOLVER_RTI if so["nlp_solver_type"] == "SQP_RTI" else SOLVER_SQP,

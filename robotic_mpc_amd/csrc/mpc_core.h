@@ -3418,7 +3418,7 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
     // it linearises at its start against its own window (the carried linearisation was formed against the previous one, and so was
     // the fast path's right-hand side, which the closing pass therefore does not form), its cost and residual norms are those of the
     // new iterate against that window, and log column t measures the task errors against schedule row t.  Everything else carries as
-    // without a schedule; there is no shift.
+    // without a schedule; there is no shift (but SHIFT, below).
     // PERT (with REF; the kernels of mpcb_rollout_pert, mpc_rollout_pert.hip): the built-in plant is not the model -- `pert` holds
     // this simulation's plant bandwidths, input disturbance and measurement noise (each may be null).  TRUE state and FEEDBACK state
     // part ways: sm.xhat is what the solve sees, z_t + x_noise[t]; the true z_t stays in sm.logv[24..35] from one plant step to the
@@ -3441,15 +3441,24 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
     // this simulation's surface table.  Step t's window is ssched + t * NSURF -- stage k reads row t + k -- and log column t measures
     // the task errors against row t, as the reference schedule's.  The step linearises again at its start (REF), so nothing of a
     // window carries; the row index is the absolute step number, in every launch.
+    // SHIFT (with REF and PERT, not with TERM or OBS; the kernels of mpcb_rollout_warm, mpc_rollout_shift.hip): `wmode` is this
+    // simulation's warm-start mode, constant over the run.  With WARM_SHIFT every step t >= 1 -- t the absolute step number: the
+    // first step of a later launch too, never step 0, which starts from the initial guess -- moves the carried solver memory one
+    // stage towards stage 0 first (shift_pass), exactly as control_step<WARM> does: stage k of step t and stage k + 1 of step
+    // t - 1 read the same rows of the tables.  Any other value carries.  The step linearises at its start anyway (REF), and
+    // nothing of the chunk pool is live between the log of step t - 1 and the first pass of step t (shift_group stages through
+    // it): a REF step forms no fast-path right-hand side ahead, every QP factorises afresh, and the log collects in Smem::logbuf.
     struct NoSched {};
-    template <bool REF = false, bool PERT = false, bool OBS = false>
+    template <bool REF = false, bool PERT = false, bool OBS = false, bool SHIFT = false>
     MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {},
                         typename std::conditional<PERT, PlantPert, NoSched>::type pert = {},
                         typename std::conditional<TERM == TERM_TABLE, TermTab, NoSched>::type tt = {},
                         typename std::conditional<OBS, ObsArg, NoSched>::type ob = {},
-                        typename std::conditional<SURF != 0, const double *, NoSched>::type ssched = {})
+                        typename std::conditional<SURF != 0, const double *, NoSched>::type ssched = {},
+                        typename std::conditional<SHIFT, int, NoSched>::type wmode = {})
     {
         static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
+        static_assert(!SHIFT || (REF && PERT && !TERM && !DIST), "the rollout with the shift warm start runs the perturbed rollout's step, without a terminal cost or an observer");
         static_assert(!SURF || (REF && PERT && !TERM && !DIST), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
         static_assert(!TERM || (TERM == TERM_TABLE && REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
         static_assert(OBS == (DIST == DIST_SHARED) && (!OBS || (REF && PERT)), "the rollout with an observer runs the perturbed rollout's step on the engine whose disturbance is in the shared block");
@@ -3516,6 +3525,9 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
             }
             if constexpr (TERM == TERM_TABLE) term.x = tt.x_ref + (size_t)i * NX;
             if constexpr (SURF) this->surf = ssched + (size_t)i * NSURF;
+            if constexpr (SHIFT) {
+                if (i >= 1 && ex.uni(wmode) == WARM_SHIFT) shift_pass();
+            }
             if constexpr (OBS) ex.par([&](int lane) {
                 // the estimate this step's model takes: into the shared block for eff_u, and row i of the log
                 if (lane < 6) {

@@ -150,7 +150,7 @@ __global__ void mpc_debug_task_lin_kernel(int n, Robot rb, const InstParams *__r
 // ------------------------------------------------------------------------------------ host
 // The variants of the controller step and the kinds of rollout; each is one kernel (family) per engine, see with_kernel below.
 enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS, STEP_DIST, STEP_SURF };
-enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM, ROLLOUT_OBS, ROLLOUT_SURF };
+enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM, ROLLOUT_OBS, ROLLOUT_SURF, ROLLOUT_SHIFT, ROLLOUT_SHIFT_SURF };
 
 struct mpcb_handle {
     int device = -1;
@@ -243,11 +243,13 @@ static int with_kernel(const mpcb_handle *h, RolloutKind kind, F &&f)
 {
     const int nw = h->waves_per_sim, wpe = h->wpe;
     if (h->engine == 1)
-        return kind == ROLLOUT_SURF ? f(stream_rollout_surf_kernel())
+        return kind == ROLLOUT_SHIFT || kind == ROLLOUT_SHIFT_SURF ? f(stream_rollout_shift_kernel(kind == ROLLOUT_SHIFT_SURF))
+             : kind == ROLLOUT_SURF ? f(stream_rollout_surf_kernel())
              : kind == ROLLOUT_OBS  ? f(stream_rollout_obs_kernel())
              : kind == ROLLOUT_TERM ? f(stream_rollout_term_kernel()) : kind == ROLLOUT_PERT ? f(stream_rollout_pert_kernel())
              : kind == ROLLOUT_REF  ? f(stream_rollout_ref_kernel())  : f(stream_rollout_kernel(h->pb.precision));
-    return kind == ROLLOUT_SURF ? f(rollout_surf_kernel(nw, wpe))
+    return kind == ROLLOUT_SHIFT || kind == ROLLOUT_SHIFT_SURF ? f(rollout_shift_kernel(nw, wpe, kind == ROLLOUT_SHIFT_SURF))
+         : kind == ROLLOUT_SURF ? f(rollout_surf_kernel(nw, wpe))
          : kind == ROLLOUT_OBS  ? f(rollout_obs_kernel(nw, wpe))
          : kind == ROLLOUT_TERM ? f(rollout_term_kernel(nw, wpe)) : kind == ROLLOUT_PERT ? f(rollout_pert_kernel(nw, wpe))
          : kind == ROLLOUT_REF  ? f(rollout_ref_kernel(nw, wpe))  : f(rollout_kernel(nw, wpe));
@@ -260,6 +262,7 @@ struct RolloutArgs {
     int *queue; int chunk_steps; long long timeout_ticks;   // throughput engine
     const double *yref_sched; PlantPert pert; TermTab term; ObsArg obs;  // ref / pert / term / obs
     const double *surf_sched;                                            // surf
+    const int *warm;                                                     // shift
 };
 
 // Every kernel starts (pb, robot record, params, ws_base, ws_stride).  Latency engine: the record by value, a workgroup of
@@ -307,6 +310,10 @@ static void launch(RolloutSurfFn k, const mpcb_handle *h, hipStream_t s, const R
 {
     latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.surf_sched);
 }
+static void launch(RolloutShiftFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.surf_sched, a.warm);
+}
 static void launch(StreamRolloutFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
 {
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks);
@@ -334,6 +341,11 @@ static void launch(StreamRolloutSurfFn k, const mpcb_handle *h, hipStream_t s, c
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.surf_sched);
 }
 
+static void launch(StreamRolloutShiftFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.surf_sched, a.warm);
+}
+
 // One launch of `variant`'s kernel on stream s, between the two events mpcb_last_kernel_ms reads.  Latency engine: the dynamic-LDS
 // ceiling is a process-wide attribute of the kernel, not of this handle, so it is raised to the largest pool any handle can ask
 // for, right before the launch.
@@ -356,7 +368,7 @@ static int timed_launch(mpcb_handle *h, V variant, hipStream_t s, const Args &ar
 
 static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
                        const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream,
-                       const double *surf_sched = nullptr);
+                       const double *surf_sched = nullptr, const int *warm = nullptr);
 
 extern "C" {
 
@@ -648,12 +660,21 @@ int mpcb_rollout_surf(mpcb_handle *h, int step0, int step1, const mpcb_result *o
     return rollout_any(h, step0, step1, o, yref_sched, pert_, nullptr, nullptr, nullptr, nullptr, stream, surf_sched);
 }
 
+// (warm == NULL: mpcb_rollout_surf, hence with surf_sched == NULL mpcb_rollout_pert; otherwise the kernels of the rollout with the shift
+// warm start, mpc_rollout_shift.hip / mpc_stream_rollout_shift.hip, built without or with the scheduled surface)
+int mpcb_rollout_warm(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                      const double *surf_sched, const int *warm, void *stream)
+{
+    return rollout_any(h, step0, step1, o, yref_sched, pert_, nullptr, nullptr, nullptr, nullptr, stream, surf_sched, warm);
+}
+
 }  // extern "C"
 
-// The one launch path of every rollout: at most one of term_blocks, obs_gain and surf_sched is given.
+// The one launch path of every rollout: at most one of term_blocks, obs_gain and surf_sched is given; warm goes with neither
+// term_blocks nor obs_gain.
 static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
                        const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream,
-                       const double *surf_sched)
+                       const double *surf_sched, const int *warm)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
@@ -686,6 +707,12 @@ static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *
         return fail(h, MPCB_EINVAL, "mpcb_rollout_surf: a surface schedule is offered with SQP_RTI only");
     if (surf_sched && !yref_sched)
         return fail(h, MPCB_EINVAL, "mpcb_rollout_surf: a rollout over a scheduled surface needs a reference schedule (the packed rows when there is none)");
+    if (warm && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_warm: the shift warm start is offered in fp64 only (no fp32 Riccati leg)");
+    if (warm && h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_warm: the shift warm start is offered with SQP_RTI only");
+    if (warm && !yref_sched)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_warm: a rollout with the shift warm start needs a reference schedule (the packed rows when there is none)");
     if (!o) return fail(h, MPCB_EINVAL, "result pointer is NULL");
     if (step0 != h->next_step && step0 != 0)
         return fail(h, MPCB_ESTATE, "step0 must continue the previous rollout (or be 0 to restart)");
@@ -695,13 +722,14 @@ static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *
         return fail(h, MPCB_EINVAL, "every result array must be provided");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const RolloutKind kind = surf_sched ? ROLLOUT_SURF : obs_gain ? ROLLOUT_OBS : term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
+    const RolloutKind kind = warm ? (surf_sched ? ROLLOUT_SHIFT_SURF : ROLLOUT_SHIFT) : surf_sched ? ROLLOUT_SURF : obs_gain ? ROLLOUT_OBS : term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
     RolloutArgs args{};
     args.yref_sched = yref_sched;
     if (pert_) args.pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
     args.term = TermTab{term_blocks, term_xref};
     args.obs = ObsArg{obs_gain, d_hat};
     args.surf_sched = surf_sched;
+    args.warm = warm;
     std::memcpy(&args.out, o, sizeof args.out);
     args.step0 = step0;
     args.step1 = step1;

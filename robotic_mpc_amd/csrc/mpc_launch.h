@@ -19,6 +19,8 @@ using RolloutObsFn = void (*)(Problem, Robot, const InstParams *, double *, size
                               ObsArg);
 using RolloutSurfFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
                                const double *);
+using RolloutShiftFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
+                                const double *, const int *);
 // throughput engine (mpc_stream.h): the robot record in device memory, no pool; rollouts take (queue, chunk_steps, timeout_ticks)
 using StreamStepFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, StepIO, int);
 using StreamRolloutFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long);
@@ -32,6 +34,8 @@ using StreamRolloutObsFn = void (*)(Problem, const Robot *, const InstParams *, 
                                     const double *, PlantPert, ObsArg);
 using StreamRolloutSurfFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
                                      const double *, PlantPert, const double *);
+using StreamRolloutShiftFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
+                                      const double *, PlantPert, const double *, const int *);
 
 // The kernel of the latency engine's template K<NWV, WPE = 1> for a launch geometry (mpcb_setup picks it; <2> and <1> are reached
 // through MPCB_WAVES_PER_SIM), as a pointer of type Fn.  The module holds its kernels in the order they are instantiated in, which is
@@ -70,5 +74,8 @@ StreamRolloutPertFn stream_rollout_pert_kernel();
 StreamRolloutTermFn stream_rollout_term_kernel();
 StreamRolloutObsFn stream_rollout_obs_kernel();
 StreamRolloutSurfFn stream_rollout_surf_kernel();
+// mpc_rollout_shift.hip / mpc_stream_rollout_shift.hip: mpcb_rollout_warm, without (`surf` false) and with a surface table
+RolloutShiftFn rollout_shift_kernel(int waves_per_sim, int wpe, bool surf);
+StreamRolloutShiftFn stream_rollout_shift_kernel(bool surf);
 
 }  // namespace mpcb

@@ -2328,7 +2328,7 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 // this simulation (NMAX the longest horizon of the batch; this simulation reads rows [t, t + N) at step t, and row t for log column
 // t).  Step i is control_step against the window sched + i * NTASK with ref_changed set, followed by the plant step: it linearises at
 // its start against its own window, and forms its own cost and residual norms against it -- the next step's first pass runs against
-// the next window, so nothing is deferred.  Everything else carries as without a schedule; there is no shift.
+// the next window, so nothing is deferred.  Everything else carries as without a schedule; there is no shift (but SHIFT, below).
 // PERT (with REF; the kernel of mpcb_rollout_pert, mpc_stream_rollout_pert.hip): the built-in plant is not the model -- `pert_` holds this
 // simulation's plant bandwidths, input disturbance and measurement noise (each may be null).  sm.xhat is the FEEDBACK state of the
 // solve, z_t + x_noise[t]; the TRUE z_t stays in sm.logv[24..35] from one plant step to the next (no pass of the step touches those),
@@ -2351,14 +2351,24 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 // is this simulation's surface table.  Step t's window is ss_ + t * NSURF -- stage k < N reads row t + k -- and log column t measures
 // the task errors against row t.  Nothing of a window carries to the next step, launch or work item: the row index is the absolute
 // step number.
-template <class FT, bool REF = false, bool PERT = false, bool TERM = false, bool OBS = false, bool SURF = false>
+// SHIFT (with REF and PERT, not with TERM or OBS; the kernel of mpcb_rollout_warm, mpc_stream_rollout_shift.hip): `wm_` is this
+// simulation's warm-start mode, constant over the run.  With WARM_SHIFT every step t >= 1 -- t the absolute step number: the first
+// step of a later launch and of a later work item too, never step 0, which starts from the initial guess -- moves the carried solver
+// memory one stage towards stage 0 of the simulation's own horizon first (shift_pass<false>, as control_step<WARM> does).  Any other
+// value carries.  The step linearises at its start anyway (REF); mpc_step leaves no store of the records in flight, the iterate's slot
+// index (Carry::cur, ST_CUR) and the queue hand-off are what they were: shift_pass moves both homes of the iterate.
+template <bool SQP, int DIST = 0>
+SE_PASS void shift_pass(int N, DistArg<DIST> da = {});   // (defined below, with the controller step)
+template <class FT, bool REF = false, bool PERT = false, bool TERM = false, bool OBS = false, bool SURF = false, bool SHIFT = false>
 SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                     const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched_ = {},
                     typename std::conditional<PERT, PlantPert, NoSched>::type pert_ = {},
                     typename std::conditional<TERM, TermTab, NoSched>::type tt_ = {},
                     typename std::conditional<OBS, ObsArg, NoSched>::type ob_ = {},
-                    typename std::conditional<SURF, const double *, NoSched>::type ss_ = {})
+                    typename std::conditional<SURF, const double *, NoSched>::type ss_ = {},
+                    typename std::conditional<SHIFT, int, NoSched>::type wm_ = {})
 {
+    static_assert(!SHIFT || (REF && PERT && !TERM && !OBS), "the rollout with the shift warm start runs the perturbed rollout's step, without a terminal cost or an observer");
     static_assert(!SURF || (REF && PERT && !TERM && !OBS), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
     const double *ssched = nullptr;
     if constexpr (SURF) ssched = uni_ref(TaskRef{ss_}).y;
@@ -2426,6 +2436,9 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if constexpr (REF) {
             const TaskRef ref{sched + (size_t)i * NTASK};
             c.lin_valid = false;
+            if constexpr (SHIFT) {
+                if (i >= 1 && uni(wm_) == WARM_SHIFT) shift_pass<false, 0>(N, DistArg<0>{});
+            }
             if constexpr (OBS) {
                 // the estimate this step's model takes: into LDS for eff_u, and row i of the log
                 fence();
@@ -2523,8 +2536,8 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
 // before -- no wait between blocks.  The passes that follow fetch these records through the ring: stores drained first.
 constexpr int SH_R = 12;
 // DIST: the tail is propagated with the effective input, x_N <- Ad x_N + Bd (u_{N-1} + d), this step's disturbance.
-template <bool SQP, int DIST = 0>
-SE_PASS void shift_pass(int N, DistArg<DIST> da = {})
+template <bool SQP, int DIST>
+SE_PASS void shift_pass(int N, DistArg<DIST> da)
 {
     SSmem &sm = g_ssm;
     const SWs w = sm.w;

@@ -74,6 +74,13 @@ CONTROLLER_ENGINES = {"auto": -1, "latency": 0, "stream": 1}
 WARM_CARRY, WARM_RESET, WARM_SHIFT = 0, 1, 2
 
 
+def warm_modes(cfgs: Sequence[Dict]) -> Optional[np.ndarray]:
+    """The warm-start modes of a bucket as mpcb_rollout_warm takes them, int32 [batch] of WARM_CARRY / WARM_SHIFT (config key
+    warm_start), or None when every simulation carries."""
+    modes = np.array([WARM_SHIFT if c.get("warm_start", "carry") == "shift" else WARM_CARRY for c in cfgs], dtype=np.int32)
+    return modes if (modes == WARM_SHIFT).any() else None
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -95,7 +102,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
             "mpcb_step_dist",
             "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term", "mpcb_rollout_obs",
-            "mpcb_step_surf", "mpcb_rollout_surf")
+            "mpcb_step_surf", "mpcb_rollout_surf", "mpcb_rollout_warm")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -158,6 +165,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_step_dist.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_void_p]
     lib.mpcb_step_surf.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_void_p]
     lib.mpcb_rollout_surf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, C.c_void_p]
+    lib.mpcb_rollout_warm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, _ip,
+                                      C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -279,7 +288,7 @@ class MpcBatchEngine:
         return r
 
     def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None, term=None, obs=None,
-                surf=None):
+                surf=None, warm=None):
         """Asynchronous launch of closed-loop steps [step0, step1) into device buffers.  `yref`: the task reference schedules of
         the batch, a contiguous float64 device tensor [batch, Nsim + N, 5] (N the longest horizon; schedule_tensor) -- the same one
         for every launch of a run -- or None for the packed references (mpcb_rollout).  `pert`: the plant perturbation of the
@@ -295,7 +304,17 @@ class MpcBatchEngine:
         offered together with `term`.
         `surf`: the surface schedules of the batch (mpcb_rollout_surf; surface_tensor), a contiguous float64 device tensor
         [batch, Nsim + N, 6] (row r: a..f at time r dt) -- the same one for every launch of a run; it needs `yref` likewise, takes
-        `pert` or the nominal plant, and is not offered together with `term` or `obs`."""
+        `pert` or the nominal plant, and is not offered together with `term` or `obs`.
+        `warm`: the warm-start modes of the batch (mpcb_rollout_warm; warm_tensor), a contiguous int32 device tensor [batch] of
+        WARM_CARRY / WARM_SHIFT, constant over the run -- the same one for every launch; a simulation whose mode is WARM_SHIFT moves
+        its carried solver memory one stage towards stage 0 before every step but the run's first.  It needs `yref` likewise, takes
+        `pert` or the nominal plant and `surf` or the packed surface, and is not offered together with `term` or `obs`."""
+        if warm is not None:
+            if term is not None:
+                raise ValueError("the shift warm start (warm) is not offered together with a terminal cost (term)")
+            if obs is not None:
+                raise ValueError("the shift warm start (warm) is not offered together with a disturbance observer (obs)")
+            return self._rollout_pert(bufs, step0, step1, yref, pert, stream, surf=surf, warm=warm)
         if surf is not None:
             if term is not None:
                 raise ValueError("a surface schedule (surf) is not offered together with a terminal cost (term)")
@@ -327,10 +346,20 @@ class MpcBatchEngine:
         if tuple(yref.shape) != (pb.batch, pb.Nsim + pb.N, 5) or not yref.is_contiguous() or str(yref.dtype) != "torch.float64":
             raise ValueError(f"yref must be a contiguous float64 tensor [{pb.batch}, {pb.Nsim + pb.N}, 5], got {tuple(yref.shape)} {yref.dtype}")
 
-    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None, obs=None, surf=None):
-        """rollout(pert=, term=, obs=, surf=): every shape is checked before the library is called."""
+    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None, obs=None, surf=None, warm=None):
+        """rollout(pert=, term=, obs=, surf=, warm=): every shape is checked before the library is called."""
         pb = self._pb
         tp = {}
+        if warm is not None:
+            if yref is None:
+                raise ValueError("a rollout with the shift warm start needs yref: schedule_tensor(cfgs) supplies the packed rows when "
+                                 "there is no schedule")
+            if not hasattr(warm, "data_ptr") or tuple(warm.shape) != (pb.batch,) or not warm.is_contiguous() \
+                    or str(warm.dtype) != "torch.int32" or not warm.is_cuda or warm.device.index != self.device:
+                raise ValueError(f"warm must be a contiguous int32 tensor [{pb.batch}] on cuda:{self.device}, got "
+                                 f"{tuple(getattr(warm, 'shape', ()))} {getattr(warm, 'dtype', type(warm).__name__)} "
+                                 f"{getattr(warm, 'device', '')}".rstrip())
+            pert = {} if pert is None else pert
         if surf is not None:
             if yref is None:
                 raise ValueError("a rollout over a surface schedule needs yref: schedule_tensor(cfgs) supplies the packed rows when "
@@ -394,6 +423,11 @@ class MpcBatchEngine:
 
             stream = torch.cuda.current_stream(self.device).cuda_stream
         r = self._result_struct(bufs)
+        if warm is not None:
+            sp = C.cast(C.c_void_p(surf.data_ptr()), _dp) if surf is not None else None
+            self._check(self.lib.mpcb_rollout_warm(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
+                                                   sp, C.cast(C.c_void_p(warm.data_ptr()), _ip), C.c_void_p(stream)), "mpcb_rollout_warm")
+            return
         if surf is not None:
             self._check(self.lib.mpcb_rollout_surf(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
                                                    C.cast(C.c_void_p(surf.data_ptr()), _dp), C.c_void_p(stream)), "mpcb_rollout_surf")
@@ -447,6 +481,16 @@ class MpcBatchEngine:
 
         return torch.from_numpy(surface.stack(cfgs)).to(torch.device("cuda", self.device))
 
+    def warm_tensor(self, cfgs: Sequence[Dict]):
+        """The warm-start modes of a bucket (config key warm_start) on this engine's device, int32 [batch] of WARM_CARRY /
+        WARM_SHIFT, or None when every simulation carries: that bucket takes the path it took without the key."""
+        modes = warm_modes(cfgs)
+        if modes is None:
+            return None
+        import torch
+
+        return torch.from_numpy(modes).to(torch.device("cuda", self.device))
+
     def perturbation_tensors(self, cfgs: Sequence[Dict]):
         """The plant perturbations of a bucket (plant.stack) on this engine's device -- {"wcv", "u_dist", "x_noise"} -- or None when
         the configurations carry none (a bucket is all or nothing: packing.bucket_key)."""
@@ -469,12 +513,13 @@ class MpcBatchEngine:
     def schedule_tensor(self, cfgs: Sequence[Dict]):
         """The reference schedules of a bucket (reference.stack) on this engine's device, or None when the configurations carry
         none (a bucket is all or nothing: packing.bucket_key) -- unless they carry a plant perturbation, a terminal cost, a
-        disturbance observer or a surface schedule: those rollouts always track a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
+        disturbance observer, a surface schedule or the shift warm start: those rollouts always track a schedule, the packed row [0, 1, 0, px_ref, vy_ref] on every row when there is no other."""
         from . import reference
 
         if not any(c.get("reference_schedule") is not None for c in cfgs):
             if not any(c.get("plant_perturbation") is not None or c.get("terminal_cost") is not None
-                       or c.get("disturbance_observer") is not None or c.get("surface_schedule") is not None for c in cfgs):
+                       or c.get("disturbance_observer") is not None or c.get("surface_schedule") is not None
+                       or c.get("warm_start", "carry") == "shift" for c in cfgs):
                 return None
             import torch
 
@@ -672,10 +717,11 @@ class MpcBatchEngine:
         term = self.terminal_tensors(cfgs)
         obs = self.observer_tensors(cfgs)
         surf = self.surface_tensor(cfgs)
+        warm = self.warm_tensor(cfgs)
         chunk = step_chunk if step_chunk and step_chunk > 0 else pb.Nsim
         self.last_kernel_ms = []
         for s0 in range(0, pb.Nsim, chunk):
-            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert, term=term, obs=obs, surf=surf)
+            self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), yref=yref, pert=pert, term=term, obs=obs, surf=surf, warm=warm)
             self.sync()
             self.last_kernel_ms.append(self.kernel_ms())
         if obs is not None:
@@ -701,6 +747,8 @@ class MpcBatchEngine:
         if any(c.get("disturbance_observer") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no disturbance observer: run configurations with a disturbance_observer through run() / "
                              "run_device()")
+        if any(c.get("warm_start", "carry") == "shift" for c in cfgs):
+            raise ValueError("mpcb_run takes no warm-start modes: run configurations with warm_start='shift' through run() / run_device()")
         if any(c.get("surface_schedule") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no surface schedule: run configurations with a surface_schedule through run() / run_device()")
         pb = make_problem(cfgs)

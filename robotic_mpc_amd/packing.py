@@ -61,7 +61,8 @@ def bucket_key(cfg: Dict, ragged: bool = False):
     over a perturbed plant (config key plant_perturbation: the kernels of mpcb_rollout_pert), with or without a schedule, and
     simulations with a terminal cost (config key terminal_cost: the kernels of mpcb_rollout_term), with or without either, and
     simulations with a disturbance observer (config key disturbance_observer: the kernels of mpcb_rollout_obs; any pole), and
-    simulations over a scheduled surface (config key surface_schedule: the kernels of mpcb_rollout_surf; any schedule)."""
+    simulations over a scheduled surface (config key surface_schedule: the kernels of mpcb_rollout_surf; any schedule).  The warm-start mode (config key warm_start)
+    is NOT part of the key: it is chosen per simulation inside one launch (mpcb_rollout_warm), so a grid over it stays one bucket."""
     return (cfg["robot_name"], cfg.get("urdf_path"), cfg.get("ee_frame"), tuple(np.asarray(cfg["t_ee"]).tolist()),
             None if ragged else cfg["N"], cfg["Nsim"], cfg["solver_type"], cfg["max_iter"], cfg["qp_iter_max"],
             bool(cfg["fixed_step"]), int(cfg.get("precision", 0)), cfg.get("reference_schedule") is not None) + \

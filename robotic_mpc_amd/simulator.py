@@ -330,11 +330,12 @@ class _EngineRunner:
             term = eng.terminal_tensors(cfgs)       # ... and its terminal costs, or None (likewise)
             obs = eng.observer_tensors(cfgs)        # ... and its disturbance observers, or None (likewise)
             surf = eng.surface_tensor(cfgs)         # ... and its surface schedules, or None (likewise)
-            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert, term=term, obs=obs, surf=surf)
+            warm = eng.warm_tensor(cfgs)            # ... and its warm-start modes, or None: every simulation carries (likewise)
+            eng.rollout(bufs, 0, pb.Nsim, yref=yref, stream=stream.cuda_stream, pert=pert, term=term, obs=obs, surf=surf, warm=warm)
             summary = eng.summary(bufs, stream=stream.cuda_stream)
             if obs is not None:
                 bufs["d_hat"] = obs["d_hat"]        # the estimates travel with the logs: gathered, checkpointed, get_data()["d_hat"]
-        return eng, stream, bufs, summary, (yref, pert, term, obs, surf)
+        return eng, stream, bufs, summary, (yref, pert, term, obs, surf, warm)
 
     def collect(self, ticket):
         eng, stream, bufs, summary, _yref = ticket

@@ -36,9 +36,13 @@ STREAM_ROLLOUT_OBS_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stre
 # on the engine built with its SURF flag (the stage's coefficients loaded by the lane that linearises it), under budgets of their own
 ROLLOUT_SURF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_surf.hip")
 STREAM_ROLLOUT_SURF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_surf.hip")
+# the kernels of the rollout with the shift warm start (mpcb_rollout_warm; modules of their own): the perturbed rollout's and the scheduled
+# surface's with Engine::shift_pass / se::shift_pass at the top of a step, under budgets of their own below
+ROLLOUT_SHIFT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_shift.hip")
+STREAM_ROLLOUT_SHIFT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_shift.hip")
 SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC, ROLLOUT_PERT_SRC, STREAM_ROLLOUT_PERT_SRC,
            ROLLOUT_TERM_SRC, STREAM_ROLLOUT_TERM_SRC, ROLLOUT_OBS_SRC, STREAM_ROLLOUT_OBS_SRC, ROLLOUT_SURF_SRC,
-           STREAM_ROLLOUT_SURF_SRC)
+           STREAM_ROLLOUT_SURF_SRC, ROLLOUT_SHIFT_SRC, STREAM_ROLLOUT_SHIFT_SRC)
 
 
 def scan(asm_text):
@@ -111,6 +115,12 @@ BUDGET = {
     "22mpc_stream_surf_kernelId": 158,
     "DevExecILi8ELi1EELi0ELi0ELi1EE10nlp_directILb1ELb1E": 45, "DevExecILi4ELi2EELi0ELi0ELi1EE10nlp_directILb1ELb1E": 44,
     "DevExecILi4ELi1EELi0ELi0ELi1EE10nlp_directILb1ELb1E": 8,
+    # the rollout with the shift warm start (recorded: 235 / 303 / 61 for the kernel bodies without a surface table against the perturbed
+    # rollout's 232 / 300 / 61, 232 / 304 / 63 with one against the scheduled surface's 229 / 301 / 63; 149 and 142 for the throughput
+    # engine's; the NLP passes are those two rollouts' own)
+    "24mpc_rollout_shift_kernelILi8ELi1E": 258, "24mpc_rollout_shift_kernelILi4ELi2E": 333, "24mpc_rollout_shift_kernelILi4ELi1E": 68,
+    "29mpc_rollout_shift_surf_kernelILi8ELi1E": 255, "29mpc_rollout_shift_surf_kernelILi4ELi2E": 334, "29mpc_rollout_shift_surf_kernelILi4ELi1E": 70,
+    "23mpc_stream_shift_kernelId": 164, "28mpc_stream_shift_surf_kernelId": 158,
 }
 
 
