@@ -566,6 +566,57 @@ int mpcb_rollout_warm(mpcb_handle *h, int step0, int step1, const mpcb_result *o
                       const double *surf_sched /* DEVICE [batch][Nsim + N][MPCB_NSURF] or NULL */,
                       const int *warm /* DEVICE [batch] of MPCB_WARM_CARRY | MPCB_WARM_SHIFT, or NULL */, void *stream);
 
+/* ---- terminal cost, input disturbance / observer, scheduled surface and shift in ONE step and ONE rollout ---- */
+/* The entries above each add one closed-loop capability and refuse the others.  These two run all four at once, opt-in; nothing above
+ * changes.  Both are SQP_RTI and fp64 only (MPCB_EINVAL otherwise), on whichever engine the handle was set up with, ragged horizons
+ * and the work queue included.
+ *
+ * One kernel per entry and engine, not one per subset.  Each of term, dist / obs, surf and warm may be NULL = that feature is absent
+ * for the whole batch; a simulation of a batch that does not use a feature brings NEUTRAL data for it:
+ *   terminal cost      zero blocks (x_e is then multiplied by zeros; any finite rows)
+ *   disturbance        d = 0 (step); observer gains l1 = l2 = 0 (rollout): d^ stays 0, and u + 0.0 is exact
+ *   surface            a window / table whose rows all equal the simulation's own packed a..f
+ *   warm start         MPCB_WARM_CARRY
+ * The HOST fills the neutral tables, the kernels take no branch on a null pointer: for a NULL argument these entries fill them in
+ * device memory the handle keeps for this purpose (allocated and filled at the first such call after a setup, once every argument has
+ * been validated -- that one call synchronises its stream -- sized by the tables it stands for, reused by later calls, freed by
+ * mpcb_destroy; the workspace and mpcb_workspace_bytes do not grow).  A caller who passes all tables allocates nothing here.
+ *
+ * mpcb_step_combined: one real-time iteration of the NLP in which stage k evaluates its task outputs on row k of `surf`
+ * (mpcb_step_surf), the model is x+ = Ad x + Bd (u + d), d = `dist`, with the qddot rows of that model (mpcb_step_dist), and
+ * l_N = 1/2 (x_N - x_e)' P (x_N - x_e) from `term` is added, not scaled by dt (mpcb_step_term).  With MPCB_WARM_SHIFT the carried
+ * memory moves one stage first and the tail is x_N <- Ad x_N + Bd (u_{N-1} + d), THIS step's d.  term_changed, dist_changed and
+ * surf_changed act as ref_changed does.  No sensitivities.  Array shapes as in the single-feature entries.  MPCB_ESTATE on a handle
+ * not set up as a controller.
+ *
+ * mpcb_rollout_combined: the closed loop over the plant of mpcb_rollout_pert in which step t -- t the absolute step number, in every
+ * launch and work-queue item -- is
+ *   mpcb_step_combined(xhat_t, window t of yref_sched, ref_changed = 1, warm = (t >= 1 ? mode_i : MPCB_WARM_CARRY),
+ *                      term = [blocks_i | x_ref[i][t]], dist = d^_t, surf = rows t .. t + N of surf_sched)
+ * with d^_t the estimate of the observer of mpcb_rollout_obs (d^_0 = 0), written to d_hat[i][t] BEFORE the shift, which uses it.
+ * Step 0 never shifts.  On a ragged batch the terminal cost sits on each simulation's own last stage.  Nothing new carries: d^
+ * crosses a launch in the slots mpcb_rollout_obs uses.  MPCB_ESTATE on a controller handle or before mpcb_setup; the step-range rules
+ * of mpcb_rollout; yref_sched is required (the packed rows when there is none).  After such a launch mpcb_kernel_info reports this
+ * rollout's kernel.  Device time against the single-feature rollouts: profiles/rollout_combined_rate.txt. */
+typedef struct {
+    const double *blocks;  /* DEVICE [batch][18]        pqq 6 | pqv 6 | pvv 6, as mpcb_rollout_term's term_blocks */
+    const double *x_ref;   /* DEVICE [batch][Nsim][12]  row t = x_e of step t                                      */
+} mpcb_term_table;
+typedef struct {
+    const double *gain;    /* DEVICE [batch][12]        l1[6] | l2[6], as mpcb_rollout_obs's obs_gain              */
+    double *d_hat;         /* DEVICE [batch][Nsim][6]   written: row t = the estimate step t used                  */
+} mpcb_observer;
+int mpcb_step_combined(mpcb_handle *h, const mpcb_step_io *io, const double *yref /* DEVICE [batch][N][MPCB_NREF] or NULL */,
+                       int ref_changed, const int *warm /* DEVICE [batch] of MPCB_WARM_* or NULL */, int reset,
+                       const double *term /* DEVICE [batch][30] or NULL */, int term_changed,
+                       const double *dist /* DEVICE [batch][6] or NULL */, int dist_changed,
+                       const double *surf /* DEVICE [batch][N][MPCB_NSURF] or NULL */, int surf_changed, void *stream);
+int mpcb_rollout_combined(mpcb_handle *h, int step0, int step1, const mpcb_result *out_dev,
+                          const double *yref_sched /* DEVICE [batch][Nsim + N][MPCB_NREF] */, const mpcb_plant_pert *pert /* or NULL */,
+                          const mpcb_term_table *term /* or NULL */, const mpcb_observer *obs /* or NULL */,
+                          const double *surf_sched /* DEVICE [batch][Nsim + N][MPCB_NSURF] or NULL */,
+                          const int *warm /* DEVICE [batch] of MPCB_WARM_CARRY | MPCB_WARM_SHIFT, or NULL */, void *stream);
+
 /* 1: the last mpcb_rollout / mpcb_rollout_ref / mpcb_rollout_pert / mpcb_rollout_term / mpcb_rollout_obs / mpcb_rollout_surf / mpcb_rollout_warm launch of this handle went through the throughput
  * engine's work queue, 0: it did not (< 0: error).  Host state only. */
 int mpcb_queue_used(mpcb_handle *h);

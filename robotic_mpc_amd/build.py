@@ -21,14 +21,17 @@ ARCH = "gfx950"
 # of the rollout over a perturbed plant (mpcb_rollout_pert; likewise) and of the rollout with a terminal cost (mpcb_rollout_term),
 # and the steps with an input disturbance in the prediction model (mpcb_step_dist), and the rollout kernels whose steps take that
 # disturbance from an on-device observer (mpcb_rollout_obs), the steps and rollouts over a scheduled surface (mpcb_step_surf,
-# mpcb_rollout_surf), and the rollout kernels with the per-simulation shift warm start (mpcb_rollout_warm)
+# mpcb_rollout_surf), and the rollout kernels with the per-simulation shift warm start (mpcb_rollout_warm), and the step and rollout
+# kernels in which terminal cost, disturbance / observer, scheduled surface and shift are live at once (mpcb_step_combined,
+# mpcb_rollout_combined)
 SOURCES = ("mpc_kernel.hip", "mpc_step.hip", "mpc_stream_step.hip", "mpc_step_warm.hip", "mpc_stream_step_warm.hip",
            "mpc_step_sens.hip", "mpc_stream_step_sens.hip", "mpc_step_sensw.hip", "mpc_stream_step_sensw.hip",
            "mpc_step_term.hip", "mpc_stream_step_term.hip", "mpc_step_term_sens.hip", "mpc_stream_step_term_sens.hip",
            "mpc_rollout_ref.hip", "mpc_stream_rollout_ref.hip", "mpc_rollout_pert.hip", "mpc_stream_rollout_pert.hip",
            "mpc_rollout_term.hip", "mpc_stream_rollout_term.hip", "mpc_step_dist.hip", "mpc_stream_step_dist.hip",
            "mpc_rollout_obs.hip", "mpc_stream_rollout_obs.hip", "mpc_step_surf.hip", "mpc_stream_step_surf.hip",
-           "mpc_rollout_surf.hip", "mpc_stream_rollout_surf.hip", "mpc_rollout_shift.hip", "mpc_stream_rollout_shift.hip")
+           "mpc_rollout_surf.hip", "mpc_stream_rollout_surf.hip", "mpc_rollout_shift.hip", "mpc_stream_rollout_shift.hip",
+           "mpc_step_combined.hip", "mpc_stream_step_combined.hip", "mpc_rollout_combined.hip", "mpc_stream_rollout_combined.hip")
 
 
 def _stale(target: str) -> bool:

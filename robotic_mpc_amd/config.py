@@ -60,7 +60,12 @@ EXTENSION_DEFAULTS = {"translation_ee_t": (0.0, 0.0, 0.1), "urdf_path": None, "e
                       # one stage towards stage 0 first, from the run's second step on (MPCB_WARM_SHIFT, mpcb_rollout_warm); per
                       # simulation, so a grid over it is one bucket; "shift": SQP_RTI and fp64 only, not together with
                       # terminal_cost or disturbance_observer
-                      "warm_start": "carry"}
+                      "warm_start": "carry",
+                      # opt-in: with True any subset of terminal_cost, disturbance_observer, surface_schedule and
+                      # warm_start="shift" may be configured together; the run then goes through the combined rollout
+                      # (mpcb_rollout_combined), one launch per bucket whatever subset each simulation uses.  SQP_RTI and fp64 only.
+                      # False: every "not offered together with" above stands
+                      "combine_features": False}
 WARM_STARTS = ("carry", "shift")
 # codes of the parameter record (include/mpcbatch.h [7]); RK4 = 0 keeps default records unchanged
 PLANT_INTEGRATORS = {"RK4": 0, "Euler": 1, "RK2": 2, "RK3": 3}
@@ -273,6 +278,15 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
     t_ee = np.asarray(cfg["translation_ee_t"], dtype=np.float64).reshape(-1)
     if t_ee.shape != (3,):
         raise ValueError("translation_ee_t must have 3 entries")
+    combine = cfg["combine_features"]
+    if not isinstance(combine, (bool, np.bool_)):
+        raise ValueError(f"combine_features must be True or False, got {combine!r}")
+    combine = bool(combine)
+    if combine:
+        if so["nlp_solver_type"] != "SQP_RTI":
+            raise ValueError("combine_features is offered with nlp_solver_type='SQP_RTI' only")
+        if cfg["riccati_precision"] == "fp32":
+            raise ValueError("combine_features is offered with riccati_precision='fp64' only")
     schedule = cfg["reference_schedule"]
     if schedule is not None:
         from . import reference
@@ -310,7 +324,7 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
     if obs is not None:
         from . import observer
 
-        if term is not None:
+        if term is not None and not combine:
             raise ValueError("a disturbance_observer is not offered together with a terminal_cost")
         if so["nlp_solver_type"] != "SQP_RTI":
             raise ValueError("a disturbance_observer is offered with nlp_solver_type='SQP_RTI' only")
@@ -322,9 +336,9 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
     if surf is not None:
         from . import surface
 
-        if term is not None:
+        if term is not None and not combine:
             raise ValueError("a surface_schedule is not offered together with a terminal_cost")
-        if obs is not None:
+        if obs is not None and not combine:
             raise ValueError("a surface_schedule is not offered together with a disturbance_observer")
         if so["nlp_solver_type"] != "SQP_RTI":
             raise ValueError("a surface_schedule is offered with nlp_solver_type='SQP_RTI' only")
@@ -339,9 +353,9 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
     if not isinstance(warm, str) or warm not in WARM_STARTS:
         raise ValueError(f"warm_start must be one of {WARM_STARTS}, got {warm!r}")
     if warm == "shift":
-        if term is not None:
+        if term is not None and not combine:
             raise ValueError("warm_start='shift' is not offered together with a terminal_cost")
-        if obs is not None:
+        if obs is not None and not combine:
             raise ValueError("warm_start='shift' is not offered together with a disturbance_observer")
         if so["nlp_solver_type"] != "SQP_RTI":
             raise ValueError("warm_start='shift' is offered with nlp_solver_type='SQP_RTI' only")
@@ -349,7 +363,7 @@ def resolve_config(config: Mapping[str, Any]) -> Dict[str, Any]:
             raise ValueError("warm_start='shift' is offered with riccati_precision='fp64' only")
     return {
         "reference_schedule": schedule, "plant_perturbation": perturbation, "terminal_cost": term, "disturbance_observer": obs,
-        "surface_schedule": surf, "warm_start": warm,
+        "surface_schedule": surf, "warm_start": warm, "combine_features": combine,
         "robot_name": cfg["robot_name"], "urdf_path": cfg["urdf_path"], "ee_frame": cfg["ee_frame"],
         "N": N, "Nsim": Nsim, "dt": dt,
         "solver_type": SOLVER_RTI if so["nlp_solver_type"] == "SQP_RTI" else SOLVER_SQP,

@@ -106,8 +106,14 @@ class BatchController:
     _surf_on = False
     _surf_changed = False
     _surf_stream = None
+    # BatchController(combined=True): the three above and the shift may be in force together (mpcb_step_combined)
+    _combined = False
 
-    def __init__(self, configs: Sequence[Mapping], device: int = 0, engine: str = "latency"):
+    def __init__(self, configs: Sequence[Mapping], device: int = 0, engine: str = "latency", combined: bool = False):
+        """``combined=True`` (opt-in, SQP_RTI only): ``set_terminal_cost``, ``set_input_disturbance`` / ``step(dist=)``,
+        ``set_surface`` / ``step(surface=)`` and ``step(shift=)`` may all be in force together; every step then runs the combined
+        controller step (include/mpcbatch.h, mpcb_step_combined), with neutral data for whatever is switched off, and
+        ``sens`` / ``sens_w`` are refused.  Without it nothing changes: each of the three refuses the other two."""
         if engine not in CONTROLLER_ENGINES:
             raise ValueError(f"engine must be one of {sorted(CONTROLLER_ENGINES)}, got {engine!r}")
         if len(configs) == 0:
@@ -130,6 +136,9 @@ class BatchController:
             raise ValueError("riccati_precision='fp32' is refused by the controller step on every engine: it is fp64 only")
         from .simulator import chain_for
 
+        if combined and cfgs[0]["solver_type"] != packing.SOLVER_RTI:
+            raise ValueError("BatchController(combined=True) needs SQP_RTI configurations: the combined step is not offered with full SQP")
+        self._combined = bool(combined)
         chain = chain_for(cfgs[0])
         self.configs = cfgs
         self.horizons = horizons
@@ -405,9 +414,9 @@ class BatchController:
             return
         if x_ref is None:
             raise ValueError("set_terminal_cost needs the terminal reference x_ref with P")
-        if self._surf_on:
+        if self._surf_on and not self._combined:
             raise ValueError("a terminal cost is not offered while a surface window is in force (set_surface(None) switches it off)")
-        if self._dist_on:
+        if self._dist_on and not self._combined:
             raise ValueError("a terminal cost is not offered while an input disturbance is in force (set_input_disturbance(None) "
                              "switches it off)")
         blocks, xe = self._check_terminal(P, x_ref)
@@ -445,10 +454,10 @@ class BatchController:
         B = self.batch
         if self.configs[0]["solver_type"] != packing.SOLVER_RTI:
             raise ValueError("set_input_disturbance needs an SQP_RTI controller: the input disturbance is not offered with full SQP")
-        if self._term_on:
+        if self._term_on and not self._combined:
             raise ValueError("an input disturbance is not offered while a terminal cost is in force (set_terminal_cost(None) "
                              "switches it off)")
-        if self._surf_on:
+        if self._surf_on and not self._combined:
             raise ValueError("an input disturbance is not offered while a surface window is in force (set_surface(None) switches it off)")
         if isinstance(d, np.ndarray):
             shape, dtype_ok = tuple(d.shape), d.dtype == np.float64
@@ -513,10 +522,10 @@ class BatchController:
         B, N = self.batch, self.N
         if self.configs[0]["solver_type"] != packing.SOLVER_RTI:
             raise ValueError("set_surface needs an SQP_RTI controller: the scheduled surface is not offered with full SQP")
-        if self._term_on:
+        if self._term_on and not self._combined:
             raise ValueError("a surface window is not offered while a terminal cost is in force (set_terminal_cost(None) "
                              "switches it off)")
-        if self._dist_on:
+        if self._dist_on and not self._combined:
             raise ValueError("a surface window is not offered while an input disturbance is in force (set_input_disturbance(None) "
                              "switches it off)")
         if isinstance(coeffs, np.ndarray):
@@ -628,6 +637,8 @@ class BatchController:
         ``sens=True``, ``sens_w=True`` and ``dist`` then raise ``ValueError``."""
         import torch
 
+        if self._combined:
+            return self._step_combined(xhat, predict, yref, shift, sens, sens_w, dist, surface)
         if surface is not None:
             if dist is not None:
                 raise ValueError("a surface window is not offered together with an input disturbance (dist)")
@@ -728,6 +739,53 @@ class BatchController:
         if sens_w:
             out["du0_dw"] = self._sensw
         return out
+
+    def _step_combined(self, xhat, predict, yref, shift, sens, sens_w, dist, surface) -> Dict:
+        """step() of a controller built with combined=True: whatever of the terminal cost, the input disturbance and the surface
+        window is in force goes into ONE launch of the combined step, with ``shift`` as its warm-start modes; what is switched off is
+        handed over as None and the library fills its neutral table.  With ``shift`` the tail is propagated with this step's
+        disturbance."""
+        import torch
+
+        if sens or sens_w:
+            raise ValueError("step(sens=True) / step(sens_w=True) are not offered on a combined controller (BatchController(..., "
+                             "combined=True)): the combined step forms no sensitivities")
+        if surface is not None:
+            self._check_surface(surface)
+        if dist is not None:
+            self._check_disturbance(dist)
+        if yref is not None:
+            self._check_reference(yref)
+        shift_all = isinstance(shift, (bool, np.bool_))
+        if not shift_all:
+            self._check_mask(shift, "shift")
+        x = self._xhat(xhat)
+        io = dict(self._buffers(predict), xhat=x)
+        if yref is not None:
+            self.set_reference(yref)
+        if dist is not None:
+            self.set_input_disturbance(dist)
+        if surface is not None:
+            self.set_surface(surface)
+        stream = torch.cuda.current_stream(self.device)
+        warm = None
+        if self._reset_mask is not None or not shift_all or bool(shift):
+            warm = self._compose_warm(shift, shift_all, stream)
+        for on, src in ((self._ref_on, self._ref_stream), (True, self._weights_stream), (self._term_on, self._term_stream),
+                        (self._dist_on, self._dist_stream), (self._surf_on, self._surf_stream)):
+            if on and src is not None and src != stream:
+                stream.wait_stream(src)                   # the copies land before the step reads them
+        # (whatever changed, or was switched off, leaves a stale linearisation behind exactly as a changed reference does)
+        self.engine.step_combined(io, self._yref if self._ref_on else None, ref_changed=self._ref_changed, warm=warm, reset=self._reset,
+                                  term=self._term if self._term_on else None, term_changed=self._term_changed,
+                                  dist=self._dist if self._dist_on else None, dist_changed=self._dist_changed,
+                                  surf=self._surf if self._surf_on else None, surf_changed=self._surf_changed,
+                                  stream=stream.cuda_stream)
+        self._step_stream = stream
+        self._reset = False
+        self._ref_changed = self._term_changed = self._dist_changed = self._surf_changed = False
+        self._reset_mask = None
+        return {k: v for k, v in io.items() if k != "xhat"}
 
     def _compose_warm(self, shift, shift_all, stream):
         """The int32 [B] modes of the next step in the controller's own buffer, written on the step's stream: reset where

@@ -3441,13 +3441,17 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
     // this simulation's surface table.  Step t's window is ssched + t * NSURF -- stage k reads row t + k -- and log column t measures
     // the task errors against row t, as the reference schedule's.  The step linearises again at its start (REF), so nothing of a
     // window carries; the row index is the absolute step number, in every launch.
-    // SHIFT (with REF and PERT, not with TERM or OBS; the kernels of mpcb_rollout_warm, mpc_rollout_shift.hip): `wmode` is this
+    // SHIFT (with REF and PERT, not with TERM or OBS but COMBINED, below; the kernels of mpcb_rollout_warm, mpc_rollout_shift.hip): `wmode` is this
     // simulation's warm-start mode, constant over the run.  With WARM_SHIFT every step t >= 1 -- t the absolute step number: the
     // first step of a later launch too, never step 0, which starts from the initial guess -- moves the carried solver memory one
     // stage towards stage 0 first (shift_pass), exactly as control_step<WARM> does: stage k of step t and stage k + 1 of step
     // t - 1 read the same rows of the tables.  Any other value carries.  The step linearises at its start anyway (REF), and
     // nothing of the chunk pool is live between the log of step t - 1 and the first pass of step t (shift_group stages through
     // it): a REF step forms no fast-path right-hand side ahead, every QP factorises afresh, and the log collects in Smem::logbuf.
+    // COMBINED (Engine<Ex, TERM_TABLE, DIST_SHARED, 1>::rollout<true, true, true, true>; the kernels of mpcb_rollout_combined,
+    // mpc_rollout_combined.hip): all four at once.  Step t sets x_e = row t of the terminal table and the surface window at row t --
+    // absolute step numbers, so they slide with the shift in every launch -- publishes d^_t, THEN shifts (the tail takes d^_t), then
+    // solves.  A simulation that does not use a feature brings neutral data for it (include/mpcbatch.h).  Nothing new carries.
     struct NoSched {};
     template <bool REF = false, bool PERT = false, bool OBS = false, bool SHIFT = false>
     MPC_HD void rollout(const Outputs &out, int inst, int step0, int step1, typename std::conditional<REF, const double *, NoSched>::type sched = {},
@@ -3458,8 +3462,10 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
                         typename std::conditional<SHIFT, int, NoSched>::type wmode = {})
     {
         static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
-        static_assert(!SHIFT || (REF && PERT && !TERM && !DIST), "the rollout with the shift warm start runs the perturbed rollout's step, without a terminal cost or an observer");
-        static_assert(!SURF || (REF && PERT && !TERM && !DIST), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
+        // (COMBINED: the one instantiation in which all four are live, the kernels of mpcb_rollout_combined; any other mix stays refused)
+        constexpr bool COMBINED = TERM == TERM_TABLE && DIST == DIST_SHARED && SURF == 1 && REF && PERT && OBS && SHIFT;
+        static_assert(!SHIFT || COMBINED || (REF && PERT && !TERM && !DIST), "the rollout with the shift warm start runs the perturbed rollout's step, without a terminal cost or an observer");
+        static_assert(!SURF || COMBINED || (REF && PERT && !TERM && !DIST), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
         static_assert(!TERM || (TERM == TERM_TABLE && REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
         static_assert(OBS == (DIST == DIST_SHARED) && (!OBS || (REF && PERT)), "the rollout with an observer runs the perturbed rollout's step on the engine whose disturbance is in the shared block");
         static_assert(!DIST || OBS, "a rollout takes its input disturbance from its own observer");
@@ -3525,9 +3531,6 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
             }
             if constexpr (TERM == TERM_TABLE) term.x = tt.x_ref + (size_t)i * NX;
             if constexpr (SURF) this->surf = ssched + (size_t)i * NSURF;
-            if constexpr (SHIFT) {
-                if (i >= 1 && ex.uni(wmode) == WARM_SHIFT) shift_pass();
-            }
             if constexpr (OBS) ex.par([&](int lane) {
                 // the estimate this step's model takes: into the shared block for eff_u, and row i of the log
                 if (lane < 6) {
@@ -3536,6 +3539,11 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
                     gst(ob.d_hat + (size_t)i * NU + lane, ob_d.at(lane));
                 }
             });
+            // (after the publication: with OBS the shifted tail is x_N <- Ad x_N + Bd (u_{N-1} + d^_t), THIS step's estimate, which
+            // shift_pass reads through eff_u -- the phase boundary between the two orders the write and the reads)
+            if constexpr (SHIFT) {
+                if (i >= 1 && ex.uni(wmode) == WARM_SHIFT) shift_pass();
+            }
             const int status = nlp_step<!PERT>(lin_valid, &sqp_iter, &qp_iter, res4, &cost, &plant_done, lin, search);
             const double t1 = ex.clock();
             PROF_T0(tp);
@@ -3891,13 +3899,16 @@ struct Engine : DistPtr<DIST>, SurfPtr<SURF> {
     template <bool WARM = false, bool SENS = false, bool SENSW = false>
     MPC_HD void control_step(const StepIO &io, int inst, bool reset)
     {
+        // (COMBINED: Engine<Ex, 1, 1, 1>::control_step<true>, the kernels of mpcb_step_combined -- terminal cost, input disturbance,
+        // surface window and per-simulation warm start in one step; any other mix stays refused)
+        constexpr bool COMBINED = TERM == 1 && DIST == 1 && SURF == 1 && WARM && !SENS && !SENSW;
         static_assert(!(TERM && SENSW), "the weight sensitivity is not offered with a terminal cost");
-        static_assert(!(DIST && (TERM || SENS || SENSW)), "the input disturbance is not offered with sensitivities or a terminal cost");
+        static_assert(COMBINED || !(DIST && (TERM || SENS || SENSW)), "the input disturbance is not offered with sensitivities or a terminal cost");
         Smem &sm = ex.smem();
         Ws &w = c.w;
         if constexpr (TERM) term = io.term + (size_t)inst * NTERM;
         if constexpr (DIST) this->dist = io.dist + (size_t)inst * NU;
-        static_assert(!(SURF && (TERM || DIST || SENS || SENSW)), "the scheduled surface is not offered with sensitivities, a terminal cost or an input disturbance");
+        static_assert(COMBINED || !(SURF && (TERM || DIST || SENS || SENSW)), "the scheduled surface is not offered with sensitivities, a terminal cost or an input disturbance");
         if constexpr (SURF) this->surf = io.surf + (size_t)inst * N * NSURF;
         bool lin_valid = false;
         int mode = WARM_CARRY;

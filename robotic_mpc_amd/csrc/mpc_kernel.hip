@@ -149,8 +149,8 @@ __global__ void mpc_debug_task_lin_kernel(int n, Robot rb, const InstParams *__r
 
 // ------------------------------------------------------------------------------------ host
 // The variants of the controller step and the kinds of rollout; each is one kernel (family) per engine, see with_kernel below.
-enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS, STEP_DIST, STEP_SURF };
-enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM, ROLLOUT_OBS, ROLLOUT_SURF, ROLLOUT_SHIFT, ROLLOUT_SHIFT_SURF };
+enum StepVariant { STEP_BASE, STEP_WARM, STEP_SENS, STEP_SENSW, STEP_TERM, STEP_TERM_SENS, STEP_DIST, STEP_SURF, STEP_COMBINED };
+enum RolloutKind { ROLLOUT_BASE, ROLLOUT_REF, ROLLOUT_PERT, ROLLOUT_TERM, ROLLOUT_OBS, ROLLOUT_SURF, ROLLOUT_SHIFT, ROLLOUT_SHIFT_SURF, ROLLOUT_COMBINED };
 
 struct mpcb_handle {
     int device = -1;
@@ -180,6 +180,10 @@ struct mpcb_handle {
     bool controller = false;   // set up by mpcb_setup_controller: mpcb_step only (no rollouts)
     bool reset_next = false;   // the next mpcb_step starts from the initial guess whatever its flag says
     bool weights_changed = false;   // mpcb_set_weights since the last step: the carried linearisation is stale (as after ref_changed)
+    double *d_neutral = nullptr;    // mpcb_step_combined / mpcb_rollout_combined: the neutral tables of the features given as NULL
+    size_t neutral_cap = 0;         // (allocated on the first such call, never part of the workspace)
+    size_t neutral_layout[5] = {0, 0, 0, 0, 0};   // what the block holds: entry (1 rollout, 2 step) and the doubles of its four runs;
+                                    // {0, ..}: nothing -- mpcb_setup* invalidates it (the surface rows are the packed a..f)
 };
 
 static int fail(mpcb_handle *h, int code, const char *what, hipError_t e = hipSuccess)
@@ -227,12 +231,14 @@ static int with_kernel(const mpcb_handle *h, StepVariant v, F &&f)
 {
     const int nw = h->waves_per_sim, wpe = h->wpe;
     if (h->engine == 1)
-        return f(v == STEP_SURF      ? stream_step_surf_kernel()
+        return f(v == STEP_COMBINED  ? stream_step_combined_kernel()
+                 : v == STEP_SURF    ? stream_step_surf_kernel()
                  : v == STEP_DIST    ? stream_step_dist_kernel()
                  : v == STEP_TERM_SENS ? stream_step_term_sens_kernel() : v == STEP_TERM ? stream_step_term_kernel()
                  : v == STEP_SENSW   ? stream_step_sensw_kernel()     : v == STEP_SENS ? stream_step_sens_kernel()
                  : v == STEP_WARM    ? stream_step_warm_kernel()      : stream_step_kernel());
-    return f(v == STEP_SURF      ? step_surf_kernel(nw, wpe)
+    return f(v == STEP_COMBINED  ? step_combined_kernel(nw, wpe)
+             : v == STEP_SURF    ? step_surf_kernel(nw, wpe)
              : v == STEP_DIST    ? step_dist_kernel(nw, wpe)
              : v == STEP_TERM_SENS ? step_term_sens_kernel(nw, wpe) : v == STEP_TERM ? step_term_kernel(nw, wpe)
              : v == STEP_SENSW   ? step_sensw_kernel(nw, wpe)     : v == STEP_SENS ? step_sens_kernel(nw, wpe)
@@ -243,12 +249,14 @@ static int with_kernel(const mpcb_handle *h, RolloutKind kind, F &&f)
 {
     const int nw = h->waves_per_sim, wpe = h->wpe;
     if (h->engine == 1)
-        return kind == ROLLOUT_SHIFT || kind == ROLLOUT_SHIFT_SURF ? f(stream_rollout_shift_kernel(kind == ROLLOUT_SHIFT_SURF))
+        return kind == ROLLOUT_COMBINED ? f(stream_rollout_combined_kernel())
+             : kind == ROLLOUT_SHIFT || kind == ROLLOUT_SHIFT_SURF ? f(stream_rollout_shift_kernel(kind == ROLLOUT_SHIFT_SURF))
              : kind == ROLLOUT_SURF ? f(stream_rollout_surf_kernel())
              : kind == ROLLOUT_OBS  ? f(stream_rollout_obs_kernel())
              : kind == ROLLOUT_TERM ? f(stream_rollout_term_kernel()) : kind == ROLLOUT_PERT ? f(stream_rollout_pert_kernel())
              : kind == ROLLOUT_REF  ? f(stream_rollout_ref_kernel())  : f(stream_rollout_kernel(h->pb.precision));
-    return kind == ROLLOUT_SHIFT || kind == ROLLOUT_SHIFT_SURF ? f(rollout_shift_kernel(nw, wpe, kind == ROLLOUT_SHIFT_SURF))
+    return kind == ROLLOUT_COMBINED ? f(rollout_combined_kernel(nw, wpe))
+         : kind == ROLLOUT_SHIFT || kind == ROLLOUT_SHIFT_SURF ? f(rollout_shift_kernel(nw, wpe, kind == ROLLOUT_SHIFT_SURF))
          : kind == ROLLOUT_SURF ? f(rollout_surf_kernel(nw, wpe))
          : kind == ROLLOUT_OBS  ? f(rollout_obs_kernel(nw, wpe))
          : kind == ROLLOUT_TERM ? f(rollout_term_kernel(nw, wpe)) : kind == ROLLOUT_PERT ? f(rollout_pert_kernel(nw, wpe))
@@ -314,6 +322,10 @@ static void launch(RolloutShiftFn k, const mpcb_handle *h, hipStream_t s, const 
 {
     latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.surf_sched, a.warm);
 }
+static void launch(RolloutCombinedFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    latency_launch(k, h, a.grid, s, a.out, a.step0, a.step1, h->pool_doubles, a.yref_sched, a.pert, a.term, a.obs, a.surf_sched, a.warm);
+}
 static void launch(StreamRolloutFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
 {
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks);
@@ -346,6 +358,12 @@ static void launch(StreamRolloutShiftFn k, const mpcb_handle *h, hipStream_t s, 
     stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.surf_sched, a.warm);
 }
 
+static void launch(StreamRolloutCombinedFn k, const mpcb_handle *h, hipStream_t s, const RolloutArgs &a)
+{
+    stream_launch(k, h, a.grid, s, a.out, a.step0, a.step1, a.queue, a.chunk_steps, a.timeout_ticks, a.yref_sched, a.pert, a.term, a.obs,
+                  a.surf_sched, a.warm);
+}
+
 // One launch of `variant`'s kernel on stream s, between the two events mpcb_last_kernel_ms reads.  Latency engine: the dynamic-LDS
 // ceiling is a process-wide attribute of the kernel, not of this handle, so it is raised to the largest pool any handle can ask
 // for, right before the launch.
@@ -368,7 +386,38 @@ static int timed_launch(mpcb_handle *h, V variant, hipStream_t s, const Args &ar
 
 static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
                        const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream,
-                       const double *surf_sched = nullptr, const int *warm = nullptr);
+                       const double *surf_sched = nullptr, const int *warm = nullptr, bool combined = false);
+
+// mpcb_step_combined / mpcb_rollout_combined: the neutral tables of the features given as NULL, in one block of device memory the
+// handle keeps: runs of n[0..3] doubles, [0] and [1] zeros (terminal record / blocks and x_ref; disturbance / gains and the d_hat
+// scratch rows), [2] the neutral surface table of `rows` rows per simulation, [3] zeros read as MPCB_WARM_CARRY.  Called AFTER the
+// entry has validated its arguments.  The tables are constants of the handle's setup: they are filled once -- on stream s, which is
+// synchronised so that a later call on another stream finds them -- and again only when the layout changes or after a new setup.
+static int neutral_tables(mpcb_handle *h, int entry, const size_t n[4], size_t rows, hipStream_t s, double **out)
+{
+    static_assert(WARM_CARRY == 0, "the neutral modes are a zero fill");
+    const size_t total = n[0] + n[1] + n[2] + n[3], need = total * sizeof(double);
+    const size_t layout[5] = {(size_t)entry, n[0], n[1], n[2], n[3]};
+    *out = nullptr;
+    if (total == 0) return MPCB_OK;
+    if (need > h->neutral_cap) {
+        if (h->d_neutral) (void)hipFree(h->d_neutral);      // (hipFree waits for the launches that read the old block)
+        h->d_neutral = nullptr; h->neutral_cap = 0; h->neutral_layout[0] = 0;
+        if (hipMalloc((void **)&h->d_neutral, need) != hipSuccess) return fail(h, MPCB_ENOMEM, "neutral table allocation failed");
+        h->neutral_cap = need;
+    }
+    *out = h->d_neutral;
+    if (std::memcmp(layout, h->neutral_layout, sizeof layout) == 0) return MPCB_OK;
+    h->neutral_layout[0] = 0;
+    HIPCHK(h, hipMemsetAsync(h->d_neutral, 0, need, s));
+    if (n[2]) {
+        neutral_surf_fill(h->pb.batch, rows, h->d_params, h->d_neutral + n[0] + n[1], s);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    std::memcpy(h->neutral_layout, layout, sizeof layout);
+    return MPCB_OK;
+}
 
 extern "C" {
 
@@ -411,6 +460,7 @@ void mpcb_destroy(mpcb_handle *h)
     if (h->d_params) (void)hipFree(h->d_params);
     if (h->d_ws) (void)hipFree(h->d_ws);
     if (h->d_queue) (void)hipFree(h->d_queue);
+    if (h->d_neutral) (void)hipFree(h->d_neutral);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     delete h;
@@ -573,6 +623,7 @@ static int setup_impl(mpcb_handle *h, const mpcb_problem *p, const double *param
     }
     h->ready = true;
     h->next_step = 0;
+    h->neutral_layout[0] = 0;       // (new parameter records: the neutral surface table is stale)
     h->last_rollout = ROLLOUT_BASE;
     h->timed = false;
     h->controller = controller;
@@ -668,13 +719,34 @@ int mpcb_rollout_warm(mpcb_handle *h, int step0, int step1, const mpcb_result *o
     return rollout_any(h, step0, step1, o, yref_sched, pert_, nullptr, nullptr, nullptr, nullptr, stream, surf_sched, warm);
 }
 
+// (always the kernels of mpc_rollout_combined.hip / mpc_stream_rollout_combined.hip; a feature given as NULL gets its neutral table here)
+int mpcb_rollout_combined(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
+                          const mpcb_term_table *term, const mpcb_observer *obs, const double *surf_sched, const int *warm, void *stream)
+{
+    if (!h) return MPCB_EINVAL;
+    if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
+    if (h->controller) return fail(h, MPCB_ESTATE, "mpcb_rollout on a controller handle (mpcb_setup_controller): use mpcb_step");
+    if (h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_combined: the combined rollout is offered in fp64 only (no fp32 Riccati leg)");
+    if (h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_combined: the combined rollout is offered with SQP_RTI only");
+    if (!yref_sched)
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_combined: the combined rollout needs a reference schedule (the packed rows when there is none)");
+    if (term && (!term->blocks || !term->x_ref))
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_combined: term needs blocks and x_ref");
+    if (obs && (!obs->gain || !obs->d_hat))
+        return fail(h, MPCB_EINVAL, "mpcb_rollout_combined: obs needs gain and d_hat");
+    return rollout_any(h, step0, step1, o, yref_sched, pert_, term ? term->blocks : nullptr, term ? term->x_ref : nullptr,
+                       obs ? obs->gain : nullptr, obs ? obs->d_hat : nullptr, stream, surf_sched, warm, true);
+}
+
 }  // extern "C"
 
 // The one launch path of every rollout: at most one of term_blocks, obs_gain and surf_sched is given; warm goes with neither
-// term_blocks nor obs_gain.
+// term_blocks nor obs_gain.  `combined` (mpcb_rollout_combined): all of them are given, and the combined kernels run.
 static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *o, const double *yref_sched, const mpcb_plant_pert *pert_,
                        const double *term_blocks, const double *term_xref, const double *obs_gain, double *d_hat, void *stream,
-                       const double *surf_sched, const int *warm)
+                       const double *surf_sched, const int *warm, bool combined)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_rollout before mpcb_setup");
@@ -722,7 +794,20 @@ static int rollout_any(mpcb_handle *h, int step0, int step1, const mpcb_result *
         return fail(h, MPCB_EINVAL, "every result array must be provided");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const RolloutKind kind = warm ? (surf_sched ? ROLLOUT_SHIFT_SURF : ROLLOUT_SHIFT) : surf_sched ? ROLLOUT_SURF : obs_gain ? ROLLOUT_OBS : term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
+    if (combined) {
+        // every argument is validated: the neutral tables of the features given as NULL (zero blocks -- x_e then multiplies zeros --,
+        // zero gains with the d_hat log going to scratch rows, the packed surface on every row, all modes MPCB_WARM_CARRY)
+        const size_t B = (size_t)h->pb.batch, Nsim = (size_t)h->pb.Nsim, rows = Nsim + (size_t)h->pb.N;
+        const size_t n[4] = {term_blocks ? 0 : B * 18 + B * Nsim * 12, obs_gain ? 0 : B * 12 + B * Nsim * 6,
+                             surf_sched ? 0 : B * rows * NSURF, warm ? 0 : (B + 1) / 2};
+        double *nb = nullptr;
+        if (int rc = neutral_tables(h, 1, n, rows, s, &nb)) return rc;
+        if (!term_blocks) { term_blocks = nb; term_xref = nb + B * 18; }
+        if (!obs_gain) { obs_gain = nb + n[0]; d_hat = nb + n[0] + B * 12; }
+        if (!surf_sched) surf_sched = nb + n[0] + n[1];
+        if (!warm) warm = reinterpret_cast<const int *>(nb + n[0] + n[1] + n[2]);
+    }
+    const RolloutKind kind = combined ? ROLLOUT_COMBINED : warm ? (surf_sched ? ROLLOUT_SHIFT_SURF : ROLLOUT_SHIFT) : surf_sched ? ROLLOUT_SURF : obs_gain ? ROLLOUT_OBS : term_blocks ? ROLLOUT_TERM : pert_ ? ROLLOUT_PERT : yref_sched ? ROLLOUT_REF : ROLLOUT_BASE;
     RolloutArgs args{};
     args.yref_sched = yref_sched;
     if (pert_) args.pert = PlantPert{pert_->wcv, pert_->u_dist, pert_->x_noise};
@@ -810,7 +895,8 @@ int mpcb_step_sens(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
 
 static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                      const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream,
-                     const double *dist = nullptr, int dist_changed = 0, const double *surf = nullptr, int surf_changed = 0);
+                     const double *dist = nullptr, int dist_changed = 0, const double *surf = nullptr, int surf_changed = 0,
+                     bool combined = false);
 
 // (du0_dw == NULL: all of the above; otherwise the kernels that also form the weight sensitivity, supersets of the sens ones)
 int mpcb_step_sens_w(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
@@ -843,9 +929,26 @@ int mpcb_step_surf(mpcb_handle *h, const mpcb_step_io *io, const double *yref, i
     return step_impl(h, io, yref, ref_changed, warm, reset, nullptr, nullptr, nullptr, 0, nullptr, stream, nullptr, 0, surf, surf_changed);
 }
 
+// (always the kernels of mpc_step_combined.hip / mpc_stream_step_combined.hip; a feature given as NULL gets its neutral table here, and
+// warm == NULL stays NULL: the step reads it as MPCB_WARM_CARRY for all)
+int mpcb_step_combined(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
+                       const double *term, int term_changed, const double *dist, int dist_changed, const double *surf, int surf_changed,
+                       void *stream)
+{
+    if (!h) return MPCB_EINVAL;
+    if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
+    if (!h->controller) return fail(h, MPCB_ESTATE, "mpcb_step needs a handle set up by mpcb_setup_controller");
+    if (h->pb.solver_type != MPCB_SOLVER_SQP_RTI)
+        return fail(h, MPCB_EINVAL, "mpcb_step_combined: the combined step is offered with SQP_RTI; this controller runs full SQP");
+    if (h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
+        return fail(h, MPCB_EINVAL, "mpcb_step_combined: the combined step is offered in fp64 only (no fp32 Riccati leg)");
+    return step_impl(h, io, yref, ref_changed, warm, reset, nullptr, nullptr, term, term_changed, nullptr, stream, dist, dist_changed, surf,
+                     surf_changed, true);
+}
+
 static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref, int ref_changed, const int *warm, int reset,
                      const mpcb_step_sens_out *sens, double *du0_dw, const double *term, int term_changed, double *du0_dxe, void *stream,
-                     const double *dist, int dist_changed, const double *surf, int surf_changed)
+                     const double *dist, int dist_changed, const double *surf, int surf_changed, bool combined)
 {
     if (!h) return MPCB_EINVAL;
     if (!h->ready) return fail(h, MPCB_ESTATE, "mpcb_step before mpcb_setup_controller");
@@ -868,9 +971,19 @@ static int step_impl(mpcb_handle *h, const mpcb_step_io *io, const double *yref,
         return fail(h, MPCB_EINVAL, "mpcb_step_surf: the scheduled surface is offered with SQP_RTI; this controller runs full SQP");
     if (surf && h->pb.precision == MPCB_PRECISION_FP32_RICCATI)
         return fail(h, MPCB_EINVAL, "mpcb_step_surf: the scheduled surface is offered in fp64 only (no fp32 Riccati leg)");
-    const StepVariant variant = surf ? STEP_SURF : dist ? STEP_DIST : term ? (sens ? STEP_TERM_SENS : STEP_TERM) : du0_dw ? STEP_SENSW : sens ? STEP_SENS : warm ? STEP_WARM : STEP_BASE;
+    const StepVariant variant = combined ? STEP_COMBINED : surf ? STEP_SURF : dist ? STEP_DIST : term ? (sens ? STEP_TERM_SENS : STEP_TERM) : du0_dw ? STEP_SENSW : sens ? STEP_SENS : warm ? STEP_WARM : STEP_BASE;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
+    if (combined) {
+        // every argument is validated: the neutral tables of the features given as NULL (a zero record, d = 0, the packed surface)
+        const size_t B = (size_t)h->pb.batch;
+        const size_t n[4] = {term ? 0 : B * NTERM, dist ? 0 : B * NU, surf ? 0 : B * (size_t)h->pb.N * NSURF, 0};
+        double *nb = nullptr;
+        if (int rc = neutral_tables(h, 2, n, (size_t)h->pb.N, s, &nb)) return rc;
+        if (!term) term = nb;
+        if (!dist) dist = nb + n[0];
+        if (!surf) surf = nb + n[0] + n[1];
+    }
     StepArgs args;
     StepIO &sio = args.io;
     std::memcpy(&sio, io, sizeof(mpcb_step_io));

@@ -21,6 +21,8 @@ using RolloutSurfFn = void (*)(Problem, Robot, const InstParams *, double *, siz
                                const double *);
 using RolloutShiftFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
                                 const double *, const int *);
+using RolloutCombinedFn = void (*)(Problem, Robot, const InstParams *, double *, size_t, Outputs, int, int, int, const double *, PlantPert,
+                                   TermTab, ObsArg, const double *, const int *);
 // throughput engine (mpc_stream.h): the robot record in device memory, no pool; rollouts take (queue, chunk_steps, timeout_ticks)
 using StreamStepFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, StepIO, int);
 using StreamRolloutFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long);
@@ -36,6 +38,8 @@ using StreamRolloutSurfFn = void (*)(Problem, const Robot *, const InstParams *,
                                      const double *, PlantPert, const double *);
 using StreamRolloutShiftFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
                                       const double *, PlantPert, const double *, const int *);
+using StreamRolloutCombinedFn = void (*)(Problem, const Robot *, const InstParams *, double *, size_t, Outputs, int, int, int *, int, long long,
+                                         const double *, PlantPert, TermTab, ObsArg, const double *, const int *);
 
 // The kernel of the latency engine's template K<NWV, WPE = 1> for a launch geometry (mpcb_setup picks it; <2> and <1> are reached
 // through MPCB_WAVES_PER_SIM), as a pointer of type Fn.  The module holds its kernels in the order they are instantiated in, which is
@@ -77,5 +81,13 @@ StreamRolloutSurfFn stream_rollout_surf_kernel();
 // mpc_rollout_shift.hip / mpc_stream_rollout_shift.hip: mpcb_rollout_warm, without (`surf` false) and with a surface table
 RolloutShiftFn rollout_shift_kernel(int waves_per_sim, int wpe, bool surf);
 StreamRolloutShiftFn stream_rollout_shift_kernel(bool surf);
+// mpc_step_combined.hip / mpc_stream_step_combined.hip, mpc_rollout_combined.hip / mpc_stream_rollout_combined.hip: mpcb_step_combined
+// and mpcb_rollout_combined, all four features in one instantiation; neutral_surf_fill (mpc_rollout_combined.hip) writes the neutral
+// surface table [batch][rows][NSURF], every row of simulation i = InstParams::coeffs of i, on stream s
+StepFn step_combined_kernel(int waves_per_sim, int wpe);
+StreamStepFn stream_step_combined_kernel();
+RolloutCombinedFn rollout_combined_kernel(int waves_per_sim, int wpe);
+StreamRolloutCombinedFn stream_rollout_combined_kernel();
+void neutral_surf_fill(int batch, size_t rows, const InstParams *params, double *out, hipStream_t s);
 
 }  // namespace mpcb

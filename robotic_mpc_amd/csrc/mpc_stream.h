@@ -2351,7 +2351,11 @@ SE_DEV StepStats mpc_step(const Problem &pb, Carry &c, Lin &&lin, Search &&searc
 // is this simulation's surface table.  Step t's window is ss_ + t * NSURF -- stage k < N reads row t + k -- and log column t measures
 // the task errors against row t.  Nothing of a window carries to the next step, launch or work item: the row index is the absolute
 // step number.
-// SHIFT (with REF and PERT, not with TERM or OBS; the kernel of mpcb_rollout_warm, mpc_stream_rollout_shift.hip): `wm_` is this
+// COMBINED (REF, PERT, TERM, OBS, SURF and SHIFT; the kernel of mpcb_rollout_combined, mpc_stream_rollout_combined.hip): all four in one
+// mpc_step.  The observer publishes d^_t first, then the shift runs with it (shift_pass<false, DIST_SHARED>), then the step; x_e and the
+// surface window are rows of the absolute step number, the terminal cost sits on the simulation's own last stage.  A simulation that
+// does not use a feature brings neutral data for it (include/mpcbatch.h).  Nothing new carries.
+// SHIFT (with REF and PERT, not with TERM or OBS but COMBINED; the kernel of mpcb_rollout_warm, mpc_stream_rollout_shift.hip): `wm_` is this
 // simulation's warm-start mode, constant over the run.  With WARM_SHIFT every step t >= 1 -- t the absolute step number: the first
 // step of a later launch and of a later work item too, never step 0, which starts from the initial guess -- moves the carried solver
 // memory one stage towards stage 0 of the simulation's own horizon first (shift_pass<false>, as control_step<WARM> does).  Any other
@@ -2368,13 +2372,15 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
                     typename std::conditional<SURF, const double *, NoSched>::type ss_ = {},
                     typename std::conditional<SHIFT, int, NoSched>::type wm_ = {})
 {
-    static_assert(!SHIFT || (REF && PERT && !TERM && !OBS), "the rollout with the shift warm start runs the perturbed rollout's step, without a terminal cost or an observer");
-    static_assert(!SURF || (REF && PERT && !TERM && !OBS), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
+    // (COMBINED: the one instantiation in which all four are live, the kernel of mpcb_rollout_combined; any other mix stays refused)
+    constexpr bool COMBINED = REF && PERT && TERM && OBS && SURF && SHIFT;
+    static_assert(!SHIFT || COMBINED || (REF && PERT && !TERM && !OBS), "the rollout with the shift warm start runs the perturbed rollout's step, without a terminal cost or an observer");
+    static_assert(!SURF || COMBINED || (REF && PERT && !TERM && !OBS), "the rollout over a scheduled surface runs the perturbed rollout's step, without a terminal cost or an observer");
     const double *ssched = nullptr;
     if constexpr (SURF) ssched = uni_ref(TaskRef{ss_}).y;
     static_assert(REF || !PERT, "the perturbed rollout runs the scheduled rollout's step");
     static_assert(!TERM || (REF && PERT), "the rollout with a terminal cost runs the perturbed rollout's step");
-    static_assert(!OBS || (REF && PERT && !TERM), "the rollout with an observer runs the perturbed rollout's step, without a terminal cost");
+    static_assert(!OBS || COMBINED || (REF && PERT && !TERM), "the rollout with an observer runs the perturbed rollout's step, without a terminal cost");
     const double *sched = nullptr;
     if constexpr (REF) sched = uni_ref(TaskRef{sched_}).y;
     const double *p_wcv = nullptr, *p_ud = nullptr, *p_xn = nullptr;
@@ -2436,9 +2442,6 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
         if constexpr (REF) {
             const TaskRef ref{sched + (size_t)i * NTASK};
             c.lin_valid = false;
-            if constexpr (SHIFT) {
-                if (i >= 1 && uni(wm_) == WARM_SHIFT) shift_pass<false, 0>(N, DistArg<0>{});
-            }
             if constexpr (OBS) {
                 // the estimate this step's model takes: into LDS for eff_u, and row i of the log
                 fence();
@@ -2449,6 +2452,17 @@ SE_DEV void rollout(const Problem &pb, const InstParams *params, const Robot *rb
                 }
                 fence();
             }
+            // (after the publication: with OBS the shifted tail is x_N <- Ad x_N + Bd (u_{N-1} + d^_t), THIS step's estimate, read from LDS)
+            if constexpr (SHIFT) {
+                if (i >= 1 && uni(wm_) == WARM_SHIFT) shift_pass<false, OBS ? DIST_SHARED : 0>(N, DistArg<OBS ? DIST_SHARED : 0>{});
+            }
+            if constexpr (COMBINED) {
+                // all four: the terminal cost on this simulation's own stage N with x_e = row i, the estimate in the model, window i
+                const SurfArg<1> sa{ssched + (size_t)i * NSURF};
+                s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true, 1>(alpha, do_update, sqp_mult, slot, ref, sa); },
+                                 [&](int sqp_iter) { return line_search<true, 1>(sqp_iter, ref, sa); }, nullptr, false, NoHook{},
+                                 TermArg<TERM_TABLE>{tt_.blocks, tt_.x_ref + (size_t)i * NX}, DistArg<DIST_SHARED>{});
+            } else
             if constexpr (TERM)
                 s = mpc_step<FT>(pb, c, [&](double alpha, bool do_update, bool sqp_mult, int slot) { lin_pass<true>(alpha, do_update, sqp_mult, slot, ref); },
                                  [&](int sqp_iter) { return line_search<true>(sqp_iter, ref); }, nullptr, false, NoHook{},
@@ -2773,13 +2787,15 @@ SE_PASS void sens_pass(double *dx_, double *dy_, int *valid_, int N, int NMAX, b
 // DIST (the kernel of mpcb_step_dist, SQP_RTI): io.dist holds this simulation's input disturbance (DistArg).  Not with SENS, SENSW, TERM.
 // SURF (the kernel of mpcb_step_surf): io.surf holds this simulation's surface window, row k = stage k's a..f, rows strided by the
 // batch's longest horizon as the reference's are (SurfArg).  Not with SENS, SENSW, TERM, DIST.
+// COMBINED (WARM, TERM, DIST and SURF, no sensitivities; the kernel of mpcb_step_combined): the four in one mpc_step.
 template <class FT, bool WARM = false, bool SENS = false, bool SENSW = false, bool TERM = false, bool DIST = false, bool SURF = false>
 SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robot *rbp, double *ws_base, size_t ws_stride,
                          const StepIO &io, int inst, bool reset)
 {
+    constexpr bool COMBINED = WARM && TERM && DIST && SURF && !SENS && !SENSW;
     static_assert(!(TERM && SENSW), "the weight sensitivity is not offered with a terminal cost");
-    static_assert(!(DIST && (TERM || SENS || SENSW)), "the input disturbance is not offered with sensitivities or a terminal cost");
-    static_assert(!(SURF && (TERM || SENS || SENSW || DIST)), "the scheduled surface is not offered with sensitivities, a terminal cost or an input disturbance");
+    static_assert(COMBINED || !(DIST && (TERM || SENS || SENSW)), "the input disturbance is not offered with sensitivities or a terminal cost");
+    static_assert(COMBINED || !(SURF && (TERM || SENS || SENSW || DIST)), "the scheduled surface is not offered with sensitivities, a terminal cost or an input disturbance");
     SSmem &sm = g_ssm;
     const int lane = threadIdx.x;
     const int N = load_instance<FT>(pb, params, rbp, ws_base, ws_stride, inst), NMAX = pb.N;
@@ -2842,6 +2858,9 @@ SE_DEV void control_step(const Problem &pb, const InstParams *params, const Robo
                                    io.sens_valid + inst, N, NMAX, exact, {},
                                    TermSensArgs<true>{tp, io.du0_dxe ? io.du0_dxe + (size_t)inst * NU * NX : nullptr});
         }, TermArg<true>{tp});
+    } else if constexpr (COMBINED) {
+        s = mpc_step<FT>(pb, c, lin, search, nullptr, false, NoHook{}, TermArg<true>{io.term + (size_t)inst * NTERM},
+                         DistArg<true>{io.dist + (size_t)inst * NU});
     } else if constexpr (TERM) {
         s = mpc_step<FT>(pb, c, lin, search, nullptr, false, NoHook{}, TermArg<true>{io.term + (size_t)inst * NTERM});
     } else if constexpr (DIST) {

@@ -341,7 +341,7 @@ def _empty_like_bucket(cfg: Dict, with_summary: bool = False) -> Dict[str, np.nd
     S, T = cfg["Nsim"], cfg["Nsim"] + 1
     out = {name: np.zeros((0,) + shp(S, T), dtype=np.float64 if ty == "f8" else np.int32)
            for name, ty, shp in RESULT_FIELDS}
-    if cfg.get("disturbance_observer") is not None:
+    if cfg.get("disturbance_observer") is not None or cfg.get("combine_features"):
         out["d_hat"] = np.zeros((0, S, 6))     # (the bucket's other ranks bring their estimates: every rank gathers the same keys)
     if with_summary:
         out["summary"] = np.zeros((0, NSUMMARY))

@@ -81,6 +81,44 @@ def warm_modes(cfgs: Sequence[Dict]) -> Optional[np.ndarray]:
     return modes if (modes == WARM_SHIFT).any() else None
 
 
+def combined_arrays(cfgs: Sequence[Dict]) -> Dict:
+    """The tables of a combined bucket as numpy arrays: "yref" [B, Nsim + N, 5], "pert" {"wcv" [B, 6], "u_dist" [B, Nsim, 6],
+    "x_noise" [B, Nsim, 12]}, "term" {"blocks" [B, 18], "x_ref" [B, Nsim, 12]}, "gain" [B, 12], "surf" [B, Nsim + N, 6], "warm" [B]
+    int32 (N the longest horizon).  A simulation that does not use a feature gets the neutral rows of include/mpcbatch.h: the packed
+    reference row, the model's bandwidths and zero disturbance / noise, zero terminal blocks (and zero x_ref rows), zero observer
+    gains, its own packed a..f on every row, WARM_CARRY."""
+    from . import observer, plant, reference, surface, terminal
+
+    B, Nsim = len(cfgs), int(cfgs[0]["Nsim"])
+    rows = Nsim + max(int(c["N"]) for c in cfgs)
+
+    def padded(y):
+        out = np.empty((rows, y.shape[1]))
+        out[:y.shape[0]], out[y.shape[0]:] = y, y[-1]
+        return out
+
+    a = {"yref": np.empty((B, rows, 5)), "pert": {"wcv": np.empty((B, 6)), "u_dist": np.zeros((B, Nsim, 6)), "x_noise": np.zeros((B, Nsim, 12))},
+         "term": {"blocks": np.zeros((B, 18)), "x_ref": np.zeros((B, Nsim, 12))}, "gain": np.zeros((B, 12)),
+         "surf": np.empty((B, rows, 6)), "warm": np.zeros(B, dtype=np.int32)}
+    for i, c in enumerate(cfgs):
+        a["yref"][i] = padded(reference.sample(c)) if c.get("reference_schedule") is not None else reference.packed_rows(c, rows)
+        a["surf"][i] = padded(surface.sample(c)) if c.get("surface_schedule") is not None else surface.packed_rows(c, rows)
+        if c.get("plant_perturbation") is not None:
+            p = plant.sample(c)
+            for k in ("wcv", "u_dist", "x_noise"):
+                a["pert"][k][i] = p[k]
+        else:
+            a["pert"]["wcv"][i] = np.asarray(c["wcv"], dtype=np.float64)
+        if c.get("terminal_cost") is not None:
+            t = terminal.sample(c)
+            a["term"]["blocks"][i], a["term"]["x_ref"][i] = t["blocks"].T.reshape(18), t["x_ref"]
+        if c.get("disturbance_observer") is not None:
+            a["gain"][i] = observer.stack([c])[0]
+        if c.get("warm_start", "carry") == "shift":
+            a["warm"][i] = WARM_SHIFT
+    return a
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -95,6 +133,16 @@ class MpcbStepSensOut(C.Structure):
     _fields_ = [("du0_dx", C.POINTER(C.c_double)), ("du0_dyref", C.POINTER(C.c_double)), ("valid", C.POINTER(C.c_int))]
 
 
+class MpcbTermTable(C.Structure):
+    """mpcb_term_table (include/mpcbatch.h): device pointers."""
+    _fields_ = [("blocks", C.POINTER(C.c_double)), ("x_ref", C.POINTER(C.c_double))]
+
+
+class MpcbObserver(C.Structure):
+    """mpcb_observer (include/mpcbatch.h): device pointers."""
+    _fields_ = [("gain", C.POINTER(C.c_double)), ("d_hat", C.POINTER(C.c_double))]
+
+
 _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", "mpcb_last_error",
             "mpcb_workspace_bytes", "mpcb_result_bytes_per_sim", "mpcb_setup", "mpcb_rollout", "mpcb_sync",
             "mpcb_last_kernel_ms", "mpcb_kernel_info", "mpcb_launch_info", "mpcb_engine", "mpcb_engine_for", "mpcb_summary",
@@ -102,7 +150,7 @@ _EXPORTS = ("mpcb_version", "mpcb_device_count", "mpcb_create", "mpcb_destroy", 
             "mpcb_step_ref", "mpcb_step_warm", "mpcb_step_sens", "mpcb_set_weights", "mpcb_step_sens_w", "mpcb_step_term",
             "mpcb_step_dist",
             "mpcb_rollout_ref", "mpcb_queue_used", "mpcb_rollout_pert", "mpcb_rollout_term", "mpcb_rollout_obs",
-            "mpcb_step_surf", "mpcb_rollout_surf", "mpcb_rollout_warm")
+            "mpcb_step_surf", "mpcb_rollout_surf", "mpcb_rollout_warm", "mpcb_step_combined", "mpcb_rollout_combined")
 
 
 def load_library(path: Optional[str] = None) -> C.CDLL:
@@ -167,6 +215,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.mpcb_rollout_surf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, C.c_void_p]
     lib.mpcb_rollout_warm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert), _dp, _ip,
                                       C.c_void_p]
+    lib.mpcb_step_combined.argtypes = [C.c_void_p, C.POINTER(MpcbStepIO), _dp, C.c_int, _ip, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp,
+                                       C.c_int, C.c_void_p]
+    lib.mpcb_rollout_combined.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(MpcbResult), _dp, C.POINTER(MpcbPlantPert),
+                                          C.POINTER(MpcbTermTable), C.POINTER(MpcbObserver), _dp, _ip, C.c_void_p]
     lib.mpcb_controller_engine_for.restype = C.c_int
     if hasattr(lib, "mpcb_debug_task_lin"):
         lib.mpcb_debug_task_lin.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
@@ -288,7 +340,7 @@ class MpcBatchEngine:
         return r
 
     def rollout(self, bufs, step0: int, step1: int, yref=None, stream: Optional[int] = None, pert=None, term=None, obs=None,
-                surf=None, warm=None):
+                surf=None, warm=None, combined: bool = False):
         """Asynchronous launch of closed-loop steps [step0, step1) into device buffers.  `yref`: the task reference schedules of
         the batch, a contiguous float64 device tensor [batch, Nsim + N, 5] (N the longest horizon; schedule_tensor) -- the same one
         for every launch of a run -- or None for the packed references (mpcb_rollout).  `pert`: the plant perturbation of the
@@ -308,7 +360,13 @@ class MpcBatchEngine:
         `warm`: the warm-start modes of the batch (mpcb_rollout_warm; warm_tensor), a contiguous int32 device tensor [batch] of
         WARM_CARRY / WARM_SHIFT, constant over the run -- the same one for every launch; a simulation whose mode is WARM_SHIFT moves
         its carried solver memory one stage towards stage 0 before every step but the run's first.  It needs `yref` likewise, takes
-        `pert` or the nominal plant and `surf` or the packed surface, and is not offered together with `term` or `obs`."""
+        `pert` or the nominal plant and `surf` or the packed surface, and is not offered together with `term` or `obs`.
+        `combined`: route to mpcb_rollout_combined, the one rollout in which `term`, `obs`, `surf` and `warm` may all be given (any
+        subset; each as described above, None = absent for the whole batch).  A simulation of the batch that does not use a feature
+        brings neutral rows for it (combined_tensors).  It needs `yref`; SQP_RTI and fp64 only.  Without it every refusal above
+        stands."""
+        if combined:
+            return self._rollout_pert(bufs, step0, step1, yref, pert, stream, term=term, obs=obs, surf=surf, warm=warm, combined=True)
         if warm is not None:
             if term is not None:
                 raise ValueError("the shift warm start (warm) is not offered together with a terminal cost (term)")
@@ -346,10 +404,14 @@ class MpcBatchEngine:
         if tuple(yref.shape) != (pb.batch, pb.Nsim + pb.N, 5) or not yref.is_contiguous() or str(yref.dtype) != "torch.float64":
             raise ValueError(f"yref must be a contiguous float64 tensor [{pb.batch}, {pb.Nsim + pb.N}, 5], got {tuple(yref.shape)} {yref.dtype}")
 
-    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None, obs=None, surf=None, warm=None):
+    def _rollout_pert(self, bufs, step0, step1, yref, pert, stream, term=None, obs=None, surf=None, warm=None, combined=False):
         """rollout(pert=, term=, obs=, surf=, warm=): every shape is checked before the library is called."""
         pb = self._pb
         tp = {}
+        if combined:
+            if yref is None:
+                raise ValueError("a combined rollout needs yref: schedule_tensor(cfgs) supplies the packed rows when there is no schedule")
+            pert = {} if pert is None else pert
         if warm is not None:
             if yref is None:
                 raise ValueError("a rollout with the shift warm start needs yref: schedule_tensor(cfgs) supplies the packed rows when "
@@ -423,6 +485,15 @@ class MpcBatchEngine:
 
             stream = torch.cuda.current_stream(self.device).cuda_stream
         r = self._result_struct(bufs)
+        if combined:
+            tt = MpcbTermTable(tp["blocks"], tp["x_ref"]) if term is not None else None
+            ob = MpcbObserver(tp["gain"], tp["d_hat"]) if obs is not None else None
+            self._check(self.lib.mpcb_rollout_combined(
+                self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
+                C.byref(tt) if tt is not None else None, C.byref(ob) if ob is not None else None,
+                C.cast(C.c_void_p(surf.data_ptr()), _dp) if surf is not None else None,
+                C.cast(C.c_void_p(warm.data_ptr()), _ip) if warm is not None else None, C.c_void_p(stream)), "mpcb_rollout_combined")
+            return
         if warm is not None:
             sp = C.cast(C.c_void_p(surf.data_ptr()), _dp) if surf is not None else None
             self._check(self.lib.mpcb_rollout_warm(self._h, step0, step1, C.byref(r), C.cast(C.c_void_p(yref.data_ptr()), _dp), C.byref(p),
@@ -490,6 +561,23 @@ class MpcBatchEngine:
         import torch
 
         return torch.from_numpy(modes).to(torch.device("cuda", self.device))
+
+    def combined_tensors(self, cfgs: Sequence[Dict]):
+        """What rollout(combined=True) takes for a bucket of configurations with combine_features, on this engine's device --
+        {"yref", "pert", "term", "obs", "surf", "warm"}, every table present -- or None for any other bucket.  Each simulation
+        brings its own rows for the features it uses and NEUTRAL rows for the others (combined_arrays), so one launch serves
+        whatever subsets the bucket mixes; obs["d_hat"] [batch, Nsim, 6] is filled by the rollout (zeros where there is no observer)."""
+        if not any(c.get("combine_features") for c in cfgs):
+            return None
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        a = combined_arrays(cfgs)
+        put = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)   # noqa: E731
+        return {"yref": put(a["yref"]), "pert": {k: put(v) for k, v in a["pert"].items()},
+                "term": {k: put(v) for k, v in a["term"].items()},
+                "obs": {"gain": put(a["gain"]), "d_hat": torch.zeros((len(cfgs), int(cfgs[0]["Nsim"]), 6), dtype=torch.float64, device=dev)},
+                "surf": put(a["surf"]), "warm": put(a["warm"])}
 
     def perturbation_tensors(self, cfgs: Sequence[Dict]):
         """The plant perturbations of a bucket (plant.stack) on this engine's device -- {"wcv", "u_dist", "x_noise"} -- or None when
@@ -691,6 +779,33 @@ class MpcBatchEngine:
         self._check(self.lib.mpcb_step_surf(self._h, C.byref(r), yp, int(bool(ref_changed)), wp, int(bool(reset)), sp,
                                             int(bool(surf_changed)), C.c_void_p(stream)), "mpcb_step_surf")
 
+    def step_combined(self, io, yref=None, ref_changed: bool = False, warm=None, reset: bool = False, term=None,
+                      term_changed: bool = False, dist=None, dist_changed: bool = False, surf=None, surf_changed: bool = False,
+                      stream: Optional[int] = None):
+        """mpcb_step_combined: the controller step in which the terminal cost `term` [batch, 30], the input disturbance `dist`
+        [batch, 6], the surface window `surf` [batch, N, 6] and the warm-start modes `warm` [batch] are in force at once -- each a
+        contiguous device tensor as in step_sens / step_dist / step_surf / step_warm, or None: absent for the whole batch (the
+        library then fills neutral data: zero blocks, d = 0, the packed surface on every row).  A simulation that does not use a
+        feature brings neutral rows itself.  `*_changed`: the step linearises again first.  SQP_RTI and fp64 only."""
+        pb = self._pb
+        for name, t, shape in (("term", term, (pb.batch, 30)), ("dist", dist, (pb.batch, 6)), ("surf", surf, (pb.batch, pb.N, 6))):
+            if t is not None and (not hasattr(t, "data_ptr") or tuple(t.shape) != shape or not t.is_contiguous()
+                                  or str(t.dtype) != "torch.float64" or not t.is_cuda):
+                raise ValueError(f"{name} must be a contiguous float64 device tensor {list(shape)}, got "
+                                 f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t).__name__)}")
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        r = self._step_struct(io)
+
+        def ptr(t, ty=_dp):
+            return C.cast(C.c_void_p(t.data_ptr()), ty) if t is not None else None
+
+        self._check(self.lib.mpcb_step_combined(self._h, C.byref(r), ptr(yref), int(bool(ref_changed)), ptr(warm, _ip), int(bool(reset)),
+                                                ptr(term), int(bool(term_changed)), ptr(dist), int(bool(dist_changed)), ptr(surf),
+                                                int(bool(surf_changed)), C.c_void_p(stream)), "mpcb_step_combined")
+
     def debug_task_lin(self, cfgs: Sequence[Dict], chain, x: np.ndarray) -> np.ndarray:
         """Diagnostic: the device linearisation at points x[i] = [q; qdot] with the parameters of cfgs[i];
         returns [n, 60] records laid out like a G2 stage record (r 0..4, dg/dq 24..53, dg5/dqdot 54..59)."""
@@ -712,6 +827,16 @@ class MpcBatchEngine:
         """setup + all steps; returns (problem, dict of device tensors). Synchronous."""
         pb = self.setup(cfgs, chain)
         bufs = self.alloc_results(pb)
+        comb = self.combined_tensors(cfgs)     # a bucket with combine_features: every table, neutral rows where a feature is off
+        if comb is not None:
+            chunk = step_chunk if step_chunk and step_chunk > 0 else pb.Nsim
+            self.last_kernel_ms = []
+            for s0 in range(0, pb.Nsim, chunk):
+                self.rollout(bufs, s0, min(pb.Nsim, s0 + chunk), combined=True, **comb)
+                self.sync()
+                self.last_kernel_ms.append(self.kernel_ms())
+            bufs["d_hat"] = comb["obs"]["d_hat"]
+            return pb, bufs
         yref = self.schedule_tensor(cfgs)      # sampled and stacked once; every chunk gets the same array
         pert = self.perturbation_tensors(cfgs)
         term = self.terminal_tensors(cfgs)
@@ -738,6 +863,8 @@ class MpcBatchEngine:
         """Same through mpcb_run (library-owned device buffers, numpy in/out, no torch).  mpcb_run takes no reference schedule:
         configurations that carry one are refused, and so are configurations with a plant perturbation, a terminal cost or a
         disturbance observer."""
+        if any(c.get("combine_features") for c in cfgs):
+            raise ValueError("mpcb_run takes no combined features: run configurations with combine_features through run() / run_device()")
         if any(c.get("reference_schedule") is not None for c in cfgs):
             raise ValueError("mpcb_run takes no reference schedule: run configurations with a reference_schedule through run() / run_device()")
         if any(c.get("plant_perturbation") is not None for c in cfgs):

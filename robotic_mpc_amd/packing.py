@@ -62,7 +62,13 @@ def bucket_key(cfg: Dict, ragged: bool = False):
     simulations with a terminal cost (config key terminal_cost: the kernels of mpcb_rollout_term), with or without either, and
     simulations with a disturbance observer (config key disturbance_observer: the kernels of mpcb_rollout_obs; any pole), and
     simulations over a scheduled surface (config key surface_schedule: the kernels of mpcb_rollout_surf; any schedule).  The warm-start mode (config key warm_start)
-    is NOT part of the key: it is chosen per simulation inside one launch (mpcb_rollout_warm), so a grid over it stays one bucket."""
+    is NOT part of the key: it is chosen per simulation inside one launch (mpcb_rollout_warm), so a grid over it stays one bucket.
+    Simulations with combine_features run the combined rollout (mpcb_rollout_combined) whatever subset of the features each uses: for
+    them "combined" stands in the key where the per-feature entries would, so a grid over the features stays one bucket."""
+    if cfg.get("combine_features"):
+        return (cfg["robot_name"], cfg.get("urdf_path"), cfg.get("ee_frame"), tuple(np.asarray(cfg["t_ee"]).tolist()),
+                None if ragged else cfg["N"], cfg["Nsim"], cfg["solver_type"], cfg["max_iter"], cfg["qp_iter_max"],
+                bool(cfg["fixed_step"]), int(cfg.get("precision", 0)), "combined")
     return (cfg["robot_name"], cfg.get("urdf_path"), cfg.get("ee_frame"), tuple(np.asarray(cfg["t_ee"]).tolist()),
             None if ragged else cfg["N"], cfg["Nsim"], cfg["solver_type"], cfg["max_iter"], cfg["qp_iter_max"],
             bool(cfg["fixed_step"]), int(cfg.get("precision", 0)), cfg.get("reference_schedule") is not None) + \

@@ -157,6 +157,8 @@ class Simulator:
         self._errors_rows = rec.get("errors")
         self._summary_row = rec.get("summary")
         self._d_hat = rec.get("d_hat")     # [Nsim, 6] with a disturbance_observer: the estimate every step used
+        if self.resolved.get("combine_features") and self.resolved.get("disturbance_observer") is None:
+            self._d_hat = None             # (a combined bucket logs it for every simulation: zeros without an observer)
         self._data_computed = True
 
     def _invalidate_cache(self):
@@ -325,6 +327,12 @@ class _EngineRunner:
         pb = eng.setup(cfgs, chain)
         with torch.cuda.stream(stream):
             bufs = eng.alloc_results(pb)
+            comb = eng.combined_tensors(cfgs)  # a bucket with combine_features: every table of the combined rollout, or None
+            if comb is not None:
+                eng.rollout(bufs, 0, pb.Nsim, stream=stream.cuda_stream, combined=True, **comb)
+                summary = eng.summary(bufs, stream=stream.cuda_stream)
+                bufs["d_hat"] = comb["obs"]["d_hat"]    # (zeros for a simulation without an observer: Simulator._attach drops them)
+                return eng, stream, bufs, summary, comb
             yref = eng.schedule_tensor(cfgs)   # the bucket's reference schedules, or None (kept alive by the ticket)
             pert = eng.perturbation_tensors(cfgs)   # ... and its plant perturbations, or None (likewise)
             term = eng.terminal_tensors(cfgs)       # ... and its terminal costs, or None (likewise)

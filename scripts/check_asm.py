@@ -40,9 +40,13 @@ STREAM_ROLLOUT_SURF_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_str
 # surface's with Engine::shift_pass / se::shift_pass at the top of a step, under budgets of their own below
 ROLLOUT_SHIFT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_shift.hip")
 STREAM_ROLLOUT_SHIFT_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_shift.hip")
+# the kernels of the combined rollout (mpcb_rollout_combined; modules of their own): the perturbed rollout's on the engine built with
+# its TERM_TABLE, DIST_SHARED and SURF flags at once, with shift_pass after the observer's publication, under budgets of their own
+ROLLOUT_COMBINED_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_rollout_combined.hip")
+STREAM_ROLLOUT_COMBINED_SRC = os.path.join(ROOT, "robotic_mpc_amd", "csrc", "mpc_stream_rollout_combined.hip")
 SOURCES = (SRC, STEP_SRC, STREAM_STEP_SRC, ROLLOUT_REF_SRC, STREAM_ROLLOUT_REF_SRC, ROLLOUT_PERT_SRC, STREAM_ROLLOUT_PERT_SRC,
            ROLLOUT_TERM_SRC, STREAM_ROLLOUT_TERM_SRC, ROLLOUT_OBS_SRC, STREAM_ROLLOUT_OBS_SRC, ROLLOUT_SURF_SRC,
-           STREAM_ROLLOUT_SURF_SRC, ROLLOUT_SHIFT_SRC, STREAM_ROLLOUT_SHIFT_SRC)
+           STREAM_ROLLOUT_SURF_SRC, ROLLOUT_SHIFT_SRC, STREAM_ROLLOUT_SHIFT_SRC, ROLLOUT_COMBINED_SRC, STREAM_ROLLOUT_COMBINED_SRC)
 
 
 def scan(asm_text):
@@ -121,6 +125,13 @@ BUDGET = {
     "24mpc_rollout_shift_kernelILi8ELi1E": 258, "24mpc_rollout_shift_kernelILi4ELi2E": 333, "24mpc_rollout_shift_kernelILi4ELi1E": 68,
     "29mpc_rollout_shift_surf_kernelILi8ELi1E": 255, "29mpc_rollout_shift_surf_kernelILi4ELi2E": 334, "29mpc_rollout_shift_surf_kernelILi4ELi1E": 70,
     "23mpc_stream_shift_kernelId": 164, "28mpc_stream_shift_surf_kernelId": 158,
+    # the combined rollout (recorded: 279 / 347 / 66 for the kernel bodies against the observer rollout's 265 / 328 / 61 -- the terminal
+    # pointers, the surface pointer and the observer's registers are live across the step together -- 168 for the throughput engine's
+    # against 164; its NLP pass with the terminal terms, the effective input and the row's coefficients 54 / 50 / 2)
+    "27mpc_rollout_combined_kernelILi8ELi1E": 307, "27mpc_rollout_combined_kernelILi4ELi2E": 382, "27mpc_rollout_combined_kernelILi4ELi1E": 73,
+    "26mpc_stream_combined_kernelId": 185,
+    "DevExecILi8ELi1EELi2ELi2ELi1EE10nlp_directILb1ELb1E": 60, "DevExecILi4ELi2EELi2ELi2ELi1EE10nlp_directILb1ELb1E": 55,
+    "DevExecILi4ELi1EELi2ELi2ELi1EE10nlp_directILb1ELb1E": 8,
 }
 
 
